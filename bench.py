@@ -23,6 +23,13 @@ Multi-GPU: one process per GPU over RCCL.  Either launch through
 WORLD_SIZE unset this process -- before it touches any GPU -- starts the N
 ranks as a child ``torch.distributed.run`` and exits with its code.  Fewer
 visible GPUs than requested is an error, never a silent 1-GPU run.
+
+A plain run times the steps and prints the headline; `--full` adds the
+per-kernel profile and roofline, the all-reduce summary of a multi-rank line,
+the CPU baseline and (c3) the secondary legs.  `--dump-outputs DIR` writes
+what the last timed step computed, for comparing two builds output for output:
+every step of an epoch workload computes the same epoch from the same inputs
+(restored before it, outside the clock), so runs differ by rounding only.
 """
 import argparse
 import collections
@@ -68,6 +75,15 @@ def parse():
                         "compute in a multi-GPU line")
     p.add_argument("--breakdown", action="store_true",
                    help="print the per-kernel time breakdown to stderr")
+    p.add_argument("--full", action="store_true",
+                   help="everything beside the headline: the per-kernel "
+                   "profile and roofline, the all-reduce summary of a "
+                   "multi-rank line, the CPU baseline and (c3) the secondary "
+                   "legs")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="after the timed steps, write what the last step "
+                   "computed as DIR/<name>.npy (float32 / float64, at most "
+                   "64 MB: a seeded sample of a larger output)")
     a = p.parse_args()
     short = a.workload.startswith(("fwd", "adj")) or a.workload == "c1"  # ms-sized steps
     if a.steps is None:
@@ -492,13 +508,15 @@ def epoch_problem(workload, positions, world, rank, tp, A, data_on_host=False):
     p = dict(full, scan=full["scan"][idx])
     N = len(idx)
     np.random.seed(1234 + rank)
+    # (the minibatch order and the position fits draw from it: seeded, every
+    # run of a workload computes the same epochs)
+    import tike_amd.random
+    tike_amd.random.randomizer_np = np.random.default_rng(4321)
     eigen_probe = eigen_weights = None
     C = 0
     # (the two-slice workload runs without eigen probes, like the reference's
     # multislice test and tools/soak_multislice.py)
     if workload.startswith("c3") and workload not in MULTISLICE:
-        import tike_amd.random
-        tike_amd.random.randomizer_np = np.random.default_rng(4321)
         eigen_probe, eigen_weights = tp.init_varying_probe(
             p["scan"], p["probe"], num_eigen_probes=2, probes_with_modes=1)
         C = eigen_probe.shape[-4]
@@ -735,6 +753,39 @@ def allreduce_probe(nbytes, world, torch, dist, calls=100):
                 (ms * 1e-3) / 1e9, backend=dist.get_backend())
 
 
+DUMP_BYTES = 64 * 10**6
+
+
+def dump_outputs(directory, arrays):
+    """Write {name: array or device tensor} as directory/<name>.npy: complex
+    as float32 / float64 with a trailing (real, imag) axis.  The smallest
+    arrays are written whole first; one that exceeds its fair share of what
+    is left of DUMP_BYTES keeps a seeded sample of its rows (of its elements
+    when one row is too large), taken before it leaves the device."""
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    out = {}
+    for name, x in arrays.items():
+        t = torch.as_tensor(x)
+        if t.is_complex():
+            t = torch.view_as_real(t)
+        out[name] = t.to(torch.float64 if t.dtype in (torch.float64,
+                                                      torch.int64)
+                         else torch.float32)
+    left = DUMP_BYTES
+    for i, name in enumerate(sorted(out, key=lambda k: out[k].nbytes)):
+        t = out[name]
+        cap = left // (len(out) - i)
+        if t.nbytes > cap:
+            if t.ndim < 2 or t[0].nbytes > cap:
+                t = t.reshape(-1)
+            rows = np.random.default_rng(0).choice(
+                len(t), cap // t[0].nbytes, replace=False)
+            t = t[torch.as_tensor(np.sort(rows), device=t.device)]
+        np.save(os.path.join(directory, name + ".npy"), t.cpu().numpy())
+        left -= t.nbytes
+
+
 def main():
     a = parse()
     env_world = os.environ.get("WORLD_SIZE")
@@ -776,7 +827,11 @@ def main():
     from tike_amd._lib import _PROTOTYPES, lib
     from tike_amd.ptycho.solvers.lstsq import chunk_positions
 
-    timers = KernelTimers(lib, [n for n in _PROTOTYPES if n != "tike_init"])
+    # the per-kernel profile (--full, --breakdown) brackets launches with
+    # events; a plain run wraps nothing
+    profiling = a.full or a.breakdown
+    timers = KernelTimers(lib, [n for n in _PROTOTYPES if n != "tike_init"]
+                          if profiling else [], pool=8192 if profiling else 0)
     timers.label_cost_only = a.workload in ("c1", "c2") + MULTISLICE
     if a.workload in MULTISLICE:
         global MULTISLICE_DEPTH
@@ -784,6 +839,7 @@ def main():
         timers.cost_only_suffix = ":no_patches"
         timers.modes = EPOCH_DEFAULTS[a.workload][1]
     counts = dict(epoch=0, steps=0, in_minibatch=False)
+    prepare = None  # restores a step's inputs before it (not timed)
     cpu = None
     cpu_job = None
     C = 0
@@ -802,8 +858,9 @@ def main():
         def step():
             op.fwd_device(probe, scan, psi, out=out)
 
+        outputs = lambda: dict(farplane=out)
         units, launch_n, dominant = N, N, "tike_ptycho_fwd"
-        if rank == 0 and not a.no_cpu_baseline and world == 1:
+        if a.full and rank == 0 and not a.no_cpu_baseline and world == 1:
             cpu_job = lambda: cpu_baseline_fwd(p, S, det)
         workload = dict(workload=a.workload, positions_per_gpu=N, modes=S,
                         detector=det, solver=None)
@@ -816,8 +873,9 @@ def main():
         def step():
             op.adj_device(*adj_args, psi_adj=adj_out[0], probe_adj=adj_out[1])
 
+        outputs = lambda: dict(psi_adj=adj_out[0], probe_adj=adj_out[1])
         units, launch_n, dominant = N, N, "tike_ptycho_adj"
-        if rank == 0 and not a.no_cpu_baseline and world == 1:
+        if a.full and rank == 0 and not a.no_cpu_baseline and world == 1:
             cpu_job = lambda: cpu_baseline_adj(p, S, det)
         workload = dict(workload=a.workload, positions_per_gpu=N, modes=S,
                         detector=det, solver=None,
@@ -833,32 +891,33 @@ def main():
         ctx, p, data = built["ctx"], built["p"], built["data"]
         det, S, N, C = built["det"], built["S"], built["N"], built["C"]
         num_batch = built["num_batch"]
-        # every all-reduce, timed like a kernel
-        n_object = 2 * p["HW"]**2  # float32 words of the object-gradient slice
+        if profiling:
+            # every all-reduce, timed like a kernel
+            n_object = 2 * p["HW"]**2  # float32 words of the object gradient
 
-        def which(*tensors):
-            words = sum(t.numel() * (2 if t.is_complex() else 1)
-                        for t in tensors)
-            return "allreduce:object" if words >= n_object else "allreduce"
+            def which(*tensors):
+                words = sum(t.numel() * (2 if t.is_complex() else 1)
+                            for t in tensors)
+                return "allreduce:object" if words >= n_object else "allreduce"
 
-        timers.wrap_method(ctx.comm, "Allreduce", which)
-        # ... and counted apart where it is issued once per epoch
-        # (preconditioners, eigen-weight norms: outside the minibatch loop)
-        import tike_amd.ptycho.solvers.lstsq as _L
-        _grads = _L._get_nearplane_gradients
-        _inner = ctx.comm.Allreduce
+            timers.wrap_method(ctx.comm, "Allreduce", which)
+            # ... and counted apart where it is issued once per epoch
+            # (preconditioners, eigen-weight norms: outside the minibatch loop)
+            import tike_amd.ptycho.solvers.lstsq as _L
+            _grads = _L._get_nearplane_gradients
+            _inner = ctx.comm.Allreduce
 
-        def _count_epoch(*t):
-            if timers.enabled and not counts["in_minibatch"]:
-                counts["epoch"] += 1
-            return _inner(*t)
+            def _count_epoch(*t):
+                if timers.enabled and not counts["in_minibatch"]:
+                    counts["epoch"] += 1
+                return _inner(*t)
 
-        def _gradients(*args, **kw):
-            counts["in_minibatch"] = True  # (until the epoch's loop ends)
-            return _grads(*args, **kw)
+            def _gradients(*args, **kw):
+                counts["in_minibatch"] = True  # (until the epoch's loop ends)
+                return _grads(*args, **kw)
 
-        ctx.comm.Allreduce = _count_epoch
-        _L._get_nearplane_gradients = _gradients
+            ctx.comm.Allreduce = _count_epoch
+            _L._get_nearplane_gradients = _gradients
 
         def step():
             counts["in_minibatch"] = False
@@ -866,10 +925,42 @@ def main():
                 counts["steps"] += 1
             ctx.iterate(1)
 
+        # Every step computes the same epoch from the same inputs: the
+        # estimates with their options and the package's generator are put
+        # back before each step.  Chained epochs would carry the order in
+        # which float atomics add from run to run, and this iteration
+        # amplifies it.  (The exit-wave options are configuration and hold
+        # the mask cache: shared, not copied.)
+        import copy
+        import tike_amd.random as trandom
+        shared = lambda: {id(ctx.parameters.exitwave_options):
+                          ctx.parameters.exitwave_options}
+        start = (copy.deepcopy(ctx.parameters, shared()),
+                 copy.deepcopy(trandom.randomizer_np), np.random.get_state())
+
+        def prepare():
+            ctx.parameters = copy.deepcopy(start[0], shared())
+            trandom.randomizer_np = copy.deepcopy(start[1])
+            np.random.set_state(start[2])
+
+        def outputs():
+            # the estimates a caller reads back, and the last cost (every
+            # rank takes part: the positions are gathered).  Not through
+            # get_result(): it re-checks the positions, and c5's correction
+            # may move one onto the object's edge
+            probe_, eigen_probe, eigen_weights = ctx.get_probe()
+            got = dict(psi=ctx.get_psi(), probe=probe_, scan=ctx.get_scan(),
+                       cost=np.asarray(ctx.get_convergence()[0][-1],
+                                       np.float64))
+            if eigen_probe is not None:
+                got.update(eigen_probe=eigen_probe,
+                           eigen_weights=eigen_weights)
+            return got
+
         units = N
         launch_n = min(chunk_positions(S, det, True), N // num_batch)
         dominant = None
-        if (rank == 0 and not a.no_cpu_baseline and world == 1
+        if (a.full and rank == 0 and not a.no_cpu_baseline and world == 1
                 and a.workload in ("c1", "c2", "c3", "c5")):
             # (the slice the host leg works on; the leg itself runs AFTER
             # everything timed on the GPU: its 256 FFT threads, run first, cost
@@ -904,6 +995,8 @@ def main():
     # the timed steps is bracketed.
     profile = None
     for _ in range(a.warmup):
+        if prepare:
+            prepare()
         step()
     # cgrad replays its CG calls from captured graphs: launches inside a
     # replay cannot be bracketed, so the per-kernel shares (and the dominant
@@ -911,14 +1004,16 @@ def main():
     # steps run as users run them (graphs on, no events)
     import importlib
     _cg = importlib.import_module("tike_amd.ptycho.solvers.cgrad")
-    graphs_on = _cg.USE_GRAPHS and a.workload in ("c1", "c2")
+    graphs_on = profiling and _cg.USE_GRAPHS and a.workload in ("c1", "c2")
     if graphs_on:
         _cg.USE_GRAPHS = False
-    if a.warmup > 0:
+    if profiling and a.warmup > 0:
         # twice: torch creates the HIP event behind a pooled Event object at
         # its first record(), which the first bracketed step pays for
         for _ in range(2):
             timers.reset()
+            if prepare:
+                prepare()
             torch.cuda.synchronize()
             timers.enabled = True
             tp0 = time.perf_counter()
@@ -936,24 +1031,37 @@ def main():
         _cg.USE_GRAPHS = True
         if profile is not None:
             timers.only = set()
+            if prepare:
+                prepare()
             step()  # the occurrence that captures
             torch.cuda.synchronize()
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    timers.enabled = True
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-        step()
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    wall = time.perf_counter() - t0
-    timers.enabled = False
+    # the timed steps: back to back, or -- inputs to restore -- one at a
+    # time with the restore outside the clock
+    wall = 0.0
+    for n in [1] * a.steps if prepare else [a.steps]:
+        if prepare:
+            prepare()
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        timers.enabled = profiling
+        t0 = time.perf_counter()
+        for _ in range(n):
+            step()
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        wall += time.perf_counter() - t0
+        timers.enabled = False
     if world > 1:
         t = torch.tensor([wall], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
+    if a.dump_outputs:
+        got = outputs()
+        if rank == 0:
+            dump_outputs(a.dump_outputs, got)
+        del got
 
     plans = list(getattr(getattr(ctx, "operator", None), "_tike_amd_plans",
                          {}).values()) if ctx is not None else []
@@ -974,7 +1082,7 @@ def main():
         probe_line = allreduce_probe(8 * p["HW"]**2, world, torch, dist)
 
     secondary = None
-    if (rank == 0 and world == 1 and a.workload == "c3"
+    if (a.full and rank == 0 and world == 1 and a.workload == "c3"
             and not a.no_secondary):
         # the forward operator alone (north_star's 60 % target), driver-timed
         if ctx is not None:
@@ -1022,83 +1130,85 @@ def main():
             secondary.append(leg)
 
     if rank == 0:
-        summ = timers.summary()  # the timed steps
-        # every launch bracketed: the last warm-up step, or (--warmup 0) the
-        # timed steps themselves
-        full, full_wall = profile if profile is not None else (summ, wall)
-        kernels = {k: v for k, v in full.items() if k.startswith("tike_")}
-        pw = p.get("pw", det) if isinstance(p, dict) else det
-        if dominant is None:
-            dominant = dominant_entry(full, launch_n, S, det, C, pw)
-        k = summ.get(dominant) or full[dominant]
-        if k.get("positions"):
-            # launches of different sizes under one entry: the mean launch
-            launch_n = k["positions"] / k["calls"]
-        nbytes = algorithmic_bytes(dominant, launch_n, S, det, pw, C)
-        achieved = nbytes / (k["avg_ms"] * 1e-3) / 1e9
-        ktot = sum(v["total_ms"] for v in kernels.values())
-        if a.breakdown:
-            for name, v in sorted(full.items(),
-                                  key=lambda kv: -kv[1]["total_ms"]):
-                print(f"  {name:32s} calls {v['calls']:5d} avg {v['avg_ms']:8.3f} ms"
-                      f" total {v['total_ms']:9.2f} ms ({100 * v['total_ms'] / ktot:4.1f}%)",
-                      file=sys.stderr)
-            print(f"  kernels {ktot:.1f} ms of wall {full_wall * 1e3:.1f} ms "
-                  f"({100 * ktot / (full_wall * 1e3):.1f} %)", file=sys.stderr)
-        per_launch, per_step, pmc_file = measured_traffic(a.workload, launch_n)
         aggregate = units * world * a.steps / wall
-        roofline = {
-            "bound": "hbm", "kernel": dominant,
-            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBS,
-            "traffic": per_launch.get(dominant),
-            "algorithmic_bytes": nbytes,
-            "avg_launch_ms": k["avg_ms"], "positions_per_launch": launch_n,
-            "share_of_kernel_time": full[dominant]["total_ms"] / ktot,
-            "kernel_time_share_of_wall": ktot / (full_wall * 1e3),
-            "events": "timed steps: this kernel only; shares: an untimed "
-                      "step after the warm-up, every launch bracketed"
-            if profile is not None else "timed steps: every launch bracketed",
-        }
-        if roofline["traffic"]:
-            # the same launch priced on the bytes the counters saw cross the
-            # HBM interface (an algorithmic figure above the stream ceiling --
-            # c2's composite entry -- is Infinity-Cache hits, not bandwidth)
-            moved = roofline["traffic"] / (k["avg_ms"] * 1e-3) / 1e9
-            roofline["traffic_achieved"] = moved
-            roofline["traffic_frac"] = moved / HBM_PEAK_GBS
-        if graphs_on:
-            roofline["events"] = (
-                "launch time and shares: an untimed step launched one by one "
-                "after the warm-up; the timed steps replay captured graphs "
-                "(no events inside a replay)")
-        if not nbytes:
-            # an entry that runs a data-dependent number of passes (the
-            # device-side line search): no byte model, no fraction
-            roofline["achieved"] = roofline["frac"] = None
-            roofline["note"] = ("no algorithmic-byte model for this entry "
-                                "(data-dependent number of trial passes)")
-        elif roofline["frac"] > READ_CEILING_GBS / HBM_PEAK_GBS and (
-                roofline["traffic"] is None):
-            # a rate above what a pure read stream reaches on this chip can only
-            # come from cache hits inside the launch: not stated without the
-            # counters that show them
-            roofline["frac_withheld"] = (
-                f"algorithmic bytes / time = {achieved:.0f} GB/s exceeds the "
-                f"measured read-stream ceiling ({READ_CEILING_GBS:.0f} GB/s) and "
-                "no PMC traffic figure is committed for this kernel")
-            roofline["achieved"] = roofline["frac"] = None
-        if not a.workload.startswith(("fwd", "adj")):
-            # the whole iteration against SURVEY 8(d)'s compulsory bytes and
-            # flops (report both fractions)
-            b_iter, f_iter = iteration_bounds(S, det, pw)
-            per_gpu_rate = units * a.steps / wall
-            roofline["iteration_hbm_frac"] = (b_iter * per_gpu_rate / 1e9 /
-                                              HBM_PEAK_GBS)
-            roofline["iteration_fp32_frac"] = (f_iter * per_gpu_rate / 1e12 /
-                                               FP32_PEAK_TFLOPS)
-            roofline["traffic_per_step"] = per_step
-            roofline["traffic_source"] = pmc_file
+        roofline = None
+        if profiling:
+            summ = timers.summary()  # the timed steps
+            # every launch bracketed: the last warm-up step, or (--warmup 0) the
+            # timed steps themselves
+            full, full_wall = profile if profile is not None else (summ, wall)
+            kernels = {k: v for k, v in full.items() if k.startswith("tike_")}
+            pw = p.get("pw", det) if isinstance(p, dict) else det
+            if dominant is None:
+                dominant = dominant_entry(full, launch_n, S, det, C, pw)
+            k = summ.get(dominant) or full[dominant]
+            if k.get("positions"):
+                # launches of different sizes under one entry: the mean launch
+                launch_n = k["positions"] / k["calls"]
+            nbytes = algorithmic_bytes(dominant, launch_n, S, det, pw, C)
+            achieved = nbytes / (k["avg_ms"] * 1e-3) / 1e9
+            ktot = sum(v["total_ms"] for v in kernels.values())
+            if a.breakdown:
+                for name, v in sorted(full.items(),
+                                      key=lambda kv: -kv[1]["total_ms"]):
+                    print(f"  {name:32s} calls {v['calls']:5d} avg {v['avg_ms']:8.3f} ms"
+                          f" total {v['total_ms']:9.2f} ms ({100 * v['total_ms'] / ktot:4.1f}%)",
+                          file=sys.stderr)
+                print(f"  kernels {ktot:.1f} ms of wall {full_wall * 1e3:.1f} ms "
+                      f"({100 * ktot / (full_wall * 1e3):.1f} %)", file=sys.stderr)
+            per_launch, per_step, pmc_file = measured_traffic(a.workload, launch_n)
+            roofline = {
+                "bound": "hbm", "kernel": dominant,
+                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS,
+                "traffic": per_launch.get(dominant),
+                "algorithmic_bytes": nbytes,
+                "avg_launch_ms": k["avg_ms"], "positions_per_launch": launch_n,
+                "share_of_kernel_time": full[dominant]["total_ms"] / ktot,
+                "kernel_time_share_of_wall": ktot / (full_wall * 1e3),
+                "events": "timed steps: this kernel only; shares: an untimed "
+                          "step after the warm-up, every launch bracketed"
+                if profile is not None else "timed steps: every launch bracketed",
+            }
+            if roofline["traffic"]:
+                # the same launch priced on the bytes the counters saw cross the
+                # HBM interface (an algorithmic figure above the stream ceiling --
+                # c2's composite entry -- is Infinity-Cache hits, not bandwidth)
+                moved = roofline["traffic"] / (k["avg_ms"] * 1e-3) / 1e9
+                roofline["traffic_achieved"] = moved
+                roofline["traffic_frac"] = moved / HBM_PEAK_GBS
+            if graphs_on:
+                roofline["events"] = (
+                    "launch time and shares: an untimed step launched one by one "
+                    "after the warm-up; the timed steps replay captured graphs "
+                    "(no events inside a replay)")
+            if not nbytes:
+                # an entry that runs a data-dependent number of passes (the
+                # device-side line search): no byte model, no fraction
+                roofline["achieved"] = roofline["frac"] = None
+                roofline["note"] = ("no algorithmic-byte model for this entry "
+                                    "(data-dependent number of trial passes)")
+            elif roofline["frac"] > READ_CEILING_GBS / HBM_PEAK_GBS and (
+                    roofline["traffic"] is None):
+                # a rate above what a pure read stream reaches on this chip can only
+                # come from cache hits inside the launch: not stated without the
+                # counters that show them
+                roofline["frac_withheld"] = (
+                    f"algorithmic bytes / time = {achieved:.0f} GB/s exceeds the "
+                    f"measured read-stream ceiling ({READ_CEILING_GBS:.0f} GB/s) and "
+                    "no PMC traffic figure is committed for this kernel")
+                roofline["achieved"] = roofline["frac"] = None
+            if not a.workload.startswith(("fwd", "adj")):
+                # the whole iteration against SURVEY 8(d)'s compulsory bytes and
+                # flops (report both fractions)
+                b_iter, f_iter = iteration_bounds(S, det, pw)
+                per_gpu_rate = units * a.steps / wall
+                roofline["iteration_hbm_frac"] = (b_iter * per_gpu_rate / 1e9 /
+                                                  HBM_PEAK_GBS)
+                roofline["iteration_fp32_frac"] = (f_iter * per_gpu_rate / 1e12 /
+                                                   FP32_PEAK_TFLOPS)
+                roofline["traffic_per_step"] = per_step
+                roofline["traffic_source"] = pmc_file
         # `value` is the whole-job rate over all ranks (bench contract).  On one
         # GPU that IS BASELINE.json's "patterns/sec/GPU"; on several the label
         # says "whole job" so that nobody reads N x the per-GPU rate under a
@@ -1123,10 +1233,11 @@ def main():
             "data": ("synthetic" if not share_gpu else
                      "synthetic; TEST SWITCH: ranks share a GPU over gloo"),
             "config": workload,
-            "roofline": roofline,
         }
-        if (world > 1 or forced) and ("allreduce" in summ
-                                      or "allreduce:object" in summ):
+        if roofline is not None:
+            line["roofline"] = roofline
+        if profiling and (world > 1 or forced) and (
+                "allreduce" in summ or "allreduce:object" in summ):
             # every blocking collective of the timed steps (HIP events around
             # Comm.Allreduce): per minibatch the object-gradient slice + two
             # small packed buffers (the probe-gradient slice is started early

@@ -333,3 +333,35 @@ def test_bench_roofline_kernel_has_a_byte_model():
     T, P = 8 * S * det * det, 8 * det * det
     assert bench.algorithmic_bytes("tike_fwd_pass1", n, S, det, det,
                                    1) == n * (T + 2 * P + 8) + (S + 1) * P
+
+
+def test_bench_dump_stays_within_its_budget(tmp_path):
+    """bench.py --dump-outputs: complex arrays as float pairs, small arrays
+    whole, a larger one as the same seeded sample of its rows every time,
+    at most DUMP_BYTES in all."""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location(
+        "bench_module", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(0)
+    far = (rng.random((300, 1, 1, 128, 128)) +
+           1j * rng.random((300, 1, 1, 128, 128))).astype(np.complex64)
+    cost = np.array([1.5, 2.5])
+    for d in ("a", "b"):
+        bench.DUMP_BYTES = 10**7  # far (39 MB) must be sampled
+        bench.dump_outputs(str(tmp_path / d), dict(far=far, cost=cost))
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("far", "cost")}
+    b = np.load(tmp_path / "b" / "far.npy")
+    assert a["cost"].dtype == np.float64 and a["cost"].tolist() == [1.5, 2.5]
+    assert a["far"].dtype == np.float32 and a["far"].shape[1:] == (
+        1, 1, 128, 128, 2)
+    assert a["far"].nbytes + a["cost"].nbytes <= 10**7
+    assert 0 < len(a["far"]) < 300 and np.array_equal(a["far"], b)
+    rows = [np.flatnonzero((far.real == x[..., 0]).all(axis=(1, 2, 3, 4)))
+            for x in a["far"][:3]]
+    assert all(len(i) == 1 for i in rows)
+    np.testing.assert_array_equal(
+        a["far"][0][..., 1], far[rows[0][0]].imag)

@@ -1642,7 +1642,7 @@ def test_bench_whole_job_line_of_two_ranks():
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", "29541", os.path.join(root, "bench.py"), "--gpus",
          "2", "--steps", "2", "--warmup", "1", "--positions", "160",
-         "--allreduce-probe"],
+         "--allreduce-probe", "--full"],
         env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -1723,9 +1723,9 @@ def test_bench_rccl_path_through_the_launcher():
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node=1", "--master-addr", "127.0.0.1", "--master-port",
          "29533", os.path.join(root, "bench.py"), "--gpus", "1", "--steps",
-         "1", "--warmup", "1", "--positions", "200", "--no-cpu-baseline",
-         "--no-secondary"], env=env, capture_output=True, text=True,
-        timeout=900)
+         "1", "--warmup", "1", "--positions", "200", "--full",
+         "--no-cpu-baseline", "--no-secondary"], env=env, capture_output=True,
+        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["value"] > 0
@@ -1740,6 +1740,48 @@ def test_bench_rccl_path_through_the_launcher():
     assert line["collective_backend"] == "nccl" and line["rccl_ranks"] == 1
     assert line["ranks_agree"] == 0.0
     assert 0 < line["roofline"]["iteration_hbm_frac"] < 1
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run times its steps and prints the headline alone (the
+    profile, roofline, CPU baseline and secondary legs are --full's);
+    --dump-outputs writes what a caller of the last step receives, and two
+    runs with the same arguments write the same outputs up to rounding."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    runs = []
+    for run in ("a", "b"):
+        r = subprocess.run(
+            [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1",
+             "--steps", "3", "--warmup", "1", "--positions", "200",
+             "--dump-outputs", str(tmp_path / run)], env=env,
+            capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        runs.append({f[:-4]: np.load(tmp_path / run / f)
+                     for f in os.listdir(tmp_path / run)})
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["warmup"] == 1
+    assert line["value"] > 0 and line["unit"] == "patterns/s"
+    np.testing.assert_allclose(line["value"],
+                               200 / (line["ms_per_step"] * 1e-3), rtol=1e-6)
+    assert not {"roofline", "secondary", "cpu_baseline"} & set(line)
+    got = runs[0]
+    assert set(got) == {"psi", "probe", "scan", "cost", "eigen_probe",
+                        "eigen_weights"}
+    assert all(x.dtype in (np.float32, np.float64) for x in got.values())
+    assert sum(x.nbytes for x in got.values()) <= 64 * 10**6
+    # complex arrays carry a trailing (real, imag) axis
+    assert got["probe"].shape == (1, 1, 8, 256, 256, 2)
+    assert got["scan"].shape == (200, 2) and np.isfinite(got["cost"]).all()
+    # float atomics add in any order: rounding, not an epoch-on-epoch drift
+    for name, x in got.items():
+        assert_close(runs[1][name], x, normwise=2e-6, maxabs=np.inf,
+                     what=name)
 
 
 @pytest.mark.parametrize("tag", ["epie", "object", "twoslice", "poisson",

@@ -9,12 +9,12 @@ export TMPDIR=/tmp
 o=gpurun_out
 mkdir -p $o/profiles_$tag
 # 1. the bench lines
-python3 bench.py > $o/profiles_$tag/${tag}_bench_c3.json 2> $o/${tag}_bench_c3.err
-python3 bench.py --workload c2 --no-cpu-baseline > $o/profiles_$tag/${tag}_bench_c2.json 2>/dev/null
-python3 bench.py --workload c5 --no-cpu-baseline --steps 3 > $o/profiles_$tag/${tag}_bench_c5.json 2>/dev/null
-python3 bench.py --workload c1 --steps 20 --warmup 10 > $o/profiles_$tag/${tag}_bench_c1.json 2>/dev/null
+python3 bench.py --full > $o/profiles_$tag/${tag}_bench_c3.json 2> $o/${tag}_bench_c3.err
+python3 bench.py --full --workload c2 --no-cpu-baseline > $o/profiles_$tag/${tag}_bench_c2.json 2>/dev/null
+python3 bench.py --full --workload c5 --no-cpu-baseline --steps 3 > $o/profiles_$tag/${tag}_bench_c5.json 2>/dev/null
+python3 bench.py --full --workload c1 --steps 20 --warmup 10 > $o/profiles_$tag/${tag}_bench_c1.json 2>/dev/null
 for w in fwd256x1 fwd256x8 fwd128x1; do
-  python3 bench.py --workload $w --no-cpu-baseline --steps 40 --warmup 8 > $o/profiles_$tag/${tag}_bench_$w.json 2>/dev/null
+  python3 bench.py --full --workload $w --no-cpu-baseline --steps 40 --warmup 8 > $o/profiles_$tag/${tag}_bench_$w.json 2>/dev/null
 done
 # 2. kernel-trace summary of the default command
 rm -rf $o/${tag}_prof_c3
@@ -45,5 +45,5 @@ cp $o/${tag}_inst_mix.md $o/profiles_$tag/${tag}_inst_mix_dynamic.md
 # 6. SQ stall counters of the 128^2 forward kernel (north_star's 60 % target)
 bash tools/pmc_cmd.sh fwd128_lds_kernel python3 bench.py --workload fwd128x1 --no-cpu-baseline --steps 5 --warmup 1 > $o/profiles_$tag/${tag}_pmc_sq_fwd128.txt 2>&1
 # 7. the re-benched default line last (the box is warm)
-python3 bench.py > $o/profiles_$tag/${tag}_bench_c3.json 2> $o/${tag}_bench_c3.err
+python3 bench.py --full > $o/profiles_$tag/${tag}_bench_c3.json 2> $o/${tag}_bench_c3.err
 cat $o/profiles_$tag/${tag}_bench_c3.json

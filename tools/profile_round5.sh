@@ -8,13 +8,13 @@ export TMPDIR=/tmp
 o=gpurun_out
 mkdir -p $o/profiles_$tag
 if [ $part = bench ] || [ $part = all ]; then
-  python3 bench.py > $o/profiles_$tag/${tag}_bench_c3.json 2> $o/${tag}_bench_c3.err
-  python3 bench.py --workload c1 --steps 20 --warmup 10 > $o/profiles_$tag/${tag}_bench_c1.json 2>/dev/null
+  python3 bench.py --full > $o/profiles_$tag/${tag}_bench_c3.json 2> $o/${tag}_bench_c3.err
+  python3 bench.py --full --workload c1 --steps 20 --warmup 10 > $o/profiles_$tag/${tag}_bench_c1.json 2>/dev/null
   for w in c2 c5 c3poisson c3rpie c3rpie2; do
-    python3 bench.py --workload $w --no-cpu-baseline --steps 3 > $o/profiles_$tag/${tag}_bench_$w.json 2>/dev/null
+    python3 bench.py --full --workload $w --no-cpu-baseline --steps 3 > $o/profiles_$tag/${tag}_bench_$w.json 2>/dev/null
   done
   for w in fwd256x1 fwd256x8 fwd128x1 adj256x1 adj256x8 adj128x1; do
-    python3 bench.py --workload $w --no-cpu-baseline --steps 40 --warmup 8 > $o/profiles_$tag/${tag}_bench_$w.json 2>/dev/null
+    python3 bench.py --full --workload $w --no-cpu-baseline --steps 40 --warmup 8 > $o/profiles_$tag/${tag}_bench_$w.json 2>/dev/null
   done
 fi
 if [ $part = stats ] || [ $part = all ]; then

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 o=gpurun_out
 python -m pytest tests/test_operators_gpu.py tests/test_solvers_gpu.py -m gpu -x -q -k "ptycho or full_size or headline_shapes" 2>&1 | tail -15 > $o/r05_adj_tests.txt
 for w in adj256x1 adj128x1 adj256x8 fwd256x1; do
-  python bench.py --workload $w --no-cpu-baseline 2>/dev/null | tail -1 > $o/r05_bench_$w.json
+  python bench.py --full --workload $w --no-cpu-baseline 2>/dev/null | tail -1 > $o/r05_bench_$w.json
   python - $o/r05_bench_$w.json <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1]))

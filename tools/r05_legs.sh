@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 o=gpurun_out; tag=${1:-x}; shift
 ws=${@:-adj256x1 adj128x1 adj256x8 fwd256x1}
 for w in $ws; do
-  python bench.py --workload $w --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 > $o/r05_bench_${w}_$tag.json
+  python bench.py --full --workload $w --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 > $o/r05_bench_${w}_$tag.json
   python - $o/r05_bench_${w}_$tag.json <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1]))
