@@ -38,7 +38,7 @@ extern "C" {
  * A binding compares tike_abi_version() of the loaded library with the
  * TIKE_ABI_VERSION it was written against before its first call
  * (tike_amd/_lib.py does; INTEGRATION.md shows the check). */
-#define TIKE_ABI_VERSION 11
+#define TIKE_ABI_VERSION 12
 
 /* sha256 (64 hex digits) of the sources the library was built from: the PMC
  * traffic files under profiles/ carry it, and bench.py withholds a traffic
@@ -922,6 +922,61 @@ int tike_lstsq_tail_finish(const float* tail3, const float* sums3, double count,
                            long nprobe, float* weights, long weights_row, int S, int m,
                            const float* stats, const float* sums5, int B, int npix,
                            void* stream);
+
+/* ---- the single-rank form of the packed tail for ONE eigen probe: the two
+ * per-position passes (step statistics; eigen position sums) become one, since
+ * the eigen projection is split as
+ *   eigen_proj[n] = q[n] - sum_p Re(mpu_0 conj(E_0)),
+ *   q[n] = sum_p Re(conj(O_n) chi_n,0 conj(E_0))
+ * and q comes out of pass 2, which holds those values already:
+ *
+ *   tike_ifft2_pass2_gradients_eproj              (+ q)
+ *   tike_eigen_pixel_update1q                     update += sum_n R_n pm[n]
+ *   tike_lstsq_step_stats_eigen1                  nacc; stats and sums5 (against E')
+ *   tike_lstsq_tail_solve1                        eigen0 <- E'; sums3, tail3
+ *   tike_lstsq_tail_finish                        weights, probe, steps
+ *
+ * tike_ifft2_pass2_gradients_eproj: tike_ifft2_pass2_gradients (det 128 or 256,
+ *   objproj, num_eigen >= 1, eigen_modes >= 1; TIKE_ERR_UNSUPPORTED otherwise) and
+ *   q (nscan) f32 as above for the first eigen probe of mode 0; qtab: scratch of
+ *   nscan * det / 4 floats.  Deterministic in either mode.
+ * tike_eigen_pixel_update1q: tike_eigen_pixel_update1 (no sums3) with
+ *   eigen_proj formed from q on the fly; eproj_out (nscan) receives it, or NULL;
+ *   c0part: scratch of 64 floats.
+ * tike_lstsq_step_stats_eigen1: nacc[0..2] += { sum |update|^2, sum |eigen0|^2,
+ *   sum Re(conj(eigen0) update) } (nacc zero on entry; eigen0 = mode 0 of the first
+ *   eigen probe), then stats (nscan,8) as tike_lstsq_step_stats (stored patches,
+ *   the preconditioned object update and the probe update given; one eigen probe,
+ *   eigen_weights (nscan,2,S)) and sums5 (nscan,5) as tike_eigen_position_sums1
+ *   against E' = normalise(eigen0 + beta_eigen u / mnorm(u)), u = update / count,
+ *   in one pass; eigen0 itself is not written.  Probe windows of 256 k pixels a
+ *   side or dividing 256, H W < 2^28: TIKE_ERR_UNSUPPORTED otherwise.
+ * tike_lstsq_tail_solve1: eigen0 <- E' (from nacc); sums3 = tike_lstsq_step_sums
+ *   (stats, costs, B, eps), tail3[0..1] the solves of tike_lstsq_tail_mid with them
+ *   and tail3[2] = sum_n sums5[n][2] / npix.  One rank only: no all-reduce sits
+ *   between the sums and the solves. */
+int tike_ifft2_pass2_gradients_eproj(const void* work, const void* patches, const void* probe,
+                                     const void* eigen_probe, const float* eigen_weights,
+                                     int num_eigen, int eigen_modes, void* objproj, void* chi0,
+                                     void* m_probe_update, float mpu_scale, int nscan, int S,
+                                     int det, float inv_scale, float* qtab, float* q,
+                                     void* stream);
+int tike_eigen_pixel_update1q(const void* patches, const void* chi0, const void* mpu0,
+                              const void* eigen0, const float* q, const float* weights_c,
+                              long weights_row, const float* norm, void* update, int nscan,
+                              int pw, int chi_modes, const void* psi, const float* scan, int H,
+                              int W, float* c0part, float* eproj_out, void* stream);
+int tike_lstsq_step_stats_eigen1(const void* chi, const float* scan,
+                                 const void* object_update_precond, const void* probe,
+                                 const void* eigen_probe, const float* eigen_weights,
+                                 int eigen_modes, const void* m_probe_update, const void* patches,
+                                 const void* update, float* nacc, double count, float beta_eigen,
+                                 float* stats, float* sums5, int nscan, int S, int chi_modes,
+                                 int pw, int H, int W, void* stream);
+int tike_lstsq_tail_solve1(void* eigen0, const void* update, int npix, const float* nacc,
+                           float beta_eigen, const float* stats, const float* costs,
+                           const float* sums5, int B, float eps, double count, int recover_psi,
+                           int recover_probe, float* sums3, float* tail3, void* stream);
 
 /* ---- the chunk body of _get_nearplane_gradients (lstsq.py:422-579) in ONE call:
  * the far-plane-free pipeline for a chunk of nscan positions,

@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("TIKE_AMD_LIB") or os.path.join(
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "tike_amd.h")
 
 # the header version this binding's prototypes were written against
-ABI_VERSION = 11
+ABI_VERSION = 12
 ERR_ARG = 1000001
 ERR_UNSUPPORTED = 1000002
 ERR_COMM = 2000000
@@ -158,6 +158,15 @@ _PROTOTYPES = {
                                   _i, _i, _p],
     "tike_lstsq_tail_finish": [_p, _p, _d, _p, _p, _p, _p, _f, _l, _p, _l, _i,
                                _i, _p, _p, _i, _i, _p],
+    "tike_ifft2_pass2_gradients_eproj": [_p, _p, _p, _p, _p, _i, _i, _p, _p,
+                                         _p, _f, _i, _i, _i, _f, _p, _p, _p],
+    "tike_eigen_pixel_update1q": [_p, _p, _p, _p, _p, _p, _l, _p, _p, _i, _i,
+                                  _i, _p, _p, _i, _i, _p, _p, _p],
+    "tike_lstsq_step_stats_eigen1": [_p, _p, _p, _p, _p, _p, _i, _p, _p, _p,
+                                     _p, _d, _f, _p, _p, _i, _i, _i, _i, _i,
+                                     _i, _p],
+    "tike_lstsq_tail_solve1": [_p, _p, _i, _p, _f, _p, _p, _p, _i, _f, _d, _i,
+                               _i, _p, _p, _p],
     "tike_lstsq_chunk_gradients": [_p, _p, _p, _p, _p, _i, _i, _p, _i, _p, _i,
                                    _f, _l, _p, _p, _p, _p, _p, _p, _p, _p, _f,
                                    _p, _i, _i, _i, _i, _i, _f, _f, _p],

@@ -14,6 +14,9 @@ the tests that compare two routes.
   TIKE_CHUNK_POSITIONS=n    kernel chunks of n positions (several per minibatch)
   TIKE_EIGEN_SUMS_GATHER=0  eigen position sums on the stored patches
   TIKE_STATS_GATHER=1       step statistics gather O_n from the object
+  TIKE_FUSED_TAIL=0         one eigen probe, one rank: the staged packed tail
+                            (step statistics and eigen position sums as two
+                            passes) instead of the fused one
   TIKE_PRECOND_CHUNK=n      positions per chunk of the multislice preconditioner
   TIKE_MS_SLICE_STEP=0 / TIKE_MS_FIRST_STORED=0 / TIKE_MS_STEP_BACK=0
                             multislice rpie: the unfused slice step / the
@@ -38,6 +41,7 @@ poisson_steps_in_pass2 = _flag("TIKE_POISSON_LINEAR", True)
 chunk_positions = _int("TIKE_CHUNK_POSITIONS")
 eigen_sums_gather = _flag("TIKE_EIGEN_SUMS_GATHER", True)
 stats_gather = _flag("TIKE_STATS_GATHER", False)
+fused_tail = _flag("TIKE_FUSED_TAIL", True)
 precond_chunk = _int("TIKE_PRECOND_CHUNK", 512)
 multislice_slice_step = _flag("TIKE_MS_SLICE_STEP", True)
 multislice_first_stored = _flag("TIKE_MS_FIRST_STORED", True)

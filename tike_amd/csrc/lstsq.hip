@@ -739,12 +739,19 @@ struct TkModeProbe {  // probe of one (position, mode): uniform values
 // per position (`mid`, `probe`, the weights and `mpu` arrive offset to the
 // first of them; tiles and mode_scale are Stot apart) and, `accumulate`, adds
 // its projection to what the launch of the group in front left in objproj.
-template <int N, int MW, int MPW, bool HAVE_PROJ, bool EIG = true, bool GRP = false>
+// QN (eigen probes in LDS, N <= 256): the wave of mode 0 also forms
+//   q_n = sum_p Re(conj(O_n) chi_n,0 conj(E_0,0))
+// over its pixels from the values it holds, one partial per (position,
+// column-wave of a slice): qtab[(slice * CW + cw) * nscan + n] (plain stores, N / 4
+// partials per position, added up in a fixed order by the launcher).
+template <int N, int MW, int MPW, bool HAVE_PROJ, bool EIG = true, bool GRP = false,
+          bool QN = false>
 __global__ __launch_bounds__(256, 2) void ifft2_pass2_gradients_kernel(
     const cf* __restrict__ mid, const cf* __restrict__ patches, const TkProbe probe,
     cf* __restrict__ objproj, cf* __restrict__ chi0, float* __restrict__ mpu, float mpu_scale,
     int nscan, int S, float inv_scale, int chunk, float* __restrict__ mpu_part,
-    const float* __restrict__ mode_scale, int Stot_ = 0, int accumulate_ = 0) {
+    const float* __restrict__ mode_scale, int Stot_ = 0, int accumulate_ = 0,
+    float* __restrict__ qtab = nullptr) {
   const int Stot = GRP ? Stot_ : S;
   const bool accumulate = GRP && accumulate_ != 0;
   constexpr int RB = N / 16;
@@ -756,6 +763,8 @@ __global__ __launch_bounds__(256, 2) void ifft2_pass2_gradients_kernel(
   // register file, so probe and patch values are re-read (L2) per use
   constexpr bool HOIST = RB <= 16;
   static_assert(NCB >= 1 && NSLICE % 8 == 0, "slice layout");
+  static_assert(!QN || (HOIST && EIG && HAVE_PROJ && !GRP && NSLICE * CW == N / 4),
+                "q_n partials: eigen slices in LDS, patch values in registers");
   constexpr int NBUF = RB <= 16 ? 2 : 1;  // slot sets (2: one barrier per position)
   __shared__ cf part[REDUCE ? NBUF * 4 * RB * 64 : 1];  // [buf][wave][yb][lane]
   extern __shared__ cf eigl[];  // conj(E_c,s) on this slice: [C][Sm][RB][64 CW]
@@ -782,6 +791,25 @@ __global__ __launch_bounds__(256, 2) void ifft2_pass2_gradients_kernel(
   // per-lane byte offset inside a row segment
   const long slice0 = (long)ya * N + (cb * CW + cw) * 64;
   const unsigned lb = (unsigned)lane * (unsigned)sizeof(cf);
+  // the QN partial of this wave's pixels: one value per (position, wave)
+  auto q_store = [&](float q, int n) {
+    // row sums by DPP (no LDS round trips on the pass's critical
+    // wave), then the four rows through readlane
+    auto dpp = [](float x, auto ctl) {
+      return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x),
+                                                     decltype(ctl)::value, 0xf, 0xf,
+                                                     false));
+    };
+    q += dpp(q, std::integral_constant<int, 0xb1>{});   // quad_perm [1,0,3,2]
+    q += dpp(q, std::integral_constant<int, 0x4e>{});   // quad_perm [2,3,0,1]
+    q += dpp(q, std::integral_constant<int, 0x141>{});  // row_half_mirror
+    q += dpp(q, std::integral_constant<int, 0x140>{});  // row_mirror
+    auto lane_q = [&](int l) {
+      return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q), l));
+    };
+    q = (lane_q(0) + lane_q(16)) + (lane_q(32) + lane_q(48));
+    if (lane == 0) qtab[(long)(slice * CW + cw) * nscan + n] = q;
+  };
   if (EIG && HAVE_PROJ && probe.weights != nullptr && probe.eigen != nullptr) {
     const int total = probe.C * probe.Sm * RB * 64 * CW;
     for (int i = threadIdx.x; i < total; i += 256) {
@@ -851,6 +879,18 @@ __global__ __launch_bounds__(256, 2) void ifft2_pass2_gradients_kernel(
             u[yb] = u[yb] * sc;  // chi of row ya + 16 yb
             acc[m][yb] = acc[m][yb] + conjf(O[yb]) * u[yb];
           }
+          if (QN && !REDUCE && s == 0) {  // wave-uniform (with REDUCE: below)
+            // eigl holds conj(E_0,0): Re(t conj(E)) = t.x el.x - t.y el.y
+            const cf* __restrict__ el = eigl + cw * 64 + lane;
+            float q = 0.f;
+#pragma unroll
+            for (int yb = 0; yb < RB; ++yb) {
+              const cf t = conjf(O[yb]) * u[yb];
+              const cf e = el[yb * (64 * CW)];
+              q += t.x * e.x - t.y * e.y;
+            }
+            q_store(q, n);
+          }
         } else {
 #pragma unroll
           for (int g = 0; g < RB; g += 8) {
@@ -907,6 +947,18 @@ __global__ __launch_bounds__(256, 2) void ifft2_pass2_gradients_kernel(
               const float wc = wn[(c + 1) * probe.S + s];
               const cf* __restrict__ el =
                   eigl + ((c * probe.Sm + s) * RB) * (64 * CW) + cw * 64 + lane;
+              if (QN && c == 0 && s == 0) {  // wave-uniform: q_n from the same loads
+                float q = 0.f;
+#pragma unroll
+                for (int yb = 0; yb < RB; ++yb) {
+                  const cf e = el[yb * (64 * CW)];
+                  slot[yb * 64] = slot[yb * 64] + (e * u[yb]) * wc;
+                  const cf t = conjf(O[yb]) * u[yb];  // (el holds conj(E))
+                  q += t.x * e.x - t.y * e.y;
+                }
+                q_store(q, n);
+                continue;
+              }
 #pragma unroll
               for (int yb = 0; yb < RB; ++yb)
                 slot[yb * 64] = slot[yb * 64] + (el[yb * (64 * CW)] * u[yb]) * wc;
@@ -965,16 +1017,51 @@ __global__ __launch_bounds__(256, 2) void ifft2_pass2_gradients_kernel(
 // (S,det,det, accumulated).  Probe window = detector; det in {128, 256, 512};
 // S <= 8 (TIKE_ERR_UNSUPPORTED otherwise: use tike_ifft2_crop* +
 // tike_lstsq_gradients).
+// q_n of every position from the partials of the QN instantiation, in a fixed order
+__global__ __launch_bounds__(256) void pass2_q_finish_kernel(const float* __restrict__ qtab,
+                                                             int slots, int nscan,
+                                                             float* __restrict__ q) {
+  // one wave per position, lane k reads slot k (slots <= 64), a fixed tree
+  const int n = blockIdx.x * 4 + (int)(threadIdx.x >> 6), k = threadIdx.x & 63;
+  if (n >= nscan) return;  // wave-uniform
+  float a = k < slots ? qtab[(long)k * nscan + n] : 0.f;
+  a = tk_wave_sum(a);
+  if (k == 0) q[n] = a;
+}
+
+// the QN instantiation of a (det, MW, MPW) launch (probe windows of 128 and
+// 256: the patch values stay in registers there); false: not compiled
+template <int N, int MW_, int MPW_>
+static bool launch_pass2_qn(dim3 grid, size_t lds, hipStream_t stream, const cf* work,
+                            const cf* patches, const TkProbe& pr, cf* objproj, cf* chi0,
+                            float* mpu, float mpu_scale, int nscan, int S, float inv_scale,
+                            int chunk, float* mpu_part, const float* mode_scale, float* qtab) {
+  if constexpr (N <= 256) {
+    hipLaunchKernelGGL((ifft2_pass2_gradients_kernel<N, MW_, MPW_, true, true, false, true>),
+                       grid, dim3(256), lds, stream, work, patches, pr, objproj, chi0, mpu,
+                       mpu_scale, nscan, S, inv_scale, chunk, mpu_part, mode_scale, 0, 0, qtab);
+    return true;
+  } else {
+    return false;
+  }
+}
+
 static int launch_pass2_gradients(const void* work, const void* patches, const void* probe,
                                   const void* eigen_probe, const float* eigen_weights,
                                   int num_eigen, int eigen_modes, void* objproj, void* chi0,
                                   void* m_probe_update, float mpu_scale, int nscan, int S,
                                   int det, float inv_scale, const float* mode_scale,
-                                  hipStream_t stream, int Stot = 0, int accumulate = 0) {
+                                  hipStream_t stream, int Stot = 0, int accumulate = 0,
+                                  float* qtab = nullptr, float* q = nullptr) {
   TK_CHECK_ARG(nscan >= 0 && S >= 1 && det >= 1);
   if (nscan == 0) return TK_OK;
   TK_CHECK_ARG(work && patches && (probe || !objproj));
   if (S > 8 || (det != 128 && det != 256 && det != 512)) return TK_ERR_UNSUPPORTED;
+  const bool qn = q != nullptr;
+  TK_CHECK_ARG(!qn || qtab);
+  if (qn && (Stot != 0 || det > 256 || !objproj || !eigen_probe || !eigen_weights ||
+             num_eigen < 1 || eigen_modes < 1))
+    return TK_ERR_UNSUPPORTED;
   // a group of S modes out of Stot (tike_ifft2_pass2_gradients_modes): the
   // weights are Stot apart, as the tiles
   const bool grp = Stot != 0;
@@ -1023,7 +1110,13 @@ static int launch_pass2_gradients(const void* work, const void* patches, const v
   if (eig_lds > 32 * 1024) return TK_ERR_UNSUPPORTED;
 #define TK_P2G(N, MW_, MPW_)                                                                 \
   do {                                                                                       \
-    if (grp && !objproj)                                                                     \
+    if (qn) {                                                                                \
+      if (!launch_pass2_qn<N, MW_, MPW_>(grid, eig_lds, stream, (const cf*)work,             \
+                                         (const cf*)patches, pr, (cf*)objproj, (cf*)chi0,    \
+                                         (float*)m_probe_update, mpu_scale, nscan, S,        \
+                                         inv_scale, chunk, mpu_part, mode_scale, qtab))      \
+        return TK_ERR_UNSUPPORTED;                                                           \
+    } else if (grp && !objproj)                                                              \
       hipLaunchKernelGGL((ifft2_pass2_gradients_kernel<N, MW_, MPW_, false, true, true>),    \
                          grid, block, 0,                                                     \
                          stream, (const cf*)work, (const cf*)patches, pr, (cf*)objproj,      \
@@ -1078,6 +1171,11 @@ static int launch_pass2_gradients(const void* work, const void* patches, const v
 #undef TK_P2G_N
 #undef TK_P2G
   TK_LAUNCH_CHECK();
+  if (qn) {
+    hipLaunchKernelGGL(pass2_q_finish_kernel, dim3((nscan + 3) / 4), dim3(256), 0, stream,
+                       qtab, det / 4, nscan, q);
+    TK_LAUNCH_CHECK();
+  }
   if (mpu_part != nullptr)
     return tk_ordered_sum((float*)m_probe_update, mpu_part, mpu_len, nchunk, true, stream);
   return TK_OK;
@@ -1110,6 +1208,24 @@ extern "C" int tike_ifft2_pass2_gradients_scaled(const void* work, const void* p
   return launch_pass2_gradients(work, patches, probe, eigen_probe, eigen_weights, num_eigen,
                                 eigen_modes, objproj, chi0, m_probe_update, mpu_scale, nscan, S,
                                 det, inv_scale, mode_scale, (hipStream_t)stream);
+}
+
+// tike_ifft2_pass2_gradients, and q[n] = sum_p Re(conj(O_n) chi_n,0 conj(E_0,0))
+// from the same registers (the step statistics' eigen projection without the
+// probe-update term; tike_eigen_pixel_update1q subtracts it).  qtab: scratch
+// of nscan * det / 4 floats.
+extern "C" int tike_ifft2_pass2_gradients_eproj(const void* work, const void* patches,
+                                                const void* probe, const void* eigen_probe,
+                                                const float* eigen_weights, int num_eigen,
+                                                int eigen_modes, void* objproj, void* chi0,
+                                                void* m_probe_update, float mpu_scale,
+                                                int nscan, int S, int det, float inv_scale,
+                                                float* qtab, float* q, void* stream) {
+  TK_ENTER();
+  TK_CHECK_ARG(nscan == 0 || (qtab && q));
+  return launch_pass2_gradients(work, patches, probe, eigen_probe, eigen_weights, num_eigen,
+                                eigen_modes, objproj, chi0, m_probe_update, mpu_scale, nscan, S,
+                                det, inv_scale, nullptr, (hipStream_t)stream, 0, 0, qtab, q);
 }
 
 // 1 where the eigen probes' LDS slices of tike_ifft2_pass2_gradients fit (32 KiB
@@ -1815,6 +1931,24 @@ __device__ __forceinline__ bool tk_interior(const TkCorner& c, int pw, int H, in
   return c.sy >= 0 && c.sx >= 0 && c.sy + pw < H && c.sx + pw < W && (long)H * W < (1L << 28);
 }
 
+// part[b] = sum over pixels p = 256 b + t (mod 256 TK_C0_PARTS) of Re(mpu_0 conj(E_0)):
+// the position-independent term of the eigen projections (plain stores, added
+// up in a fixed order by their reader)
+constexpr int TK_C0_PARTS = 64;
+__global__ __launch_bounds__(256) void eigen_proj_offset_kernel(const cf* __restrict__ mpu0,
+                                                                const cf* __restrict__ E,
+                                                                long P,
+                                                                float* __restrict__ part) {
+  __shared__ float red[4];
+  float a = 0.f;
+  for (long p = blockIdx.x * 256L + threadIdx.x; p < P; p += 256L * TK_C0_PARTS) {
+    const cf m = mpu0[p], e = E[p];
+    a += m.x * e.x + m.y * e.y;
+  }
+  a = tk_block_sum256(a, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = a;
+}
+
 // The packed tail (one eigen probe per mode, c = 0): the per-position factor
 // pm[n] = (eproj[n] / P + w[n]) / norm (probe.py:429-433) is formed on the fly
 // from the projection the step statistics left and the batch norm.
@@ -1827,9 +1961,20 @@ __global__ __launch_bounds__(256) void eigen_pixel_update1_kernel(
     long row, const float* __restrict__ norm, float inv_P, float* __restrict__ update, int nscan,
     int chunk, const float* __restrict__ stats, const float* __restrict__ costs, float eps,
     float* __restrict__ sums3, const cf* __restrict__ psi, const float* __restrict__ scan, int pw,
-    int H, int W, float* __restrict__ part) {
+    int H, int W, float* __restrict__ part, const float* __restrict__ c0part,
+    float* __restrict__ eproj_out) {
+  // c0part (tike_eigen_pixel_update1q): eproj holds q_n, the projection is
+  // q_n - c0 with c0 = sum_p Re(mpu_0 conj(E_0)) the sum of the 64 partials
+  float c0 = 0.f;
+  if (c0part != nullptr) {
+    for (int b = 0; b < TK_C0_PARTS; ++b) c0 += c0part[b];
+  }
   if (blockIdx.x + 1 == gridDim.x) {
-    if (blockIdx.y != 0 || sums3 == nullptr) return;
+    if (blockIdx.y != 0) return;
+    if (eproj_out != nullptr) {
+      for (int n = threadIdx.x; n < nscan; n += 256) eproj_out[n] = eproj[n] - c0;
+    }
+    if (sums3 == nullptr) return;
     __shared__ float red[4];
     float a1 = 0.f, a4 = 0.f, c = 0.f;
     for (int n = threadIdx.x; n < nscan; n += 256) {
@@ -1871,7 +2016,7 @@ __global__ __launch_bounds__(256) void eigen_pixel_update1_kernel(
       const cf o = tk_patch_pixel(
           psi, (unsigned)(c.sy * W + c.sx) * (unsigned)sizeof(cf) + lane_off, row_bytes, c);
       const cf r = conjf(o) * x - m0;
-      const float w = (eproj[n] * inv_P + weights_c[n * row]) * inv_norm;
+      const float w = ((eproj[n] - c0) * inv_P + weights_c[n * row]) * inv_norm;
       acc.x += r.x * w;
       acc.y += r.y * w;
     }
@@ -1879,7 +2024,7 @@ __global__ __launch_bounds__(256) void eigen_pixel_update1_kernel(
 #pragma unroll 4
     for (int n = b0; n < b1; ++n) {
       const cf r = R.at<true>(n, p);
-      const float w = (eproj[n] * inv_P + weights_c[n * row]) * inv_norm;
+      const float w = ((eproj[n] - c0) * inv_P + weights_c[n * row]) * inv_norm;
       acc.x += r.x * w;
       acc.y += r.y * w;
     }
@@ -2065,6 +2210,265 @@ __global__ __launch_bounds__(512) void eigen_position_sums1_pair_kernel(
   }
 }
 
+// The step statistics (step_stats_pair_kernel<true>, without the eigen
+// projection) and the eigen position sums (eigen_position_sums1) in ONE pass
+// over chi_n,0 and the patches.  The sums are taken against the renormalised
+// first eigen probe E' = (E + k update) / |.| (the arithmetic of
+// eigen_apply1_kernel, from nacc), formed on the fly: E itself stays the probe
+// the step statistics' varying probe is made of until the launch after this one
+// writes E'.  Two positions per work item, row walk; a pair with a position on
+// the border takes step_stats_item and a per-position strided loop.
+// sums5[n] = { s0, s1, s2, s0, s4 }: Re sum R conj(E') is s0 and s3 alike.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
+void step_stats_eigen_pair_kernel(
+    const cf* __restrict__ chi, const float* __restrict__ scan, const cf* __restrict__ gobj,
+    const TkProbe probe, const cf* __restrict__ mpu, const cf* __restrict__ patches,
+    const cf* __restrict__ update, const float* __restrict__ nacc, float inv_count, float beta,
+    float* __restrict__ stats, float* __restrict__ sums5, int nscan, int chi_modes, int pw,
+    int H, int W, int nsplit) {
+  __shared__ float red[4];
+  typedef float tk_v4f __attribute__((ext_vector_type(4)));
+  const long P = (long)pw * pw;
+  const int plen = (int)(P / nsplit);
+  const int npair = (nscan + 1) / 2;
+  // E' = (E + k u) inv (eigen_apply1_kernel)
+  const float uu = nacc[0], ee = nacc[1], eu = nacc[2];
+  const float mu = sqrtf(uu * inv_count * inv_count / (float)P);
+  const float kk = beta / mu * inv_count;
+  const float inv = 1.0f / sqrtf((ee + 2.0f * kk * eu + kk * kk * uu) / (float)P);
+  auto enew = [&](const cf e, const long p) { return (e + update[p] * kk) * inv; };
+  auto esum = [](float* a, const cf o, const cf x, const cf e, const cf m0) {
+    const cf r = conjf(o) * x - m0;
+    const cf phi = o * e;
+    a[0] += r.x * e.x + r.y * e.y;
+    a[1] += x.x * phi.x + x.y * phi.y;
+    a[2] += norm2(phi);
+    a[3] += r.y * e.x - r.x * e.y;  // Im(r conj(e))
+  };
+  auto put = [&](float* dst, const float v) {
+    if (nsplit > 1)
+      unsafeAtomicAdd(dst, v);
+    else
+      *dst = v;
+  };
+  auto finish5 = [&](const float* a, const int n) {
+    float t[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) t[k] = tk_block_sum256(a[k], red);
+    if (threadIdx.x == 0) {
+      float* o = sums5 + (long)n * 5;
+      put(o, t[0]);
+      put(o + 1, t[1]);
+      put(o + 2, t[2]);
+      put(o + 3, t[0]);
+      put(o + 4, t[3]);
+    }
+  };
+  for (int v = blockIdx.x; v < npair * nsplit; v += gridDim.x) {
+    const int n0 = 2 * (v / nsplit), part = v % nsplit;
+    const TkCorner c0 = tk_corner(scan, n0);
+    const bool two = n0 + 1 < nscan;
+    const TkCorner c1 = tk_corner(scan, two ? n0 + 1 : n0);
+    const bool in0 = c0.sy >= 0 && c0.sx >= 0 && c0.sy + pw < H && c0.sx + pw < W;
+    const bool in1 = c1.sy >= 0 && c1.sx >= 0 && c1.sy + pw < H && c1.sx + pw < W;
+    const int pbeg = part * plen + (int)threadIdx.x;
+    const int pend = part + 1 == nsplit ? (int)P : (part + 1) * plen;
+    if (!(two && in0 && in1)) {  // uniform
+      for (int i = 0; i < (two ? 2 : 1); ++i) {
+        const int n = n0 + i;
+        step_stats_item<true, true>(chi, scan, nullptr, gobj, probe, mpu, patches, stats,
+                                    chi_modes, pw, H, W, nullptr, nullptr, nsplit, n, part, red);
+        float a[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int p = pbeg; p < pend; p += blockDim.x)
+          esum(a, patches[(long)n * P + p], chi[(long)n * chi_modes * P + p],
+               enew(probe.eigen[p], p), mpu[p]);
+        finish5(a, n);
+      }
+      continue;
+    }
+    float s0 = 1.0f, s1 = 1.0f, t0 = 0.f, t1 = 0.f;  // weights of P_0 and of E_0
+    if (probe.weights != nullptr) {
+      const float* w = probe.weights + n0 * (long)(probe.C + 1) * probe.S;
+      s0 = w[0];
+      s1 = w[(long)(probe.C + 1) * probe.S];
+      t0 = w[probe.S];
+      t1 = w[(long)(probe.C + 1) * probe.S + probe.S];
+    }
+    float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float b[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float ea[4] = {0.f, 0.f, 0.f, 0.f}, eb[4] = {0.f, 0.f, 0.f, 0.f};
+    const unsigned base0 = (unsigned)(c0.sy * W + c0.sx), base1 = (unsigned)(c1.sy * W + c1.sx);
+    const cf* __restrict__ chi_a = chi + ((long)n0 * chi_modes) * P;
+    const cf* __restrict__ chi_b = chi + ((long)(n0 + 1) * chi_modes) * P;
+    const cf* __restrict__ pat_a = patches + (long)n0 * P;
+    const cf* __restrict__ pat_b = pat_a + P;
+    auto tap = [](const tk_v4f u, const tk_v4f l, const TkCorner& c) {
+      cf g = mk(u.x * c.w00, u.y * c.w00);
+      g.x += u.z * c.w01;
+      g.y += u.w * c.w01;
+      g.x += l.x * c.w10;
+      g.y += l.y * c.w10;
+      g.x += l.z * c.w11;
+      g.y += l.w * c.w11;
+      return g;
+    };
+    auto sums = [](float* acc, const cf g, const cf o, const cf x0, const cf p0, const cf pn,
+                   const cf m0) {
+      const cf dOP = g * pn;
+      const cf dPO = m0 * o;
+      const cf OP = o * p0;
+      acc[0] += norm2(dOP);
+      acc[1] += norm2(dPO);
+      const cf a2 = dOP * conjf(dPO);
+      acc[2] += a2.x;
+      acc[3] += a2.y;
+      acc[4] += dOP.x * x0.x + dOP.y * x0.y;
+      acc[5] += dPO.x * x0.x + dPO.y * x0.y;
+      acc[6] += OP.x * x0.x + OP.y * x0.y;
+      acc[7] += norm2(OP);
+    };
+    auto pixel = [&](const int p, const tk_v4f u0, const tk_v4f l0, const tk_v4f u1,
+                     const tk_v4f l1) {
+      const cf oa = pat_a[p], ob = pat_b[p];
+      const cf xa = chi_a[p], xb = chi_b[p];
+      const cf p0 = probe.probe[p];
+      const cf m0 = mpu[p];
+      const cf e1 = probe.eigen[p];
+      const cf en = enew(e1, p);
+      cf pa = p0 * s0, pb = p0 * s1;
+      pa.x += t0 * e1.x;
+      pa.y += t0 * e1.y;
+      pb.x += t1 * e1.x;
+      pb.y += t1 * e1.y;
+      sums(a, tap(u0, l0, c0), oa, xa, p0, pa, m0);
+      sums(b, tap(u1, l1, c1), ob, xb, p0, pb, m0);
+      esum(ea, oa, xa, en, m0);
+      esum(eb, ob, xb, en, m0);
+    };
+    auto taps16 = [&](const unsigned off) {
+      tk_v4f t;
+      __builtin_memcpy(&t, reinterpret_cast<const char*>(gobj) + off, sizeof(t));
+      return t;
+    };
+    // row walk of step_stats_pair_kernel (the launcher admits only windows
+    // that allow it)
+    const int cols = pw < 256 ? pw : 256, groups = 256 / cols;
+    const int rows = pw / (nsplit * groups);
+    const int ybeg = (part * groups + (int)threadIdx.x / cols) * rows;
+    for (int x = (int)threadIdx.x % cols; x < pw; x += 256) {
+      unsigned rel = (unsigned)(ybeg * W + x);
+      tk_v4f u0 = taps16((base0 + rel) * 8u), u1 = taps16((base1 + rel) * 8u);
+      int p = ybeg * pw + x;
+#pragma unroll 2
+      for (int y = 0; y < rows; ++y) {
+        rel += (unsigned)W;
+        const tk_v4f l0 = taps16((base0 + rel) * 8u), l1 = taps16((base1 + rel) * 8u);
+        pixel(p, u0, l0, u1, l1);
+        u0 = l0;
+        u1 = l1;
+        p += pw;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float ta = tk_block_sum256(a[k], red);
+      const float tb = tk_block_sum256(b[k], red);
+      if (threadIdx.x == 0) {
+        put(&stats[(long)n0 * 8 + k], ta);
+        put(&stats[(long)n0 * 8 + 8 + k], tb);
+      }
+    }
+    finish5(ea, n0);
+    finish5(eb, n0 + 1);
+  }
+}
+
+// Workgroups [0, gridDim.x - 1): nacc[0..2] += { sum |update|^2, sum |E|^2,
+// sum Re(conj(E) update) } (lstsq_tail_mid_kernel's summing workgroups).
+__global__ __launch_bounds__(256) void eigen_norm_sums1_kernel(const cf* __restrict__ E,
+                                                               const cf* __restrict__ update,
+                                                               int npix, float* __restrict__ nacc,
+                                                               float* __restrict__ part) {
+  __shared__ float red[4];
+  float uu = 0.f, ee = 0.f, eu = 0.f;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < npix; i += gridDim.x * 256) {
+    const cf e = E[i], u = update[i];
+    uu += norm2(u);
+    ee += norm2(e);
+    eu += e.x * u.x + e.y * u.y;
+  }
+  uu = tk_block_sum256(uu, red);
+  ee = tk_block_sum256(ee, red);
+  eu = tk_block_sum256(eu, red);
+  if (threadIdx.x == 0) {
+    if (part != nullptr) {  // deterministic mode: added in workgroup order afterwards
+      part[3 * blockIdx.x] = uu;
+      part[3 * blockIdx.x + 1] = ee;
+      part[3 * blockIdx.x + 2] = eu;
+    } else {
+      unsafeAtomicAdd(&nacc[0], uu);
+      unsafeAtomicAdd(&nacc[1], ee);
+      unsafeAtomicAdd(&nacc[2], eu);
+    }
+  }
+}
+
+extern "C" int tike_lstsq_step_stats_eigen1(const void* chi, const float* scan,
+                                            const void* object_update_precond, const void* probe,
+                                            const void* eigen_probe, const float* eigen_weights,
+                                            int eigen_modes, const void* m_probe_update,
+                                            const void* patches, const void* update, float* nacc,
+                                            double count, float beta_eigen, float* stats,
+                                            float* sums5, int nscan, int S, int chi_modes,
+                                            int pw, int H, int W, void* stream) {
+  TK_ENTER();
+  TK_CHECK_ARG(nscan >= 0 && S >= 1 && chi_modes >= 1 && pw >= 1 && H >= 1 && W >= 1 &&
+               eigen_modes >= 1 && count > 0);
+  TK_CHECK_ARG(probe && eigen_probe && eigen_weights && m_probe_update && update && nacc);
+  const long P = (long)pw * pw;
+  const long nitem = (nscan + 1) / 2;
+  int nsplit = 1;
+  while (nsplit < 16 && nitem * nsplit * 2 <= 8192 && P % (2048L * nsplit) == 0) nsplit *= 2;
+  if (tk_deterministic()) nsplit = 1;  // one workgroup per position pair: no atomics
+  // the row walk of the pair kernel: windows of 256 k columns or dividing 256
+  const int groups = 256 / (pw < 256 ? pw : 256);
+  if (!((pw % 256 == 0 || 256 % pw == 0) && pw % (nsplit * groups) == 0 &&
+        (long)H * W < (1L << 28)))
+    return TK_ERR_UNSUPPORTED;
+  // nacc (zero on entry) from E and the all-ranks update
+  int grid = P >= 256 * 64 ? 64 : (int)((P + 255) / 256);
+  float* part = nullptr;
+  if (tk_deterministic()) {
+    part = tk_det_scratch(sizeof(float) * 3 * (size_t)grid);
+    if (part == nullptr) grid = 1;
+  }
+  hipLaunchKernelGGL(eigen_norm_sums1_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream,
+                     (const cf*)eigen_probe, (const cf*)update, (int)P, nacc, part);
+  TK_LAUNCH_CHECK();
+  if (part != nullptr) {
+    int rc = tk_ordered_sum(nacc, part, 3, grid, true, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  if (nscan == 0) return TK_OK;
+  TK_CHECK_ARG(chi && scan && object_update_precond && patches && stats && sums5);
+  const TkProbe pr = tk_make_probe(probe, 0, eigen_probe, eigen_weights, 1, eigen_modes, S, pw,
+                                   nullptr);
+  if (nsplit > 1) {
+    hipError_t e = hipMemsetAsync(stats, 0, sizeof(float) * 8 * (size_t)nscan, (hipStream_t)stream);
+    if (e == hipSuccess)
+      e = hipMemsetAsync(sums5, 0, sizeof(float) * 5 * (size_t)nscan, (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL(step_stats_eigen_pair_kernel, dim3(tk_grid(nitem * nsplit, 16)), dim3(256),
+                     0, (hipStream_t)stream, (const cf*)chi, scan,
+                     (const cf*)object_update_precond, pr, (const cf*)m_probe_update,
+                     (const cf*)patches, (const cf*)update, (const float*)nacc,
+                     (float)(1.0 / count), beta_eigen, stats, sums5, nscan, chi_modes, pw, H, W,
+                     nsplit);
+  TK_LAUNCH_CHECK();
+  return TK_OK;
+}
+
 static TkResidual make_residual(const void* patches, const void* chi0, const void* mpu0,
                                 const void* eigen, const void* coefs, int C, int Sm, int c,
                                 int pw, int chi_modes) {
@@ -2158,7 +2562,40 @@ extern "C" int tike_eigen_pixel_update1(const void* patches, const void* chi0,
   hipLaunchKernelGGL(eigen_pixel_update1_kernel, grid, dim3(256), 0, (hipStream_t)stream, R,
                      eigen_proj, weights_c, weights_row, norm, 1.0f / (float)P, (float*)update,
                      nscan, chunk, stats, costs, eps, sums3, (const cf*)psi, scan, pw, H, W,
-                     part);
+                     part, nullptr, nullptr);
+  TK_LAUNCH_CHECK();
+  if (part != nullptr)
+    return tk_ordered_sum((float*)update, part, 2 * P, (int)grid.y, true, (hipStream_t)stream);
+  return TK_OK;
+}
+
+// tike_eigen_pixel_update1 from q (tike_ifft2_pass2_gradients_eproj) instead of
+// the projections: eigen_proj[n] = q[n] - sum_p Re(mpu_0 conj(E_0)) formed on
+// the fly (and left in eproj_out, when given); no sums3.  c0part: scratch of
+// 64 floats.
+extern "C" int tike_eigen_pixel_update1q(const void* patches, const void* chi0,
+                                         const void* mpu0, const void* eigen0, const float* q,
+                                         const float* weights_c, long weights_row,
+                                         const float* norm, void* update, int nscan, int pw,
+                                         int chi_modes, const void* psi, const float* scan,
+                                         int H, int W, float* c0part, float* eproj_out,
+                                         void* stream) {
+  TK_ENTER();
+  TK_CHECK_ARG(nscan >= 0 && pw >= 1 && chi_modes >= 1 && weights_row >= 1);
+  if (nscan == 0) return TK_OK;
+  TK_CHECK_ARG(!psi || (scan && H >= 1 && W >= 1));
+  TK_CHECK_ARG(patches && chi0 && mpu0 && eigen0 && q && weights_c && norm && update && c0part);
+  const long P = (long)pw * pw;
+  hipLaunchKernelGGL(eigen_proj_offset_kernel, dim3(TK_C0_PARTS), dim3(256), 0,
+                     (hipStream_t)stream, (const cf*)mpu0, (const cf*)eigen0, P, c0part);
+  float* part = nullptr;
+  const int chunk = probe_chunk(nscan, 2 * P, &part);
+  dim3 grid((unsigned)((P + 255) / 256) + 1, (unsigned)((nscan + chunk - 1) / chunk));
+  const TkResidual R = make_residual(patches, chi0, mpu0, eigen0, nullptr, 1, 1, 0, pw, chi_modes);
+  hipLaunchKernelGGL(eigen_pixel_update1_kernel, grid, dim3(256), 0, (hipStream_t)stream, R, q,
+                     weights_c, weights_row, norm, 1.0f / (float)P, (float*)update, nscan, chunk,
+                     nullptr, nullptr, 0.f, nullptr, (const cf*)psi, scan, pw, H, W, part,
+                     c0part, eproj_out);
   TK_LAUNCH_CHECK();
   if (part != nullptr)
     return tk_ordered_sum((float*)update, part, 2 * P, (int)grid.y, true, (hipStream_t)stream);

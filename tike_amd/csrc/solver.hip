@@ -477,6 +477,84 @@ extern "C" int tike_lstsq_tail_mid(void* eigen0, const void* update, int npix, f
   return TK_OK;
 }
 
+// The single-rank tail after tike_lstsq_step_stats_eigen1.  Workgroups
+// [0, gridDim.x - 1): E <- E' (eigen_apply1_kernel, from nacc).  Last
+// workgroup: sums3 = { sum (A1 + eps), sum (A4 + eps), sum cost } (step_sums_kernel),
+// the 2x2 solves with them (lstsq_tail_mid_kernel) and the denominator mean
+// dsum = sum_n sums5[n][2] / P: tail3 = { sum step_o, sum step_p, dsum }.
+__global__ __launch_bounds__(256) void lstsq_tail_solve1_kernel(
+    cf* __restrict__ E, const cf* __restrict__ update, const float* __restrict__ nacc,
+    float inv_count, float beta, int npix, const float* __restrict__ stats,
+    const float* __restrict__ costs, const float* __restrict__ sums5, int B, float eps,
+    int recover_psi, int recover_probe, float* __restrict__ sums3, float* __restrict__ tail3) {
+  if (blockIdx.x + 1 < gridDim.x) {
+    const float uu = nacc[0], ee = nacc[1], eu = nacc[2];
+    const float mu = sqrtf(uu * inv_count * inv_count / (float)npix);
+    const float k = beta / mu * inv_count;
+    const float inv = 1.0f / sqrtf((ee + 2.0f * k * eu + k * k * uu) / (float)npix);
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < npix; i += (gridDim.x - 1) * 256)
+      E[i] = (E[i] + update[i] * k) * inv;
+    return;
+  }
+  __shared__ float red[4];
+  float a1 = 0.f, a4 = 0.f, c = 0.f, d = 0.f;
+  for (int n = threadIdx.x; n < B; n += 256) {
+    a1 += stats[8 * n] + eps;
+    a4 += stats[8 * n + 1] + eps;
+    c += costs[n];
+    d += sums5[5 * n + 2] / (float)npix;
+  }
+  a1 = tk_block_sum256(a1, red);
+  a4 = tk_block_sum256(a4, red);
+  c = tk_block_sum256(c, red);
+  d = tk_block_sum256(d, red);
+  const float r1 = 0.5f * a1 * inv_count, r4 = 0.5f * a4 * inv_count;
+  float so = 0.f, sp = 0.f;
+  for (int n = threadIdx.x; n < B; n += 256) {
+    const float* s = stats + 8 * n;
+    const float A1 = s[0] + eps + r1, A4 = s[1] + eps + r4;
+    const float b1 = s[4], b2 = s[5];
+    float x1 = 0.f, x2 = 0.f;
+    if (recover_psi && recover_probe) {
+      const float det = A1 * A4 - (s[2] * s[2] + s[3] * s[3]);
+      x1 = -(s[2] * b2 - A4 * b1) / det;
+      x2 = (A1 * b2 - s[2] * b1) / det;
+    } else if (recover_psi) {
+      x1 = b1 / A1;
+    } else if (recover_probe) {
+      x2 = b2 / A4;
+    }
+    so += 0.9f * fmaxf(x1, 0.f);
+    sp += 0.9f * fmaxf(x2, 0.f);
+  }
+  so = tk_block_sum256(so, red);
+  sp = tk_block_sum256(sp, red);
+  if (threadIdx.x == 0) {
+    sums3[0] = a1;
+    sums3[1] = a4;
+    sums3[2] = c;
+    tail3[0] = so;
+    tail3[1] = sp;
+    tail3[2] = d;
+  }
+}
+
+extern "C" int tike_lstsq_tail_solve1(void* eigen0, const void* update, int npix,
+                                      const float* nacc, float beta_eigen, const float* stats,
+                                      const float* costs, const float* sums5, int B, float eps,
+                                      double count, int recover_psi, int recover_probe,
+                                      float* sums3, float* tail3, void* stream) {
+  TK_ENTER();
+  TK_CHECK_ARG(B >= 0 && count > 0 && npix >= 1 && sums3 && tail3);
+  TK_CHECK_ARG(eigen0 && update && nacc && (B == 0 || (stats && costs && sums5)));
+  const int grid = npix >= 256 * 64 ? 64 : (npix + 255) / 256;
+  hipLaunchKernelGGL(lstsq_tail_solve1_kernel, dim3(grid + 1), dim3(256), 0, (hipStream_t)stream,
+                     (cf*)eigen0, (const cf*)update, nacc, (float)(1.0 / count), beta_eigen,
+                     npix, stats, costs, sums5, B, eps, recover_psi, recover_probe, sums3, tail3);
+  TK_LAUNCH_CHECK();
+  return TK_OK;
+}
+
 // Everything that closes a minibatch, element-wise over max(probe, pixels,
 // positions), with tail3 = { sum step_o, sum step_p, dsum } over ALL ranks:
 //   steps[0..4] = { tail3[0], tail3[1], beta_object, beta_probe, mean cost }

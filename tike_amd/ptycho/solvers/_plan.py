@@ -288,6 +288,14 @@ class GradientPlan:
             groups=groups)
 
     # -------------------------------------------------------- workspaces
+    def eigen_q(self, C, Sm, H, W):
+        """Whether pass 2 can leave the per-position part of the eigen
+        projection (tike_ifft2_pass2_gradients_eproj) for the fused tail: the
+        fused pass 2 of one launch at 128^2 / 256^2, one eigen probe."""
+        return (self.fused and not self.groups and not self.steps_in_pass2
+                and self.det in (128, 256) and self.pw == self.det
+                and C == 1 and Sm >= 1 and H * W < (1 << 28))
+
     def buffers(self, ws, B, dev, *, varying, want_patches):
         """The chunk workspaces of this route (reused across minibatches)."""
         S, pw, det = self.S, self.pw, self.det
@@ -600,6 +608,11 @@ class GradientPlan:
                 check(lib.tike_ifft2_pass2_gradients_scaled(
                     *p2, A.ptr(b.steps), st),
                     "inverse pass 2 + gradients (x poisson steps)")
+            elif k.q is not None:
+                # ... and the per-position part of the eigen projection
+                check(lib.tike_ifft2_pass2_gradients_eproj(
+                    *p2, A.ptr(b.qtab), A.ptr(k.q), st),
+                    "inverse pass 2 + gradients + eigen projection")
             else:
                 check(lib.tike_ifft2_pass2_gradients(*p2, st),
                       "inverse pass 2 + gradients")

@@ -288,6 +288,11 @@ def lstsq_grad(parameters, data, batches, comm, *, op, epoch):
         if comm.collective:
             comm.Allreduce(eigen_norms)
 
+    # one rank, one eigen probe: the step statistics and the eigen position
+    # sums in one pass (when the gradient route leaves q, see _packed_tail)
+    want_q = bool(FUSED_TAIL and eigen_norms is not None and recover_psi
+                  and not comm.collective and not STATS_PATCH_RECOMPUTE)
+
     for batch_index in order:
         lo, hi = _lo_hi(batches[batch_index])
         comm.minibatch = int(batch_index)
@@ -295,7 +300,7 @@ def lstsq_grad(parameters, data, batches, comm, *, op, epoch):
             data, psi, scan, probe, eigen_probe, eigen_weights, lo, hi, comm,
             num_batch=num_batch, exitwave_options=exitwave_options, op=op,
             recover_psi=recover_psi, recover_probe=recover_probe,
-            position_terms=position_terms)
+            position_terms=position_terms, want_q=want_q)
 
         object_update_precond = None
         if recover_psi:
@@ -431,6 +436,12 @@ STATS_PATCH_RECOMPUTE = _tuning.stats_gather
 """The step statistics gather O_n from the object with the two 16-byte tap
 loads they already issue for the preconditioned update (same offsets)."""
 
+FUSED_TAIL = _tuning.fused_tail
+"""One rank, one eigen probe, the fused pass 2 at 128^2 / 256^2: pass 2 leaves
+the per-position part of the eigen projection, the eigen update runs before
+the step statistics, and the statistics and the eigen position sums are one
+pass over chi_n,0 and the patches (tike_lstsq_step_stats_eigen1)."""
+
 PACKED_TAIL = True
 """Tests set this to False to run the staged tail (one entry per step of the
 reference's _update_nearplane / _precondition_nearplane_gradients)."""
@@ -468,13 +479,16 @@ def _once(make):
 def _get_nearplane_gradients(data, psi, scan, probe, eigen_probe,
                              eigen_weights, lo, hi, comm, *, num_batch,
                              exitwave_options, op, recover_psi, recover_probe,
-                             position_terms=None, need_chi0=True):
+                             position_terms=None, need_chi0=True,
+                             want_q=False):
     """Object / probe gradients of one minibatch (lstsq.py:367-602).  Which
     kernels a chunk runs is the GradientPlan of the shape (`_plan.py`, cached
     on the operator like the reference's FFT plan, cache.py:32-46); this
     function walks the chunks and completes the sums over the ranks.
     need_chi0=False (cgrad: no step statistics follow) skips the store of
-    mode 0 of chi where the fused pass 2 would be its only producer."""
+    mode 0 of chi where the fused pass 2 would be its only producer.
+    want_q: pass 2 also leaves q[n] = sum_p Re(conj(O_n) chi_n,0 conj(E_0))
+    where the route allows it (returned as "q", None otherwise)."""
     dev = psi.device
     B = hi - lo
     S, pw = probe.shape[-3], probe.shape[-1]
@@ -513,6 +527,14 @@ def _get_nearplane_gradients(data, psi, scan, probe, eigen_probe,
                           or position_terms))
     if position_terms:
         taps, taps_r = gaussian_derivative_taps(sigma=0.333)
+    q = None
+    if (want_q and recover_psi and recover_probe and w_old is not None
+            and buf.patches is not None and need_chi0
+            and plan.eigen_q(C, Sm, H, W)):
+        q = _workspace(op).get("eigen_q", (max(B, 1),), torch.float32, dev)
+        buf.qtab = _workspace(op).get("eigen_qtab", (min(plan.chunk, max(B, 1)),
+                                                     det // 4),
+                                      torch.float32, dev)
     # what every chunk shares
     c = SimpleNamespace(
         op=op, data=data, psi=psi, probe=probe, ep=ep, eigen_probe=eigen_probe,
@@ -533,7 +555,8 @@ def _get_nearplane_gradients(data, psi, scan, probe, eigen_probe,
             w=None if w_old is None else w_old[rows], uq=None,
             costs=buf.costs[rows],
             patches=None if buf.patches is None else buf.patches[rows],
-            chi0=None if buf.chi0 is None else buf.chi0[rows])
+            chi0=None if buf.chi0 is None else buf.chi0[rows],
+            q=None if q is None else q[rows])
         # float32 view of the chunk for the kernels without a 16-bit loader
         # (the 256^2 gaussian hot path reads uint16 directly), made on demand
         k.data_f32 = _once(lambda a=clo, b=chi_hi: A.data_f32(data, a, b))
@@ -590,7 +613,8 @@ def _get_nearplane_gradients(data, psi, scan, probe, eigen_probe,
                 chi_modes=S if buf.single_chunk else 1, w_old=w_old,
                 patches=None if buf.patches is None else buf.patches[:B],
                 object_acc=obj_acc, m_probe_update=m_probe_update,
-                costs=buf.costs[:B], count=count, local_count=B)
+                costs=buf.costs[:B], count=count, local_count=B,
+                q=None if q is None else q[:B])
 
 
 def object_upd_sum(g):
@@ -686,6 +710,15 @@ def _packed_tail(g, psi, scan, probe, eigen_probe, eigen_weights,
     update = small[4:4 + 2 * P]
     nacc = small[4 + 2 * P:4 + 2 * P + 4]
     tail3 = small[4 + 2 * P + 4:4 + 2 * P + 7]
+    if (one and g.get("q") is not None and not comm.collective
+            and object_update_precond is not None and psi.shape[0] == 1):
+        return _fused_tail(g, psi, scan, probe, eigen_probe, eigen_weights,
+                           object_update_precond, lo, hi, op=op,
+                           num_batch=num_batch, recover_psi=recover_psi,
+                           recover_probe=recover_probe, norm=norm,
+                           steps_row=steps_row,
+                           probe_combined_update=probe_combined_update,
+                           sums3=sums3, update=update, nacc=nacc, tail3=tail3)
     stats = _step_stats(g, psi, scan, probe, eigen_probe,
                         object_update_precond, lo, hi, op=op)
     eps_total = float(np.float32(np.float32(1e-9) / P) * P)
@@ -740,6 +773,71 @@ def _packed_tail(g, psi, scan, probe, eigen_probe, eigen_weights,
             A.ptr(mpu), 1.0 / num_batch, probe.numel(),
             None if w_rows is None else w_rows.data_ptr(), row, S, 0,
             A.ptr(stats), A.ptr(sums5), B, P, st), "minibatch tail")
+    return (steps_row[2] if recover_psi else None,
+            steps_row[3] if recover_probe else None)
+
+
+def _fused_tail(g, psi, scan, probe, eigen_probe, eigen_weights,
+                object_update_precond, lo, hi, *, op, num_batch, recover_psi,
+                recover_probe, norm, steps_row, probe_combined_update, sums3,
+                update, nacc, tail3):
+    """_packed_tail for one rank and one eigen probe when pass 2 left q
+    (tike_ifft2_pass2_gradients_eproj): the eigen update first (its
+    projections are q less a term of the probe update), then the step
+    statistics and the eigen position sums against the renormalised eigen
+    probe in one pass.  Same results, one pass over chi_n,0 fewer."""
+    B = hi - lo
+    dev = psi.device
+    st = A.stream_ptr()
+    S, pw = probe.shape[-3], probe.shape[-1]
+    P = pw * pw
+    H, W = psi.shape[-2:]
+    count = float(g["count"])
+    ws = _workspace(op)
+    mpu = g["m_probe_update"]
+    Sm = eigen_probe.shape[-3]
+    w_rows = eigen_weights[lo:hi]  # (B, C+1, S) rows of this minibatch
+    row = w_rows.shape[-2] * w_rows.shape[-1]
+    E = eigen_probe[0, 0, 0]  # (pw, pw) view, contiguous
+    eps_total = float(np.float32(np.float32(1e-9) / P) * P)
+    stats = ws.get("stats", (max(B, 1), 8), torch.float32, dev)
+    sums5 = ws.get("eigen_sums5", (max(B, 1), 5), torch.float32, dev)
+    eproj = ws.get("eigen_proj", (max(B, 1),), torch.float32, dev)
+    c0part = ws.get("eigen_c0part", (64,), torch.float32, dev)
+    g["eigen_proj"] = eproj[:B]
+    gpsi = A.ptr(psi[0]) if EIGEN_PATCH_RECOMPUTE else None
+    scan_b = A.ptr(scan[lo:hi])
+    check(
+        lib.tike_eigen_pixel_update1q(
+            A.ptr(g["patches"]), A.ptr(g["chi0"]), A.ptr(mpu[0, 0, 0]),
+            A.ptr(E), A.ptr(g["q"]), w_rows[:, 1, 0].data_ptr(), row,
+            A.ptr(norm), A.ptr(update), B, pw, g["chi_modes"], gpsi, scan_b,
+            H, W, A.ptr(c0part), A.ptr(eproj), st),
+        "eigen pixel update")
+    beta_eigen = min(0.1, 1.0 / num_batch)
+    check(
+        lib.tike_lstsq_step_stats_eigen1(
+            A.ptr(g["chi0"]), scan_b, A.ptr(object_update_precond),
+            A.ptr(probe), A.ptr(eigen_probe), A.ptr(g["w_old"]), Sm,
+            A.ptr(mpu), A.ptr(g["patches"]), A.ptr(update), A.ptr(nacc), count,
+            beta_eigen, A.ptr(stats), A.ptr(sums5), B, S, g["chi_modes"], pw,
+            H, W, st),
+        "step-size statistics + eigen position sums")
+    check(
+        lib.tike_lstsq_tail_solve1(
+            A.ptr(E), A.ptr(update), P, A.ptr(nacc), beta_eigen, A.ptr(stats),
+            A.ptr(g["costs"]), A.ptr(sums5), B, eps_total, count,
+            int(recover_psi), int(recover_probe), A.ptr(sums3), A.ptr(tail3),
+            st), "eigen probe + step solve")
+    check(
+        lib.tike_lstsq_tail_finish(
+            A.ptr(tail3), A.ptr(sums3), count, A.ptr(steps_row),
+            A.ptr(probe) if recover_probe else None,
+            A.ptr(probe_combined_update) if recover_probe else None,
+            A.ptr(mpu), 1.0 / num_batch, probe.numel(), w_rows.data_ptr(), row,
+            S, 0, A.ptr(stats), A.ptr(sums5), B, P, st), "minibatch tail")
+    g["stats"] = stats[:B]
+    g["sums5"] = sums5[:B]
     return (steps_row[2] if recover_psi else None,
             steps_row[3] if recover_probe else None)
 
