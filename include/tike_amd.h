@@ -38,7 +38,7 @@ extern "C" {
  * A binding compares tike_abi_version() of the loaded library with the
  * TIKE_ABI_VERSION it was written against before its first call
  * (tike_amd/_lib.py does; INTEGRATION.md shows the check). */
-#define TIKE_ABI_VERSION 12
+#define TIKE_ABI_VERSION 13
 
 /* sha256 (64 hex digits) of the sources the library was built from: the PMC
  * traffic files under profiles/ carry it, and bench.py withholds a traffic
@@ -829,6 +829,23 @@ int tike_cgrad_line_search(int variable, const void* x, const void* d, void* xs,
                            int S, int det, int H, int W, float fwd_scale, double count,
                            double* state, int* skip, int nslots, void* stream);
 
+/* ---- tike_cgrad_line_search over the cost of a noise model on the measured
+ * pixels: the same arguments, then
+ *   measured      det*det bytes, nonzero = measured pixel, or NULL (every pixel
+ *                 measured); unmeasured counts never enter the arithmetic (they
+ *                 may be NaN)
+ *   model         0 gaussian, 1 poisson (the terms of tike_farplane_gradient)
+ *   num_measured  measured pixels per pattern: each pattern's cost is its mean
+ *                 over them
+ * tike_cgrad_line_search is this entry with (NULL, 0, det*det). */
+int tike_cgrad_line_search_masked(int variable, const void* x, const void* d, void* xs,
+                                  const void* other, const float* scan, const void* data,
+                                  int data_u16, void* scratch, float* costs, int nscan, int chunk,
+                                  int S, int det, int H, int W, float fwd_scale, double count,
+                                  double* state, int* skip, int nslots,
+                                  const unsigned char* measured, int model, long num_measured,
+                                  void* stream);
+
 /* ---- the same search with every step length evaluated in one pass.  The far
  * plane is linear in the variable the search moves along: F(x + s d) = F(x) +
  * s F(d), F(d) being the forward model with the direction in place of the object
@@ -860,6 +877,23 @@ int tike_cgrad_line_search_linear(int variable, const void* x, const void* d, vo
                                   float* costs_k, int nscan, int chunk, int S, int det, int H,
                                   int W, float fwd_scale, double count, double* state,
                                   int stage, double* sums, void* stream);
+
+/* ---- tike_cgrad_line_search_linear over the cost of a noise model on the
+ * measured pixels; measured, model, num_measured as tike_cgrad_line_search_masked.
+ * Poisson: the 16 candidate rows of costs_k (and the row sums of stages 1 and 3)
+ * hold cost(x + s d) - cost(x), formed per pixel as (I(s) - I0) - d log1p((I(s) -
+ * I0) / (I0 + 1e-9)) -- the plain totals carry the offset sum(d - d log d), on
+ * which float32 rounding would decide late in a reconstruction; a step is taken
+ * when its difference is no larger than 0, and state[0] receives the plain mean
+ * cost there.  tike_cgrad_line_search_linear is this entry with (NULL, 0, det*det). */
+int tike_cgrad_line_search_linear_masked(int variable, const void* x, const void* d, void* xs,
+                                         const void* other, const float* scan, const void* data,
+                                         int data_u16, void* far_a, int a_valid, void* far_b,
+                                         float* costs_k, int nscan, int chunk, int S, int det,
+                                         int H, int W, float fwd_scale, double count,
+                                         double* state, int stage, double* sums,
+                                         const unsigned char* measured, int model,
+                                         long num_measured, void* stream);
 
 /* ---- the packed minibatch tail: the arithmetic of tike_lstsq_step_sums / _solve,
  * tike_probe_update and the tike_eigen_* entries above for the common case of ONE

@@ -1391,16 +1391,17 @@ extern "C" int tike_cgrad_direction(const float* update_planar, const void* upda
   return TK_OK;
 }
 
-extern "C" int tike_cgrad_line_search(int variable, const void* x, const void* d, void* xs,
-                                      const void* other, const float* scan, const void* data,
-                                      int data_u16, void* scratch, float* costs, int nscan,
-                                      int chunk, int S, int det, int H, int W, float fwd_scale,
-                                      double count, double* state, int* skip, int nslots,
-                                      void* stream_) {
-  TK_ENTER();
-  hipStream_t stream = (hipStream_t)stream_;
+static int tk_cgrad_line_search(int variable, const void* x, const void* d, void* xs,
+                                const void* other, const float* scan, const void* data,
+                                int data_u16, void* scratch, float* costs, int nscan, int chunk,
+                                int S, int det, int H, int W, float fwd_scale, double count,
+                                double* state, int* skip, int nslots,
+                                const unsigned char* measured, int model, long num_measured,
+                                hipStream_t stream) {
   TK_CHECK_ARG(nscan >= 1 && chunk >= 1 && S >= 1 && H >= 1 && W >= 1 && nslots >= 1 &&
                nslots <= 30 && count > 0 && (variable == 0 || variable == 1));
+  TK_CHECK_ARG((model == 0 || model == 1) && num_measured > 0 &&
+               num_measured <= (long)det * det);
   TK_CHECK_ARG(x && d && xs && other && scan && data && scratch && costs && state && skip);
   if (det != 128 && det != 256 && det != 512) return TK_ERR_UNSUPPORTED;
   if (det == 128 && data_u16) return TK_ERR_UNSUPPORTED;  // the 128^2 cost kernel reads float32
@@ -1424,8 +1425,8 @@ extern "C" int tike_cgrad_line_search(int variable, const void* x, const void* d
         int rc = launch_fwd128_lds((const cf*)psi, scan + 2L * lo, P, (cf*)scratch, nullptr, m, S,
                                    H, W, fwd_scale, stream, nullptr, skip);
         if (rc) return rc;
-        rc = tk_farplane_gradient(scratch, (const float*)data + (size_t)lo * det * det, nullptr,
-                                  nullptr, costs + lo, m, S, det, 0, 0, 1.0f, (long)det * det,
+        rc = tk_farplane_gradient(scratch, (const float*)data + (size_t)lo * det * det, measured,
+                                  nullptr, costs + lo, m, S, det, model, 0, 1.0f, num_measured,
                                   stream, skip);
         if (rc) return rc;
         continue;
@@ -1434,8 +1435,8 @@ extern "C" int tike_cgrad_line_search(int variable, const void* x, const void* d
                             scratch, nullptr, m, S, det, det, H, W, stream, skip);
       if (rc) return rc;
       rc = tk_fwd_gradient_scale(scratch, (const char*)data + dsz * (size_t)lo * det * det,
-                                 data_u16, nullptr, nullptr, nullptr, costs + lo, nullptr, m, S,
-                                 det, fwd_scale, 0, 1.0f, (long)det * det, stream, skip);
+                                 data_u16, measured, nullptr, nullptr, costs + lo, nullptr, m, S,
+                                 det, fwd_scale, model, 1.0f, num_measured, stream, skip);
       if (rc) return rc;
     }
     hipLaunchKernelGGL(ls_decide_kernel, dim3(1), dim3(256), 0, stream, costs, nscan,
@@ -1443,6 +1444,29 @@ extern "C" int tike_cgrad_line_search(int variable, const void* x, const void* d
   }
   TK_LAUNCH_CHECK();
   return TK_OK;
+}
+
+extern "C" int tike_cgrad_line_search(int variable, const void* x, const void* d, void* xs,
+                                      const void* other, const float* scan, const void* data,
+                                      int data_u16, void* scratch, float* costs, int nscan,
+                                      int chunk, int S, int det, int H, int W, float fwd_scale,
+                                      double count, double* state, int* skip, int nslots,
+                                      void* stream_) {
+  TK_ENTER();
+  return tk_cgrad_line_search(variable, x, d, xs, other, scan, data, data_u16, scratch, costs,
+                              nscan, chunk, S, det, H, W, fwd_scale, count, state, skip, nslots,
+                              nullptr, 0, (long)det * det, (hipStream_t)stream_);
+}
+
+extern "C" int tike_cgrad_line_search_masked(
+    int variable, const void* x, const void* d, void* xs, const void* other, const float* scan,
+    const void* data, int data_u16, void* scratch, float* costs, int nscan, int chunk, int S,
+    int det, int H, int W, float fwd_scale, double count, double* state, int* skip, int nslots,
+    const unsigned char* measured, int model, long num_measured, void* stream_) {
+  TK_ENTER();
+  return tk_cgrad_line_search(variable, x, d, xs, other, scan, data, data_u16, scratch, costs,
+                              nscan, chunk, S, det, H, W, fwd_scale, count, state, skip, nslots,
+                              measured, model, num_measured, (hipStream_t)stream_);
 }
 
 // ------------------------------------------- the same line search, all steps at once
@@ -1463,28 +1487,64 @@ constexpr int TK_LS_STEPS = 8;   // step lengths per pass over the hand-offs
 constexpr int TK_LS_PASSES = 2;  // passes enqueued (the second returns at once if the first accepted)
 constexpr int TK_LS_ROWS = TK_LS_STEPS * TK_LS_PASSES + 1;  // cost rows: x, then every step
 
-// gaussian cost terms of RB pixels at step0 / 2^k, k < K (rows 1..K) and, FIRST,
-// at step 0 (row 0).  v_sqrt_f32 (1 ulp) instead of the correctly rounded sqrtf
-// (a dozen instructions each): K x RB square roots per thread are what this
-// kernel issues most, and the cost at x it is compared with is formed the same way.
-template <int K, int RB, bool FIRST, class DT>
+// cost terms of RB pixels at step0 / 2^k, k < K (rows 1..K) and, FIRST, at
+// step 0 (row 0); MK: only the measured pixels of `bits` (selected, never
+// multiplied: unmeasured counts may be NaN).
+// Gaussian: v_sqrt_f32 (1 ulp) instead of the correctly rounded sqrtf (a dozen
+// instructions each): K x RB square roots per thread are what this kernel
+// issues most, and the cost at x it is compared with is formed the same way.
+// Poisson: the rows of the step lengths hold the DIFFERENCE from x per pixel,
+//   (I(s) - I0) - d log1p((I(s) - I0) / (I0 + 1e-9)),
+// so that the decision does not rest on two float32 totals that carry the large
+// offset sum(d - d log d); row 0 is the plain term I0 - d log(I0 + 1e-9).
+// log1p(r) = log(u) + (r - (u - 1)) / u with u = (I(s) + 1e-9) / (I0 + 1e-9)
+// the rounded 1 + r (never 0); 1 / u ~ max(2 - u, 0) is exact enough for a
+// correction of the size of u's rounding.
+template <int K, int RB, bool FIRST, int MODEL, bool MK, class DT>
 __device__ __forceinline__ void tk_ksteps_costs(const float (&I0)[RB], const float (&C)[RB],
                                                 const float (&I1)[RB], const DT (&raw)[RB],
-                                                float step0, float (&acc)[K + 1]) {
+                                                unsigned bits, float step0,
+                                                float (&acc)[K + 1]) {
 #pragma unroll
   for (int p = 0; p < RB; ++p) {
-    const float sd = __builtin_amdgcn_sqrtf((float)raw[p]);
-    if (FIRST) {
-      const float t0 = __builtin_amdgcn_sqrtf(I0[p]) - sd;
-      acc[0] = fmaf(t0, t0, acc[0]);
-    }
+    const bool meas = !MK || ((bits >> p) & 1u);
     const float c2 = 2.0f * C[p];
-    float s = step0;
+    if (MODEL == 0) {
+      const float sd = __builtin_amdgcn_sqrtf((float)raw[p]);
+      if (FIRST) {
+        const float t0 = __builtin_amdgcn_sqrtf(I0[p]) - sd;
+        const float a0 = fmaf(t0, t0, acc[0]);
+        acc[0] = meas ? a0 : acc[0];
+      }
+      float s = step0;
 #pragma unroll
-    for (int k = 0; k < K; ++k, s *= 0.5f) {
-      const float I = fmaxf(fmaf(s, fmaf(s, I1[p], c2), I0[p]), 0.0f);
-      const float t = __builtin_amdgcn_sqrtf(I) - sd;
-      acc[k + 1] = fmaf(t, t, acc[k + 1]);
+      for (int k = 0; k < K; ++k, s *= 0.5f) {
+        const float I = fmaxf(fmaf(s, fmaf(s, I1[p], c2), I0[p]), 0.0f);
+        const float t = __builtin_amdgcn_sqrtf(I) - sd;
+        const float a = fmaf(t, t, acc[k + 1]);
+        acc[k + 1] = meas ? a : acc[k + 1];
+      }
+    } else {
+      const float dv = (float)raw[p];
+      const float e0 = I0[p] + 1e-9f;
+      if (FIRST) {
+        const float a0 = acc[0] + fmaf(-dv, __logf(e0), I0[p]);
+        acc[0] = meas ? a0 : acc[0];
+      }
+      const float inv0 = __builtin_amdgcn_rcpf(e0);
+      float s = step0;
+#pragma unroll
+      for (int k = 0; k < K; ++k, s *= 0.5f) {
+        // (dI from s (s I1 + 2 C) itself: I(s) - I0 of the rounded I(s)
+        // would be a multiple of ulp(I0), far coarser than the short steps)
+        const float dI = fmaxf(s * fmaf(s, I1[p], c2), -I0[p]);
+        const float I = I0[p] + dI;
+        const float r = dI * inv0;
+        const float u = (I + 1e-9f) * inv0;
+        const float lp = fmaf(r - (u - 1.0f), fmaxf(2.0f - u, 0.0f), __logf(u));
+        const float a = acc[k + 1] + fmaf(-dv, lp, dI);
+        acc[k + 1] = meas ? a : acc[k + 1];
+      }
     }
   }
 }
@@ -1521,10 +1581,10 @@ __device__ __forceinline__ void tk_ksteps_emit(float (&acc)[K + 1], float (*red)
 
 // 256^2 / 512^2: the column pass of fwd_gradient_scale_kernel over the
 // hand-offs of x (col_a) and of the direction (col_b)
-template <int N, class DT, bool FIRST>
+template <int N, class DT, bool FIRST, int MODEL, bool MK>
 __global__ __launch_bounds__(256, 2) void ls_ksteps_colpass_kernel(
     const cf* __restrict__ col_a, const cf* __restrict__ col_b, const DT* __restrict__ data,
-    float* __restrict__ costs_k, long stride, long nitem, int S, float scale,
+    const unsigned char* __restrict__ mask, float* __restrict__ costs_k, long stride, long nitem, int S, float scale,
     float inv_nmeasured, int row1, const double* __restrict__ state,
     float* __restrict__ part) {
   constexpr int RB = N / 16, NH = N / 256, K = TK_LS_STEPS;
@@ -1558,11 +1618,11 @@ __global__ __launch_bounds__(256, 2) void ls_ksteps_colpass_kernel(
     }
     DT raw[RB];
     unsigned bits;
-    tk_request_data<N, RB>(data, nullptr, n, k1, t, raw, bits);
+    tk_request_data<N, RB>(data, !MK ? (const unsigned char*)nullptr : mask, n, k1, t, raw, bits);
     float acc[K + 1];
 #pragma unroll
     for (int k = 0; k <= K; ++k) acc[k] = 0.f;
-    tk_ksteps_costs<K, RB, FIRST>(I0, C, I1, raw, step0, acc);
+    tk_ksteps_costs<K, RB, FIRST, MODEL, MK>(I0, C, I1, raw, bits, step0, acc);
     tk_ksteps_emit<K, FIRST>(acc, red, costs_k, stride, n, row1, inv_nmeasured, part,
                              k1 * NH + hb);
   }
@@ -1588,10 +1648,10 @@ __global__ __launch_bounds__(256) void ls_costs_finish_kernel(float* __restrict_
 }
 
 // stored far planes (128^2): a workgroup covers TK_FG_PIX pixels of one position
-template <bool FIRST>
+template <bool FIRST, int MODEL, bool MK>
 __global__ __launch_bounds__(256) void ls_ksteps_farplane_kernel(
     const cf* __restrict__ far_a, const cf* __restrict__ far_b, const float* __restrict__ data,
-    float* __restrict__ costs_k, long stride, int S, long npix, float inv_nmeasured, int row1,
+    const unsigned char* __restrict__ mask, float* __restrict__ costs_k, long stride, int S, long npix, float inv_nmeasured, int row1,
     const double* __restrict__ state, float* __restrict__ part) {
   constexpr int K = TK_LS_STEPS;
   __shared__ float red[4][K + 1];
@@ -1608,13 +1668,14 @@ __global__ __launch_bounds__(256) void ls_ksteps_farplane_kernel(
   for (long p = p0 + threadIdx.x; p < p1; p += blockDim.x) {
     float I0[1] = {0.f}, C[1] = {0.f}, I1[1] = {0.f};
     const float raw[1] = {data[n * npix + p]};
+    const unsigned bits = MK ? (mask[p] ? 1u : 0u) : 1u;
     for (int s = 0; s < S; ++s) {
       const cf a = FA[s * npix + p], b = FB[s * npix + p];
       I0[0] += norm2(a);
       C[0] += a.x * b.x + a.y * b.y;
       I1[0] += norm2(b);
     }
-    tk_ksteps_costs<K, 1, FIRST>(I0, C, I1, raw, step0, acc);
+    tk_ksteps_costs<K, 1, FIRST, MODEL, MK>(I0, C, I1, raw, bits, step0, acc);
   }
   tk_ksteps_emit<K, FIRST>(acc, red, costs_k, stride, n, row1, inv_nmeasured, part,
                            (int)blockIdx.x);
@@ -1625,11 +1686,13 @@ __global__ __launch_bounds__(256) void ls_ksteps_farplane_kernel(
 // First pass: fx on entry is ignored -- the cost at x is row 0, formed with the
 // same arithmetic as the trials it is compared with -- and kept in state[0] for
 // the passes behind it.  A pass that accepts nothing leaves step = the next
-// length to try; the last one also counts a failure.
+// length to try; the last one also counts a failure.  relative (poisson): the
+// rows of the step lengths hold cost(s) - cost(x); a step is accepted when that
+// is no larger than 0, and state[0] = cost(x) + the difference.
 __global__ __launch_bounds__(256) void ls_pick_kernel(const float* __restrict__ costs_k,
                                                       long stride, int n, double inv_count,
                                                       int row1, int first, int last,
-                                                      double* __restrict__ state,
+                                                      int relative, double* __restrict__ state,
                                                       int* __restrict__ accepted) {
   constexpr int K = TK_LS_STEPS;
   __shared__ double red[256];
@@ -1650,16 +1713,17 @@ __global__ __launch_bounds__(256) void ls_pick_kernel(const float* __restrict__ 
   }
   if (threadIdx.x == 0) {
     const double fx = first ? mean[0] : state[0];
+    const double bar = relative ? 0.0 : fx;
     float s = (float)state[1];
     int pick = -1;
     for (int k = 0; k < K; ++k, s *= 0.5f) {
-      if (mean[k + 1] <= fx) {
+      if (mean[k + 1] <= bar) {
         pick = k;
         break;
       }
     }
     if (pick >= 0) {
-      state[0] = mean[pick + 1];
+      state[0] = relative ? fx + mean[pick + 1] : mean[pick + 1];
       state[1] = (double)s;
       state[2] = 1.0;
       state[3] += (double)(pick + 1);
@@ -1702,22 +1766,23 @@ __global__ __launch_bounds__(256) void ls_rowsum_kernel(const float* __restrict_
 
 // The decision of ls_pick_kernel from (all-reduced) row sums.
 __global__ void ls_pick_sums_kernel(const double* __restrict__ sums, double inv_count, int row1,
-                                    int first, int last, double* __restrict__ state,
-                                    int* __restrict__ accepted) {
+                                    int first, int last, int relative,
+                                    double* __restrict__ state, int* __restrict__ accepted) {
   constexpr int K = TK_LS_STEPS;
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   if (!first && state[2] != 0.0) return;
   const double fx = first ? sums[0] * inv_count : state[0];
+  const double bar = relative ? 0.0 : fx;
   float s = (float)state[1];
   int pick = -1;
   for (int k = 0; k < K; ++k, s *= 0.5f) {
-    if (sums[row1 + k] * inv_count <= fx) {
+    if (sums[row1 + k] * inv_count <= bar) {
       pick = k;
       break;
     }
   }
   if (pick >= 0) {
-    state[0] = sums[row1 + pick] * inv_count;
+    state[0] = relative ? fx + sums[row1 + pick] * inv_count : sums[row1 + pick] * inv_count;
     state[1] = (double)s;
     state[2] = 1.0;
     state[3] += (double)(pick + 1);
@@ -1743,17 +1808,18 @@ __global__ __launch_bounds__(256) void ls_apply_kernel(const cf* __restrict__ x,
   }
 }
 
-extern "C" int tike_cgrad_line_search_linear(int variable, const void* x, const void* d, void* xs,
-                                             const void* other, const float* scan,
-                                             const void* data, int data_u16, void* far_a,
-                                             int a_valid, void* far_b, float* costs_k,
-                                             int nscan, int chunk, int S, int det, int H, int W,
-                                             float fwd_scale, double count, double* state,
-                                             int stage, double* sums, void* stream_) {
-  TK_ENTER();
-  hipStream_t stream = (hipStream_t)stream_;
+static int tk_cgrad_line_search_linear(int variable, const void* x, const void* d, void* xs,
+                                       const void* other, const float* scan, const void* data,
+                                       int data_u16, void* far_a, int a_valid, void* far_b,
+                                       float* costs_k, int nscan, int chunk, int S, int det,
+                                       int H, int W, float fwd_scale, double count,
+                                       double* state, int stage, double* sums,
+                                       const unsigned char* measured, int model,
+                                       long num_measured, hipStream_t stream) {
   TK_CHECK_ARG(nscan >= 1 && chunk >= 1 && S >= 1 && H >= 1 && W >= 1 && count > 0 &&
                (variable == 0 || variable == 1));
+  TK_CHECK_ARG((model == 0 || model == 1) && num_measured > 0 &&
+               num_measured <= (long)det * det);
   TK_CHECK_ARG(x && d && xs && other && scan && data && far_a && far_b && far_a != far_b &&
                costs_k && state);
   // stage 0: the whole search (one rank).  Several ranks, whose cost sums
@@ -1784,7 +1850,8 @@ extern "C" int tike_cgrad_line_search_linear(int variable, const void* x, const 
   const bool reuse = a_valid && nscan <= chunk;  // the gradient pass left F(x) in far_a
   const bool resident = nscan <= chunk;          // one chunk: both hand-offs stay put
   const size_t dsz = data_u16 ? 2 : 4;
-  const float inv = 1.0f / (float)((long)det * det);
+  const float inv = 1.0f / (float)num_measured;
+  const bool mk = measured != nullptr;
   // forward model of the direction: d in place of the variable
   const void* psi_b = variable == 0 ? d : other;
   const void* probe_b = variable == 0 ? other : d;
@@ -1819,14 +1886,27 @@ extern "C" int tike_cgrad_line_search_linear(int variable, const void* x, const 
         const long npix = (long)det * det;
         const dim3 grid((unsigned)((npix + TK_FG_PIX - 1) / TK_FG_PIX), (unsigned)m);
         const float* dchunk = (const float*)data + (size_t)lo * npix;
+#define TK_LSF(FIRST, M, MK)                                                                  \
+  hipLaunchKernelGGL((ls_ksteps_farplane_kernel<FIRST, M, MK>), grid, dim3(256), 0, stream,      \
+                     (const cf*)far_a, (const cf*)far_b, dchunk, measured, costs_k + lo,          \
+                     (long)nscan, S, npix, inv, row1, state, part ? part + lo : part)
+#define TK_LSF_M(FIRST)          \
+  do {                           \
+    if (model == 0 && !mk)       \
+      TK_LSF(FIRST, 0, false);   \
+    else if (model == 0)         \
+      TK_LSF(FIRST, 0, true);    \
+    else if (!mk)                \
+      TK_LSF(FIRST, 1, false);   \
+    else                         \
+      TK_LSF(FIRST, 1, true);    \
+  } while (0)
         if (pass == 0)
-          hipLaunchKernelGGL(ls_ksteps_farplane_kernel<true>, grid, dim3(256), 0, stream,
-                             (const cf*)far_a, (const cf*)far_b, dchunk, costs_k + lo,
-                             (long)nscan, S, npix, inv, row1, state, part ? part + lo : part);
+          TK_LSF_M(true);
         else
-          hipLaunchKernelGGL(ls_ksteps_farplane_kernel<false>, grid, dim3(256), 0, stream,
-                             (const cf*)far_a, (const cf*)far_b, dchunk, costs_k + lo,
-                             (long)nscan, S, npix, inv, row1, state, part ? part + lo : part);
+          TK_LSF_M(false);
+#undef TK_LSF_M
+#undef TK_LSF
         if (part)
           hipLaunchKernelGGL(ls_costs_finish_kernel, dim3(tk_grid((long)(m * 9 + 255) / 256, 8)),
                              dim3(256), 0, stream, costs_k, part, (long)nscan, lo, lo + m,
@@ -1846,16 +1926,28 @@ extern "C" int tike_cgrad_line_search_linear(int variable, const void* x, const 
       const long nitem = (long)m * 16 * (det / 256);
       const dim3 grid(tk_grid(nitem, 32)), block(256);
       const char* dchunk = (const char*)data + dsz * (size_t)lo * det * det;
-#define TK_LSK(N, DT, FIRST)                                                                  \
-  hipLaunchKernelGGL((ls_ksteps_colpass_kernel<N, DT, FIRST>), grid, block, 0, stream,           \
-                     (const cf*)far_a, (const cf*)far_b, (const DT*)dchunk, costs_k + lo,        \
-                     (long)nscan, nitem, S, fwd_scale, inv, row1, state, part ? part + lo : part)
-#define TK_LSK_N(N, DT)      \
-  do {                       \
-    if (pass == 0)           \
-      TK_LSK(N, DT, true);   \
-    else                     \
-      TK_LSK(N, DT, false);  \
+#define TK_LSK(N, DT, FIRST, M, MK)                                                           \
+  hipLaunchKernelGGL((ls_ksteps_colpass_kernel<N, DT, FIRST, M, MK>), grid, block, 0, stream,    \
+                     (const cf*)far_a, (const cf*)far_b, (const DT*)dchunk, measured,            \
+                     costs_k + lo, (long)nscan, nitem, S, fwd_scale, inv, row1, state,           \
+                     part ? part + lo : part)
+#define TK_LSK_M(N, DT, FIRST)           \
+  do {                                   \
+    if (model == 0 && !mk)               \
+      TK_LSK(N, DT, FIRST, 0, false);    \
+    else if (model == 0)                 \
+      TK_LSK(N, DT, FIRST, 0, true);     \
+    else if (!mk)                        \
+      TK_LSK(N, DT, FIRST, 1, false);    \
+    else                                 \
+      TK_LSK(N, DT, FIRST, 1, true);     \
+  } while (0)
+#define TK_LSK_N(N, DT)        \
+  do {                         \
+    if (pass == 0)             \
+      TK_LSK_M(N, DT, true);   \
+    else                       \
+      TK_LSK_M(N, DT, false);  \
   } while (0)
       if (det == 256 && data_u16)
         TK_LSK_N(256, unsigned short);
@@ -1866,6 +1958,7 @@ extern "C" int tike_cgrad_line_search_linear(int variable, const void* x, const 
       else
         TK_LSK_N(512, float);
 #undef TK_LSK_N
+#undef TK_LSK_M
 #undef TK_LSK
       if (part)
         hipLaunchKernelGGL(ls_costs_finish_kernel, dim3(tk_grid((long)(m * 9 + 255) / 256, 8)),
@@ -1875,13 +1968,13 @@ extern "C" int tike_cgrad_line_search_linear(int variable, const void* x, const 
     if (stage == 0)
       hipLaunchKernelGGL(ls_pick_kernel, dim3(1), dim3(256), 0, stream, costs_k, (long)nscan,
                          nscan, 1.0 / count, row1, (int)(pass == 0),
-                         (int)(pass + 1 == TK_LS_PASSES), state, accepted);
+                         (int)(pass + 1 == TK_LS_PASSES), model, state, accepted);
     else if (costs_now)
       hipLaunchKernelGGL(ls_rowsum_kernel, dim3(1), dim3(256), 0, stream, costs_k, (long)nscan,
                          nscan, row1, (int)(pass == 0), state, sums);
     else
       hipLaunchKernelGGL(ls_pick_sums_kernel, dim3(1), dim3(64), 0, stream, sums, 1.0 / count,
-                         row1, (int)(pass == 0), (int)(pass + 1 == TK_LS_PASSES), state,
+                         row1, (int)(pass == 0), (int)(pass + 1 == TK_LS_PASSES), model, state,
                          accepted);
   }
   if (stage != 0 && stage != 4) {
@@ -1892,6 +1985,33 @@ extern "C" int tike_cgrad_line_search_linear(int variable, const void* x, const 
                      (const cf*)x, (const cf*)d, (cf*)xs, n, state);
   TK_LAUNCH_CHECK();
   return TK_OK;
+}
+
+extern "C" int tike_cgrad_line_search_linear(int variable, const void* x, const void* d, void* xs,
+                                             const void* other, const float* scan,
+                                             const void* data, int data_u16, void* far_a,
+                                             int a_valid, void* far_b, float* costs_k,
+                                             int nscan, int chunk, int S, int det, int H, int W,
+                                             float fwd_scale, double count, double* state,
+                                             int stage, double* sums, void* stream_) {
+  TK_ENTER();
+  return tk_cgrad_line_search_linear(variable, x, d, xs, other, scan, data, data_u16, far_a,
+                                     a_valid, far_b, costs_k, nscan, chunk, S, det, H, W,
+                                     fwd_scale, count, state, stage, sums, nullptr, 0,
+                                     (long)det * det, (hipStream_t)stream_);
+}
+
+extern "C" int tike_cgrad_line_search_linear_masked(
+    int variable, const void* x, const void* d, void* xs, const void* other, const float* scan,
+    const void* data, int data_u16, void* far_a, int a_valid, void* far_b, float* costs_k,
+    int nscan, int chunk, int S, int det, int H, int W, float fwd_scale, double count,
+    double* state, int stage, double* sums, const unsigned char* measured, int model,
+    long num_measured, void* stream_) {
+  TK_ENTER();
+  return tk_cgrad_line_search_linear(variable, x, d, xs, other, scan, data, data_u16, far_a,
+                                     a_valid, far_b, costs_k, nscan, chunk, S, det, H, W,
+                                     fwd_scale, count, state, stage, sums, measured, model,
+                                     num_measured, (hipStream_t)stream_);
 }
 
 // ------------------------------------------- 128^2: the whole tile in LDS

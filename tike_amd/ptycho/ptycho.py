@@ -185,8 +185,12 @@ def _check_data_shape(data, parameters):
     (reference ptycho.py:303-331: same conditions, same messages)."""
     frames = tuple(int(n) for n in data.shape)
     window = tuple(int(n) for n in parameters.probe.shape[-2:])
-    mask = tuple(parameters.exitwave_options.measured_pixels.shape)
-    masked = parameters.algorithm_options.name != "cgrad"  # cgrad: no mask
+    measured = parameters.exitwave_options.measured_pixels
+    mask = tuple(measured.shape)
+    # cgrad: a mask whose pixels are all measured means "every pixel", whatever
+    # its shape (the probe-shaped default); one with unmeasured pixels is a mask
+    masked = (parameters.algorithm_options.name != "cgrad"
+              or not bool(np.all(np.asarray(A.to_host(measured)))))
     rules = (
         (len(frames) == 3 and min(frames) >= 1 and frames[1] == frames[2],
          f"data shape {data.shape} is incorrect. "

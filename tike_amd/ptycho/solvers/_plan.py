@@ -5,7 +5,8 @@ The reference keys a plan on (shape, dtype, device) once and reuses it
 transforms, `ptycho/solvers/lstsq.py:422-579`).  Here the counterpart of that
 plan is the ROUTE a chunk takes through the HIP entries -- which kernels, in
 which order, with which workspaces -- decided once per (detector, probe
-window, modes, noise model, step rule, mask, switches) and cached on the
+window, modes, noise model, step rule, mask, plain gradient, switches) and
+cached on the
 operator; `_get_nearplane_gradients` only walks the chunks.  The plan also
 names its launches and carries their byte models, so that `bench.py` prices a
 launch on what the plan says it moves instead of re-deriving it by entry name.
@@ -26,6 +27,10 @@ Routes:
                three launches of csrc/general.hip
   unfused      what is left (Bluestein sizes, poisson on general shapes): the
                operators one by one on a stored far plane
+
+A PLAIN plan (cgrad) forms the gradient of the cost itself -- no per-mode
+step lengths: poisson then takes the route gaussian takes for the same shape,
+with the poisson terms (model 1) in the same kernels.
 """
 from dataclasses import dataclass
 from types import SimpleNamespace
@@ -145,22 +150,26 @@ class GradientPlan:
     chunk: int
     launches: tuple       # the C-ABI entries of one chunk, in order
     groups: tuple = ()    # more modes than one pass-2 launch holds: (first, count)s
+    plain: bool = False   # the gradient of the cost (cgrad): no poisson steps
 
     def bytes(self, entry, n, C=0):
         return algorithmic_bytes(entry, n, self.S, self.det, self.pw, C)
 
     @staticmethod
     def for_(op, S, pw, det, exitwave_options, mask_u8, eigen_modes=0,
-             num_eigen=0):
+             num_eigen=0, plain=False):
         """The plan of this shape on this operator (cached on it, keyed also on
-        the module switches tests and A/B runs flip)."""
+        the module switches tests and A/B runs flip).  plain: the gradient of
+        the noise model's cost, without lstsq's per-mode step lengths."""
         from . import lstsq as L
         eo = exitwave_options
         unmeasured = float(eo.unmeasured_pixels_scaling)
         from ... import _lib
+        # (a plain plan reads neither the step rule nor the scaling of the
+        # unmeasured pixels: they are left out of its key)
         key = (_lib.DETERMINISTIC, S, pw, det, eo.noise_model,
-               eo.step_length_usemodes,
-               mask_u8 is not None, unmeasured == 1.0,
+               None if plain else eo.step_length_usemodes,
+               mask_u8 is not None, True if plain else unmeasured == 1.0,
                tuple(L.POSITION_MAJOR_SIZES), tuple(L.NO_FARPLANE_SIZES),
                tuple(L.SPLIT_FORWARD_SIZES), tuple(L.ONE_LAUNCH_GRADIENT_SIZES),
                L.POISSON_FROM_HANDOFF, L.POISSON_STEPS_IN_PASS2,
@@ -168,17 +177,20 @@ class GradientPlan:
                L.CHUNK_POSITIONS_OVERRIDE,
                L.mode_groups(S, pw, det, eigen_modes),
                bool(lib.tike_ifft2_pass2_eigen_fits(det, num_eigen,
-                                                    eigen_modes)))
+                                                    eigen_modes)),
+               bool(plain))
         cache = op.__dict__.setdefault("_tike_amd_plans", {})
         if key not in cache:
             cache[key] = GradientPlan._build(S, pw, det, eo, mask_u8, unmeasured,
-                                             L, eigen_modes, key[-1])
+                                             L, eigen_modes, key[-2], key[-1])
         return cache[key]
 
     @staticmethod
     def _build(S, pw, det, eo, mask_u8, unmeasured, L, eigen_modes=0,
-               eigen_fits=True):
-        poisson = eo.noise_model == "poisson"
+               eigen_fits=True, plain=False):
+        # (poisson: lstsq's exit-wave update with its per-mode step lengths; a
+        # plain plan routes poisson as gaussian, the model only in the kernels)
+        poisson = eo.noise_model == "poisson" and not plain
         dominant = int(poisson and eo.step_length_usemodes == "dominant_mode")
         all_modes = poisson and not dominant
         pos_major = det in L.POSITION_MAJOR_SIZES
@@ -285,7 +297,7 @@ class GradientPlan:
             launches=tuple("tike_ifft2_pass2_gradients_modes"
                            if groups and e == "tike_ifft2_pass2_gradients" else e
                            for e in launches),
-            groups=groups)
+            groups=groups, plain=bool(plain))
 
     # -------------------------------------------------------- workspaces
     def eigen_q(self, C, Sm, H, W):

@@ -3,10 +3,12 @@
 The reference snapshot ships no ptychography ``cgrad``; it is
 composed here, as BASELINE's configs ask, from the reference's own pieces:
 ``tike.opt.conjugate_gradient`` (opt.py:312-380: Dai-Yuan direction,
-backtracking line search), the gaussian cost ``Ptycho.cost`` (ptycho.py:193-204)
-and the gradient ``Ptycho.adj(gaussian_grad(...))`` (objective.py:31-44),
-following the multi-GPU pattern of lamino/solvers/cgrad.py:58-92: the cost and
-the gradient are summed over ranks, every rank then takes the same step.
+backtracking line search), the cost ``Ptycho.cost(..., model=...)``
+(ptycho.py:193-204) and its gradient ``Ptycho.adj(<model>_grad(...))``
+(objective.py:31-44, :90-104) on the measured pixels (``lstsq.py:448-452``
+selects them), following the multi-GPU pattern of lamino/solvers/cgrad.py:58-92:
+the cost and the gradient are summed over ranks, every rank then takes the same
+step.
 """
 import logging
 
@@ -19,22 +21,38 @@ from ... import opt
 from ..._lib import check, lib
 from ...operators.propagation import fft_scales
 from ..exitwave import ExitWaveOptions
+from ._plan import MODELS
 from .lstsq import (SPLIT_FORWARD_SIZES, _get_nearplane_gradients, _workspace,
-                    chunk_positions, fused_gradients, global_count,
+                    chunk_positions, fused_gradients, global_count, mask_info,
                     minibatch_key)
 
 
 logger = logging.getLogger(__name__)
 
-_GAUSSIAN = {}
+_ALL_MEASURED = {}
 
 
-def _gaussian_options(det):
-    """Every pixel measured, gaussian noise: the cost cgrad minimises."""
-    if det not in _GAUSSIAN:
-        _GAUSSIAN[det] = ExitWaveOptions(
-            measured_pixels=np.ones((det, det), dtype=bool))
-    return _GAUSSIAN[det]
+def _cost_model(exitwave_options, det):
+    """What cgrad minimises, from the caller's exit-wave options: (options the
+    gradient passes read, model 0 / 1, measured pixels per pattern, uint8 mask
+    or None).  A mask whose pixels are all measured means every pixel, whatever
+    its shape (the probe-shaped default); one with unmeasured pixels must be
+    (det, det) -- mask_info raises otherwise.  The exit-wave relaxations of
+    lstsq / rpie (unmeasured_pixels_scaling, step_length_*) are no part of a
+    cost and are not read."""
+    eo = exitwave_options
+    if eo.noise_model not in MODELS:
+        raise ValueError(f"unknown noise model {eo.noise_model!r}")
+    model = MODELS[eo.noise_model]
+    if mask_info(eo)[1] is None:
+        key = (det, eo.noise_model)
+        if key not in _ALL_MEASURED:
+            _ALL_MEASURED[key] = ExitWaveOptions(
+                measured_pixels=np.ones((det, det), dtype=bool),
+                noise_model=eo.noise_model)
+        return _ALL_MEASURED[key], model, det * det, None
+    nmeasured, mask_u8 = mask_info(eo, det)
+    return eo, model, nmeasured, mask_u8
 
 
 class _CostPlan:
@@ -44,8 +62,11 @@ class _CostPlan:
     and one reduction -- at BASELINE configs[0] (256 positions of 128^2) the
     Python between the launches was most of the epoch."""
 
-    def __init__(self, op, data, scan, lo, hi, S, pw, H, W, dev):
+    def __init__(self, op, data, scan, lo, hi, S, pw, H, W, dev, cm):
         det = op.detector_shape
+        # the cost model (_cost_model)
+        self.options, self.model, self.nmeasured, self.mask = cm
+        pmask = A.ptr(self.mask) if self.mask is not None else None
         N = hi - lo
         ws = _workspace(op)
         self.split = det in SPLIT_FORWARD_SIZES
@@ -72,6 +93,7 @@ class _CostPlan:
         # resident data that the cost kernel of this size reads as it is
         direct = isinstance(data, torch.Tensor) and (
             self.split or data.dtype == torch.float32)
+        self.pmask = pmask
         self.chunks = []
         for clo in range(lo, hi, chunk):
             chi = min(hi, clo + chunk)
@@ -83,6 +105,7 @@ class _CostPlan:
         S, pw, det, H, W = self.dims
         st = A.stream_ptr()
         ppsi, pprobe, pfar = A.ptr(psi), A.ptr(probe), A.ptr(self.far)
+        mask, model, nmeasured = self.pmask, self.model, self.nmeasured
         for clo, chi, sc, d, cost in self.chunks:
             n = chi - clo
             if d is None:  # streamed from the host, or 16-bit counts at 128^2
@@ -94,9 +117,10 @@ class _CostPlan:
                                        det, H, W, st), "cgrad forward pass 1")
                 check(
                     lib.tike_fwd_gradient_scale(
-                        pfar, d.data_ptr(), self.u16, None, None, None,
-                        cost.data_ptr(), None, n, S, det, self.fwd_scale, 0,
-                        1.0, det * det, st), "cgrad forward pass 2 + cost")
+                        pfar, d.data_ptr(), self.u16, mask, None, None,
+                        cost.data_ptr(), None, n, S, det, self.fwd_scale,
+                        model, 1.0, nmeasured, st),
+                    "cgrad forward pass 2 + cost")
             elif self.pfa:
                 if self.pfa_lds:
                     check(
@@ -114,8 +138,8 @@ class _CostPlan:
                                             0, st), "cgrad sub-tile transforms")
                 check(
                     lib.tike_pfa_combine_gradient(
-                        pfar, d.data_ptr(), None, cost.data_ptr(), n, S, det,
-                        self.fwd_scale, 0, 1.0, det * det, 0, st),
+                        pfar, d.data_ptr(), mask, cost.data_ptr(), n, S, det,
+                        self.fwd_scale, model, 1.0, nmeasured, 0, st),
                     "cgrad cost (p x p combine)")
             else:
                 check(
@@ -123,9 +147,9 @@ class _CostPlan:
                                         None, 0, 0, pfar, n, S, pw, det, H, W,
                                         self.fwd_scale, 0, st), "cgrad forward")
                 check(
-                    lib.tike_farplane_gradient(pfar, d.data_ptr(), None, None,
-                                               cost.data_ptr(), n, S, det, 0,
-                                               0, 1.0, det * det, st),
+                    lib.tike_farplane_gradient(pfar, d.data_ptr(), mask, None,
+                                               cost.data_ptr(), n, S, det,
+                                               model, 0, 1.0, nmeasured, st),
                     "cgrad cost")
         return self.costs
 
@@ -167,8 +191,8 @@ class _CostPlan:
             check(
                 lib.tike_lstsq_chunk_gradients(
                     A.ptr(psi), sc.data_ptr(), A.ptr(probe), None, None, 0, 0,
-                    d.data_ptr(), self.u16, None, 0, 1.0, det * det,
-                    A.ptr(self.far), A.ptr(mid), A.ptr(gscale),
+                    d.data_ptr(), self.u16, self.pmask, self.model, 1.0,
+                    self.nmeasured, A.ptr(self.far), A.ptr(mid), A.ptr(gscale),
                     A.ptr(patches[clo - lo:chi - lo]), cost.data_ptr(),
                     A.ptr(objproj) if want_psi else None, None, A.ptr(mpu), 1.0,
                     A.ptr(acc), n, S, det, H, W, self.fwd_scale, inv_scale,
@@ -179,9 +203,10 @@ class _CostPlan:
 
 
 def _cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, *, want_psi,
-                   want_probe, want_grad, read_cost=True, plan=None):
-    """Global gaussian cost (mean over all positions and pixels) of the
-    minibatch [lo, hi) and, optionally, d cost / d psi and d cost / d probe
+                   want_probe, want_grad, cm, read_cost=True, plan=None):
+    """Global cost (mean over all positions of each pattern's mean over its
+    measured pixels, the noise model of `cm`, _cost_model) of the minibatch
+    [lo, hi) and, optionally, d cost / d psi and d cost / d probe
     (unnormalised adjoints).
 
     The gradient is the one lstsq_grad forms (the same kernels, whatever the
@@ -190,7 +215,6 @@ def _cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, *, want_psi,
     dev = psi.device
     N = hi - lo
     S, pw = probe.shape[-3], probe.shape[-1]
-    det = op.detector_shape
     H, W = psi.shape[-2:]
     if want_grad and plan is not None and plan.supports_gradients():
         costs, acc, mpu = plan.gradients(op, comm, psi, probe, want_psi,
@@ -200,8 +224,8 @@ def _cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, *, want_psi,
     elif want_grad:
         g = _get_nearplane_gradients(
             data, psi, scan, probe, None, None, lo, hi, comm, num_batch=1,
-            exitwave_options=_gaussian_options(det), op=op,
-            recover_psi=want_psi, recover_probe=want_probe, need_chi0=False)
+            exitwave_options=cm[0], op=op, recover_psi=want_psi,
+            recover_probe=want_probe, need_chi0=False, plain=True)
         costs = g["costs"]
         gpsi = gprobe = None
         if want_psi:
@@ -210,7 +234,7 @@ def _cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, *, want_psi,
             gprobe = -g["m_probe_update"]
     else:
         gpsi = gprobe = None
-        plan = plan or _CostPlan(op, data, scan, lo, hi, S, pw, H, W, dev)
+        plan = plan or _CostPlan(op, data, scan, lo, hi, S, pw, H, W, dev, cm)
         costs = plan.run(data, psi, probe)
     total = costs.sum(dtype=torch.float64)  # device scalar (this rank)
     if read_cost:
@@ -379,23 +403,25 @@ def _cg_enqueue(plan, op, comm, x, other, variable, num_iter, step_init,
             # each pass are all-reduced between the pass and its decision
             for stage in ((1, 2, 3, 4) if comm.collective else (0,)):
                 check(
-                    lib.tike_cgrad_line_search_linear(
+                    lib.tike_cgrad_line_search_linear_masked(
                         variable, A.ptr(x), A.ptr(d), A.ptr(xs), A.ptr(other),
                         scan_ptr, data_ptr, plan.u16, A.ptr(plan.far), a_valid,
                         A.ptr(far_b), A.ptr(costs_k), N, plan.far.shape[0], S,
                         det, H, W, plan.fwd_scale, count, A.ptr(state), stage,
-                        A.ptr(row_sums), st_ptr),
+                        A.ptr(row_sums), plan.pmask, plan.model,
+                        plan.nmeasured, st_ptr),
                     "cgrad line search (all steps at once)")
                 if stage in (1, 3):
                     comm.Allreduce_f64(row_sums)
         else:
             check(
-                lib.tike_cgrad_line_search(
+                lib.tike_cgrad_line_search_masked(
                     variable, A.ptr(x), A.ptr(d), A.ptr(xs), A.ptr(other),
                     scan_ptr, data_ptr, plan.u16, A.ptr(plan.far),
                     A.ptr(plan.costs), N, plan.far.shape[0], S, det, H, W,
                     plan.fwd_scale, count, A.ptr(state), A.ptr(skip),
-                    slots[0 if i == 0 else 1], st_ptr),
+                    slots[0 if i == 0 else 1], plan.pmask, plan.model,
+                    plan.nmeasured, st_ptr),
                 "cgrad line search")
         out[5 + i].copy_(state[3])
         x = xs
@@ -583,6 +609,7 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
     recover_probe = (parameters.probe_options is not None
                      and epoch >= parameters.probe_options.update_start)
     psi, probe, scan = parameters.psi, parameters.probe, parameters.scan
+    cm = _cost_model(parameters.exitwave_options, op.detector_shape)
     batch_cost = []
     for batch_index, b in enumerate(batches):
         lo = int(b[0]) if len(b) else 0
@@ -592,7 +619,7 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
         cost = None
         finish = lambda total: _finish_cost(total, comm, op, lo, hi)
         plan = _CostPlan(op, d, s, lo, hi, probe.shape[-3], probe.shape[-1],
-                         psi.shape[-2], psi.shape[-1], psi.device)
+                         psi.shape[-2], psi.shape[-1], psi.device, cm)
         # line searches decided on the device: one rank, HBM-resident data,
         # the far-plane-free sizes and 128^2
         # (several ranks: the all-at-once search, whose cost sums are
@@ -616,8 +643,8 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
             def run(x, want_grad):
                 r = _cost_and_grad(op, comm, d, x, s, probe, lo, hi,
                                    want_psi=True, want_probe=False,
-                                   want_grad=want_grad, read_cost=False,
-                                   plan=plan)
+                                   want_grad=want_grad, cm=cm,
+                                   read_cost=False, plan=plan)
                 return r[0], r[1]
             ev = _Evaluator(run, finish)
             psi, cost = opt.conjugate_gradient(
@@ -634,8 +661,8 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
             def run(x, want_grad):
                 r = _cost_and_grad(op, comm, d, psi, s, x, lo, hi,
                                    want_psi=False, want_probe=True,
-                                   want_grad=want_grad, read_cost=False,
-                                   plan=plan)
+                                   want_grad=want_grad, cm=cm,
+                                   read_cost=False, plan=plan)
                 return r[0], r[2]
             ev = _Evaluator(run, finish)
             probe, cost = opt.conjugate_gradient(
@@ -644,7 +671,7 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
                 step_length=o.step_length)
         if cost is None:
             cost = _cost_and_grad(op, comm, d, psi, s, probe, lo, hi, want_psi=False,
-                                  want_probe=False, want_grad=False)[0]
+                                  want_probe=False, want_grad=False, cm=cm)[0]
         batch_cost.append(cost)
     if any(isinstance(c, torch.Tensor) for c in batch_cost):
         # device-side searches leave the cost on the device: one read-back

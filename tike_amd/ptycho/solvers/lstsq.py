@@ -480,7 +480,7 @@ def _get_nearplane_gradients(data, psi, scan, probe, eigen_probe,
                              eigen_weights, lo, hi, comm, *, num_batch,
                              exitwave_options, op, recover_psi, recover_probe,
                              position_terms=None, need_chi0=True,
-                             want_q=False):
+                             want_q=False, plain=False):
     """Object / probe gradients of one minibatch (lstsq.py:367-602).  Which
     kernels a chunk runs is the GradientPlan of the shape (`_plan.py`, cached
     on the operator like the reference's FFT plan, cache.py:32-46); this
@@ -488,7 +488,10 @@ def _get_nearplane_gradients(data, psi, scan, probe, eigen_probe,
     need_chi0=False (cgrad: no step statistics follow) skips the store of
     mode 0 of chi where the fused pass 2 would be its only producer.
     want_q: pass 2 also leaves q[n] = sum_p Re(conj(O_n) chi_n,0 conj(E_0))
-    where the route allows it (returned as "q", None otherwise)."""
+    where the route allows it (returned as "q", None otherwise).
+    plain=True (cgrad): the gradient of the noise model's cost on the measured
+    pixels -- no per-mode poisson step lengths, unmeasured pixels get none
+    (unmeasured_pixels_scaling is not part of a cost)."""
     dev = psi.device
     B = hi - lo
     S, pw = probe.shape[-3], probe.shape[-1]
@@ -505,7 +508,7 @@ def _get_nearplane_gradients(data, psi, scan, probe, eigen_probe,
     w_old = None if eigen_weights is None else eigen_weights[lo:hi]
     ep, _, C, Sm = _eigen_args(eigen_probe, w_old)
     plan = GradientPlan.for_(op, S, pw, det, exitwave_options, mask_u8,
-                             eigen_modes=Sm, num_eigen=C)
+                             eigen_modes=Sm, num_eigen=C, plain=plain)
 
     # planar (real plane, imaginary plane) float32 accumulator of the object
     # gradient: the shape float atomics run fastest on; recombined below
@@ -540,7 +543,8 @@ def _get_nearplane_gradients(data, psi, scan, probe, eigen_probe,
         op=op, data=data, psi=psi, probe=probe, ep=ep, eigen_probe=eigen_probe,
         C=C, Sm=Sm, H=H, W=W, st=A.stream_ptr(), fwd_scale=fwd_scale,
         inv_scale=inv_scale, nmeasured=nmeasured, mask_u8=mask_u8,
-        unmeasured=float(exitwave_options.unmeasured_pixels_scaling),
+        unmeasured=(1.0 if plain else
+                    float(exitwave_options.unmeasured_pixels_scaling)),
         step_start=float(exitwave_options.step_length_start),
         step_weight=float(exitwave_options.step_length_weight), buf=buf,
         m_probe_update=m_probe_update, num_batch=num_batch,

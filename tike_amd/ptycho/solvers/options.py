@@ -52,7 +52,15 @@ class RpieOptions(IterativeOptions):
 @dataclasses.dataclass
 class CgradOptions(IterativeOptions):
     """Conjugate-gradient solver composed from tike.opt.conjugate_gradient
-    (the reference snapshot has no ptychography cgrad)."""
+    (the reference snapshot has no ptychography cgrad).
+
+    It minimises the mean over positions of each pattern's mean cost over its
+    measured pixels, under ``exitwave_options.noise_model`` (gaussian or
+    poisson) and ``exitwave_options.measured_pixels``.  A mask whose pixels
+    are all True means every pixel, whatever its shape; a mask with unmeasured
+    pixels must have the data's shape.  ``unmeasured_pixels_scaling`` and
+    ``step_length_{weight,usemodes,start}`` relax lstsq's / rpie's exit-wave
+    update, are no part of a cost and are ignored here."""
     name: str = dataclasses.field(default="cgrad", init=False)
     batch_method: str = "compact"
     cg_iter: int = 4
