@@ -38,7 +38,7 @@ extern "C" {
  * A binding compares tike_abi_version() of the loaded library with the
  * TIKE_ABI_VERSION it was written against before its first call
  * (tike_amd/_lib.py does; INTEGRATION.md shows the check). */
-#define TIKE_ABI_VERSION 13
+#define TIKE_ABI_VERSION 14
 
 /* sha256 (64 hex digits) of the sources the library was built from: the PMC
  * traffic files under profiles/ carry it, and bench.py withholds a traffic
@@ -546,6 +546,32 @@ int tike_position_sums(const void* patches, const void* chi, int chi_modes, cons
                        const void* eigen_probe, const float* eigen_weights, int num_eigen,
                        int eigen_modes, const float* taps, int radius, float* numerator,
                        float* denominator, int nscan, int S, int pw, void* stream);
+
+/* ---- position correction for rPIE (the sums the reference writes out for it,
+ * rpie.py:508-548, with the update of rpie.py:158-170, 570-612): the same two
+ * sums as tike_position_sums, but over ALL probe modes,
+ *   numerator[n]   = ( sum_s sum Re(conj(gx P_n,s) chi_n,s), same with gy )
+ *   denominator[n] = ( sum_s sum |gx P_n,s|^2,               same with gy )
+ * formed without chi: sum_s Re(conj(g P_s) chi_s) = Re(conj(g) objproj) and
+ * sum_s |g P_s|^2 = |g|^2 sum_s |P_s|^2, with objproj (nscan,pw,pw) c64 =
+ * sum_s conj(P_n,s) chi_n,s, the input of tike_scatter_patches.  gx / gy are
+ * taken on the bilinear patch of psi (H,W) at scan[n] (edge mode 'nearest' at
+ * the PATCH border, position.py:779-810), gathered from psi: no patch is read.
+ * Window [pw/4, pw - pw/4) on both axes, pw >= 4.  Positions must satisfy
+ * check_allowed_positions (position.py:600-628); a corner outside is moved
+ * inside rather than read out of bounds.  The probe: probe (1|nscan,S,pw,pw)
+ * selected by probe_per_scan, or, with eigen_weights != NULL (probe_per_scan
+ * = 0), varying as in tike_ptycho_fwd.  intensity_work (pw,pw) f32: scratch
+ * for sum_s |probe_s|^2 of a shared probe (may be NULL otherwise).  taps: HOST
+ * floats as in tike_position_sums.  numerator, denominator (nscan,2) f32 are
+ * overwritten.  Small batches split the window over workgroups and add with
+ * float atomics; not in deterministic mode. */
+int tike_rpie_position_sums(const void* objproj, const void* psi, const float* scan,
+                            const void* probe, int probe_per_scan, const void* eigen_probe,
+                            const float* eigen_weights, int num_eigen, int eigen_modes,
+                            const float* taps, int radius, float* intensity_work,
+                            float* numerator, float* denominator, int nscan, int S, int pw,
+                            int H, int W, void* stream);
 
 /* ---- the chunk body of _get_nearplane_gradients for ANY shape (round 6;
  * ptycho/solvers/lstsq.py:422-579 = operators/cupy/ptycho.py:114-176 around

@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("TIKE_AMD_LIB") or os.path.join(
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "tike_amd.h")
 
 # the header version this binding's prototypes were written against
-ABI_VERSION = 13
+ABI_VERSION = 14
 ERR_ARG = 1000001
 ERR_UNSUPPORTED = 1000002
 ERR_COMM = 2000000
@@ -131,6 +131,8 @@ _PROTOTYPES = {
                              _p],
     "tike_position_sums": [_p, _p, _i, _p, _p, _p, _i, _i, _p, _i, _p, _p, _i,
                            _i, _i, _p],
+    "tike_rpie_position_sums": [_p, _p, _p, _p, _i, _p, _p, _i, _i, _p, _i, _p,
+                                _p, _p, _i, _i, _i, _i, _i, _p],
     "tike_farplane_gradient": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _l,
                                _p],
     "tike_intensity": [_p, _p, _l, _i, _l, _p],

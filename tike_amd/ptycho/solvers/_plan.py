@@ -588,7 +588,8 @@ class GradientPlan:
         the stored chi otherwise."""
         b, S, det, pw = c.buf, self.S, self.det, self.pw
         n, st = k.n, c.st
-        objproj = A.ptr(b.objproj) if c.recover_psi else None
+        objproj = (A.ptr(b.objproj) if getattr(c, "want_objproj",
+                                               c.recover_psi) else None)
         chi0 = A.ptr(k.chi0) if c.need_chi0 and k.chi0 is not None else None
         if self.pfa:
             check(

@@ -480,7 +480,8 @@ def _get_nearplane_gradients(data, psi, scan, probe, eigen_probe,
                              eigen_weights, lo, hi, comm, *, num_batch,
                              exitwave_options, op, recover_psi, recover_probe,
                              position_terms=None, need_chi0=True,
-                             want_q=False, plain=False):
+                             want_q=False, plain=False,
+                             all_mode_position_terms=None):
     """Object / probe gradients of one minibatch (lstsq.py:367-602).  Which
     kernels a chunk runs is the GradientPlan of the shape (`_plan.py`, cached
     on the operator like the reference's FFT plan, cache.py:32-46); this
@@ -491,7 +492,11 @@ def _get_nearplane_gradients(data, psi, scan, probe, eigen_probe,
     where the route allows it (returned as "q", None otherwise).
     plain=True (cgrad): the gradient of the noise model's cost on the measured
     pixels -- no per-mode poisson step lengths, unmeasured pixels get none
-    (unmeasured_pixels_scaling is not part of a cost)."""
+    (unmeasured_pixels_scaling is not part of a cost).
+    all_mode_position_terms (rpie): (numerator, denominator) of the shift
+    estimate summed over ALL probe modes, from the object projection of every
+    chunk (`all_mode_position_sums`); the projection is then formed whether
+    or not the object is recovered."""
     dev = psi.device
     B = hi - lo
     S, pw = probe.shape[-3], probe.shape[-1]
@@ -548,7 +553,8 @@ def _get_nearplane_gradients(data, psi, scan, probe, eigen_probe,
         step_start=float(exitwave_options.step_length_start),
         step_weight=float(exitwave_options.step_length_weight), buf=buf,
         m_probe_update=m_probe_update, num_batch=num_batch,
-        recover_psi=recover_psi, need_chi0=need_chi0)
+        recover_psi=recover_psi, need_chi0=need_chi0,
+        want_objproj=bool(recover_psi or all_mode_position_terms))
     chunk = plan.chunk
     for clo in range(lo, hi, chunk):
         chi_hi = min(hi, clo + chunk)
@@ -585,6 +591,11 @@ def _get_nearplane_gradients(data, psi, scan, probe, eigen_probe,
                     A.ptr(position_terms[0][clo:chi_hi]),
                     A.ptr(position_terms[1][clo:chi_hi]), n, S, pw, c.st),
                 "position shift sums")
+        if all_mode_position_terms:
+            all_mode_position_sums(
+                op, buf.objproj[:n], psi, k.scan, probe, ep, k.w,
+                all_mode_position_terms[0][clo:chi_hi],
+                all_mode_position_terms[1][clo:chi_hi])
         if chi_hi == hi and early:
             # the probe gradient is complete: its slice of the flat buffer
             # travels while the last object scatter runs
@@ -619,6 +630,40 @@ def _get_nearplane_gradients(data, psi, scan, probe, eigen_probe,
                 object_acc=obj_acc, m_probe_update=m_probe_update,
                 costs=buf.costs[:B], count=count, local_count=B,
                 q=None if q is None else q[:B])
+
+
+def all_mode_position_sums(op, objproj, psi, scan, probe, eigen_probe, weights,
+                           numerator, denominator, *, per_scan=False):
+    """numerator / denominator (n, 2) of the shift estimate of n positions,
+    summed over every probe mode (the sums rpie.py:508-548 sketches), from
+    objproj (n, pw, pw) = sum_s conj(P_n,s) chi_n,s and the first slice of psi
+    (`tike_rpie_position_sums`).  probe: shared, with `weights` (n, C + 1, S)
+    varying through the eigen probes, or -- per_scan -- one per position."""
+    n = objproj.shape[0]
+    S, pw = probe.shape[-3], probe.shape[-1]
+    taps, taps_r = gaussian_derivative_taps(sigma=0.333)
+    ep, w, C, Sm = _eigen_args(eigen_probe, weights)
+    work = _workspace(op).get("probe_intensity", (pw, pw), torch.float32,
+                              psi.device)
+    check(
+        lib.tike_rpie_position_sums(
+            A.ptr(objproj), A.ptr(psi[0]), A.ptr(scan), A.ptr(probe),
+            int(per_scan), A.ptr(ep), A.ptr(w), C, Sm, taps.ctypes.data,
+            taps_r, A.ptr(work), A.ptr(numerator), A.ptr(denominator), n, S,
+            pw, psi.shape[-2], psi.shape[-1], A.stream_ptr()),
+        "position shift sums (all modes)")
+
+
+def positions_allowed_flag(scan, psi_shape, pw):
+    """check_allowed_positions (position.py:600-628) as a 0-d float32 device
+    tensor: 1 where a patch or its +1 taps would leave the object (NaN
+    positions included), else 0 -- to travel with a device->host read that
+    happens anyway."""
+    corner = torch.floor(scan)
+    room = torch.tensor([psi_shape[-2] - pw - 1, psi_shape[-1] - pw - 1],
+                        dtype=scan.dtype, device=scan.device)
+    ok = ((corner >= 1) & (corner <= room)).all()
+    return (~ok).to(torch.float32)
 
 
 def object_upd_sum(g):

@@ -14,8 +14,22 @@ Quirks of the reference kept on purpose, because the bar is its iterates:
 the probe numerator is re-zeroed by every minibatch (rpie.py:349), so in
 'compact' mode only the last minibatch moves the probe; it is only formed
 when the object is recovered (:462); the probe step is ``alpha *
-max(preconditioner)`` alone (:271-280); position correction is commented out
-(:163-176, 521-563).
+max(preconditioner)`` alone (:271-280).
+
+Position correction is the one thing here the reference only sketches: its
+sums (:508-548) and its update (:158-170, 570-612) are written out there but
+switched off.  With ``position_options`` set they run: per minibatch the
+least-squares shift estimate of every position, summed over ALL probe modes
+and over the central half of the probe window, from the exit-wave update that
+reaches the first slice; after the last minibatch of the epoch one
+``lstsq._update_position`` with ``alpha`` of the algorithm options (every
+minibatch of the epoch saw the old positions, as in ``lstsq_grad``).  The sums
+need no ``chi``: sum_s Re(conj(g P_s) chi_s) = Re(conj(g) objproj) and
+sum_s |g P_s|^2 = |g|^2 sum_s |P_s|^2, with objproj = sum_s conj(P_s) chi_s
+the input of the object scatter that every route forms anyway
+(``tike_rpie_position_sums``).  The moved positions are tested against
+``check_allowed_positions`` on the device, the flag travels with the epoch's
+cost, and the solver raises before any kernel sees them.
 """
 import logging
 
@@ -30,6 +44,7 @@ from ... import random as trandom
 from ..._lib import check, lib
 from ...operators.multislice import fused_slices, next_incident_probe
 from ...operators.propagation import fft_scales
+from ..position import check_allowed_positions
 from ..probe import get_varying_probe
 from . import lstsq as L
 
@@ -44,12 +59,20 @@ def rpie(parameters, data, batches, comm, *, op, epoch):
     exitwave_options = parameters.exitwave_options
     object_options = parameters.object_options
     probe_options = parameters.probe_options
+    position_options = parameters.position_options
     if exitwave_options.noise_model not in L._MODELS:
         raise ValueError(
             f"unknown noise model {exitwave_options.noise_model!r}")
     recover_probe = (probe_options is not None
                      and epoch >= probe_options.update_start)
     recover_psi = object_options is not None
+    if position_options is not None and psi.shape[0] > 1 and not recover_psi:
+        # (:445: without the object the walk back through the slices does not
+        # happen, and the first slice never receives its exit-wave update)
+        raise ValueError(
+            "rpie corrects the positions of a multislice object only while "
+            "the object is recovered: set object_options or drop "
+            "position_options.")
     compact = o.batch_method == "compact"
     order = (range(o.num_batch) if compact else
              trandom.randomizer_np.permutation(o.num_batch))
@@ -59,6 +82,18 @@ def rpie(parameters, data, batches, comm, *, op, epoch):
     dev = psi.device
     psi_num = probe_num = None
     batch_cost = torch.zeros(o.num_batch, dtype=torch.float32, device=dev)
+    position_terms = None
+    if position_options is not None:
+        if position_options.use_position_regularization and epoch > 0:
+            # the affine pull that followed the last epoch moved the positions
+            # after they were tested (this configuration fits on the host
+            # every epoch: the read-back is one among several)
+            _raise_unless_allowed(
+                float(_positions_flag(scan, psi, probe, comm)), scan, psi,
+                probe)
+        if epoch >= position_options.update_start:
+            # numerator / denominator of the shift estimate, all local positions
+            position_terms = (torch.zeros_like(scan), torch.zeros_like(scan))
     for n in order:
         lo = int(batches[n][0]) if len(batches[n]) else 0
         hi = lo + len(batches[n])
@@ -68,15 +103,27 @@ def rpie(parameters, data, batches, comm, *, op, epoch):
         cost, probe_num = _get_nearplane_gradients(
             data, psi, scan, probe, eigen_probe, eigen_weights, lo, hi, comm,
             psi_num, op=op, exitwave_options=exitwave_options,
-            recover_psi=recover_psi, recover_probe=recover_probe)
+            recover_psi=recover_psi, recover_probe=recover_probe,
+            position_terms=position_terms)
         batch_cost[n] = cost
         if not compact:
             psi, probe = _update(psi, probe, psi_num, probe_num,
                                  object_options, probe_options, recover_probe,
                                  o)
             psi_num = probe_num = None
-    # one device->host scalar per epoch, as in the reference (rpie.py:161)
-    o.costs.append([float(batch_cost.mean().item())])
+    if position_terms is None:
+        # one device->host scalar per epoch, as in the reference (rpie.py:161)
+        o.costs.append([float(batch_cost.mean().item())])
+    else:
+        # the minibatches above all used the old positions
+        scan = L._update_position(scan, position_options, *position_terms,
+                                  comm, alpha=o.alpha, epoch=epoch)
+        # ... and the new ones must not reach a kernel unless every patch
+        # stays inside the object: the flag shares the cost's read-back
+        flag = _positions_flag(scan, psi, probe, comm)
+        cost, flag = torch.stack([batch_cost.mean(), flag]).tolist()
+        o.costs.append([float(cost)])
+        _raise_unless_allowed(flag, scan, psi, probe)
     if compact:
         psi, probe = _update(psi, probe, psi_num, probe_num, object_options,
                              probe_options, recover_probe, o,
@@ -93,7 +140,28 @@ def rpie(parameters, data, batches, comm, *, op, epoch):
         eigen_weights = eigen_weights / torch.sqrt(sq / n_local)
     parameters.psi, parameters.probe = psi, probe
     parameters.eigen_weights = eigen_weights
+    parameters.scan = scan
     return parameters
+
+
+def _positions_flag(scan, psi, probe, comm):
+    """0-d device tensor: 1 when a position of ANY rank breaks
+    check_allowed_positions, so that every rank decides alike."""
+    flag = L.positions_allowed_flag(scan, psi.shape, probe.shape[-1])
+    return comm.Allreduce_max(flag) if comm.collective else flag
+
+
+def _raise_unless_allowed(flag, scan, psi, probe):
+    """`flag`: `_positions_flag` read back.  The rank that owns the position
+    words the error as the reference does."""
+    if flag == 0.0:
+        return
+    check_allowed_positions(scan, psi, probe.shape)  # this rank's own
+    raise ValueError(
+        "Scan positions must be >= 1 and "
+        "scan positions + 1 + probe.shape must be <= psi.shape. "
+        "The position correction moved a position of another rank out of "
+        f"the object; the shape of psi is {tuple(psi.shape)}.")
 
 
 def _second_step(direction, options, errors):
@@ -141,9 +209,11 @@ def _update(psi, probe, psi_num, probe_num, object_options, probe_options,
 
 def _get_nearplane_gradients(data, psi, scan, probe, eigen_probe,
                              eigen_weights, lo, hi, comm, psi_num, *, op,
-                             exitwave_options, recover_psi, recover_probe):
+                             exitwave_options, recover_psi, recover_probe,
+                             position_terms=None):
     """Cost of the minibatch; psi_num (accumulated in place) and a fresh
-    probe numerator (D, 1, 1, S, pw, pw) (rpie.py:310-548)."""
+    probe numerator (D, 1, 1, S, pw, pw) (rpie.py:310-548).  position_terms:
+    (numerator, denominator) of the shift estimates, rows [lo, hi) filled."""
     dev = psi.device
     D = psi.shape[0]
     S = probe.shape[-3]
@@ -155,7 +225,8 @@ def _get_nearplane_gradients(data, psi, scan, probe, eigen_probe,
         g = L._get_nearplane_gradients(
             data, psi, scan, probe, eigen_probe, eigen_weights, lo, hi, comm,
             num_batch=1, exitwave_options=exitwave_options, op=op,
-            recover_psi=recover_psi, recover_probe=recover_psi)
+            recover_psi=recover_psi, recover_probe=recover_psi,
+            all_mode_position_terms=position_terms)
         if recover_psi:
             psi_num += L.object_upd_sum(g) / S
             probe_num[0] = g["m_probe_update"]
@@ -165,7 +236,7 @@ def _get_nearplane_gradients(data, psi, scan, probe, eigen_probe,
         costs, chi0, patches = _gradients_multislice(
             data, psi, scan, probe, eigen_probe, eigen_weights, lo, hi, comm,
             psi_num, probe_num, op=op, exitwave_options=exitwave_options,
-            recover_psi=recover_psi)
+            recover_psi=recover_psi, position_terms=position_terms)
         chi_modes = 1
     if recover_probe and eigen_weights is not None:
         # weights of the shared probe, mode 0 (rpie.py:505-519): the last two
@@ -219,7 +290,8 @@ def _fused_multislice_shapes(op, S, pw, exitwave_options, recover_psi, data):
 
 def _gradients_multislice_fused(data, psi, scan, probe, eigen_probe,
                                 eigen_weights, lo, hi, comm, psi_num,
-                                probe_num, *, op, exitwave_options):
+                                probe_num, *, op, exitwave_options,
+                                position_terms=None):
     """rpie.py:367-495 for an object of several slices on the fused kernels.
 
     Way forward, per slice d < D - 1: `tike_fwd_pass1` (patch of slice d x
@@ -363,6 +435,17 @@ def _gradients_multislice_fused(data, psi, scan, probe, eigen_probe,
                 costs[blo:blo + n], fwd_scale, unmeasured, nmeasured,
                 exitwave_options)
         mid = midv[0]
+
+        def first_slice_sums():
+            # objproj holds slice 0's projection now: the shift estimates of
+            # the chunk from it, the probe incident on slice 0 and psi[0]
+            if position_terms:
+                L.all_mode_position_sums(
+                    op, objproj[:n], psi, sc, unique, None, None,
+                    position_terms[0][clo:chi_hi],
+                    position_terms[1][clo:chi_hi],
+                    per_scan=incident[0][1] == 1)
+
         for tt in range(D - 1, -1, -1):
             beam, per = incident[tt]
             if step_back_in_frequency:
@@ -378,6 +461,7 @@ def _gradients_multislice_fused(data, psi, scan, probe, eigen_probe,
                     lib.tike_scatter_patches(A.ptr(objproj), A.ptr(sc),
                                              A.ptr(acc[0]), n, pw, H, W, st),
                     "object numerator")
+                first_slice_sums()
                 continue
             check(
                 lib.tike_ifft2_pass2_products(
@@ -391,6 +475,8 @@ def _gradients_multislice_fused(data, psi, scan, probe, eigen_probe,
                 lib.tike_scatter_patches(A.ptr(objproj), A.ptr(sc),
                                          A.ptr(acc[tt]), n, pw, H, W, st),
                 "object numerator")
+            if tt == 0:
+                first_slice_sums()
             if tt == 0 or step_back_in_frequency:
                 continue
             check(lib.tike_fft2_pass1(A.ptr(mid), A.ptr(far), n * S, det, 0,
@@ -451,13 +537,14 @@ def _stored_farplane_gradient(far, mid, data, lo, hi, mask_u8, costs,
 
 def _gradients_multislice(data, psi, scan, probe, eigen_probe, eigen_weights,
                           lo, hi, comm, psi_num, probe_num, *, op,
-                          exitwave_options, recover_psi):
+                          exitwave_options, recover_psi, position_terms=None):
     """rpie.py:367-495 for an object of several slices, slice by slice."""
     if _fused_multislice_shapes(op, probe.shape[-3], probe.shape[-1],
                                 exitwave_options, recover_psi, data):
         return _gradients_multislice_fused(
             data, psi, scan, probe, eigen_probe, eigen_weights, lo, hi, comm,
-            psi_num, probe_num, op=op, exitwave_options=exitwave_options)
+            psi_num, probe_num, op=op, exitwave_options=exitwave_options,
+            position_terms=position_terms)
     dev = psi.device
     B = hi - lo
     D = psi.shape[0]
@@ -532,6 +619,17 @@ def _gradients_multislice(data, psi, scan, probe, eigen_probe, eigen_weights,
                     A.ptr(pacc[tt]), n, S, pw, H, W, st),
                 "probe numerator")
             if tt == 0:
+                if position_terms:
+                    # slice 0's projection sum_s conj(P_n,s) diff_n,s with the
+                    # first incident probe; `diff` holds all modes here
+                    first = probes[0].reshape(-1, S, pw, pw)
+                    proj = torch.sum(first.conj() * diff.reshape(n, S, pw, pw),
+                                     dim=1).contiguous()
+                    L.all_mode_position_sums(
+                        op, proj, psi, sc, first.contiguous(), None, None,
+                        position_terms[0][clo:chi_hi],
+                        position_terms[1][clo:chi_hi],
+                        per_scan=first.shape[0] != 1)
                 break
             diff = op.diffraction.propagation.adj(diff)
         if not recover_psi:

@@ -139,7 +139,9 @@ print(f"lstsq_grad vs oracle: {cases - bad} of {cases} agree ({illcond} of them 
 GradientPlan.gradients = real
 
 # ---- rpie: single-slice and multislice objects (2 ... 3 slices; the fused chain
-# at 128^2 / 256^2, slice by slice elsewhere), both noise models
+# at 128^2 / 256^2, slice by slice elsewhere), both noise models, with and
+# without position correction (the NumPy composition of tests/rpie_positions.py)
+import rpie_positions as rp  # noqa: E402
 from oracle import operators as oops  # noqa: E402
 
 rcases = max(4, cases // 3)
@@ -152,13 +154,24 @@ for case in range(rcases):
     model = "poisson" if rng.random() < 0.3 else "gaussian"
     alpha = float(rng.choice((0.05, 0.5, 1.0)))
     nb = int(rng.choice((1, 2)))
+    # (positions are corrected from an object with structure, off by up to
+    # 0.7 px, with room around the scan for them to move)
+    positions = bool(alpha >= 0.5 and rng.random() < 0.5)
+    popts = dict(use_adaptive_moment=bool(rng.random() < 0.5),
+                 update_magnitude_limit=float(rng.choice((0, 1.0))),
+                 use_position_regularization=bool(rng.random() < 0.5))
     scan, psi_true, probe0, _, _, data = _headline_problem(
-        tp, det, S, N, seed=7000 + case, eigen=False)
+        tp, det, S, N, seed=7000 + case, eigen=False,
+        margin=24 if positions else 8)
     data = np.round(data * (20000.0 / data.max())).astype(np.float32)
-    psi0 = np.repeat(np.full_like(psi_true, 0.5), depth, axis=0)
+    psi0 = np.repeat(psi_true if positions else np.full_like(psi_true, 0.5),
+                     depth, axis=0)
     psi0[1:] = 1.0
+    if positions:
+        scan = (scan + rp.jitter(rng, scan.shape)).astype(np.float32)
     phys = dict(wavelength=1e-10, fov=(2e-6, 2e-6), distance=1e-6)
-    tag = f"rpie det {det} S {S} N {N} slices {depth} {model} alpha {alpha} batches {nb}"
+    tag = (f"rpie det {det} S {S} N {N} slices {depth} {model} alpha {alpha} "
+           f"batches {nb} positions {popts if positions else None}")
     batches = np.array_split(np.arange(N), nb)
     ms = dict(probe_wavelength=phys["wavelength"],
               probe_FOV_lengths=phys["fov"]) if depth > 1 else {}
@@ -170,9 +183,12 @@ for case in range(rcases):
         object_options=tp.ObjectOptions(
             **(dict(multislice_propagation_distance=phys["distance"])
                if depth > 1 else {})),
+        position_options=tp.PositionOptions(scan.copy(), **popts)
+        if positions else None,
         exitwave_options=tp.ExitWaveOptions(
             measured_pixels=np.ones((det, det), dtype=bool), noise_model=model))
     try:
+        tike_amd.random.randomizer_np = np.random.default_rng(11)
         with tp.Reconstruction(data, params, order=np.arange(N),
                                batches=batches) as ctx:
             ctx.iterate(2)
@@ -184,16 +200,26 @@ for case in range(rcases):
                      costs=[], eigen_probe=None, eigen_weights=None)
         kw = dict(propagator=propagator) if depth > 1 else {}
         state = osol.rescale_probe(state, data, det, **kw)
-        state = osol.iterate(state, data, batches, 2, detector_shape=det,
-                             solver="rpie", alpha=alpha, batch_method="compact",
-                             force_orthogonality=False, noise_model=model, **kw)
+        if positions:
+            state["position"] = rp.position_state(scan, **popts)
+            state = rp.iterate(state, data, batches, 2, detector_shape=det,
+                               alpha=alpha, batch_method="compact",
+                               force_orthogonality=False, noise_model=model,
+                               rng=np.random.default_rng(11), **kw)
+        else:
+            state = osol.iterate(state, data, batches, 2, detector_shape=det,
+                                 solver="rpie", alpha=alpha,
+                                 batch_method="compact",
+                                 force_orthogonality=False, noise_model=model,
+                                 **kw)
         ca = np.array(got.algorithm_options.costs).ravel()
         cb = np.array([np.ravel(c)[0] for c in state["costs"]])
         dc = float(np.max(np.abs(ca / cb - 1)))
         dp, dq = rel(got.psi, state["psi"]), rel(got.probe, state["probe"])
-        ok = dc < 1e-3 and dp < 1e-3 and dq < 2e-3
+        ds = float(np.abs(got.scan - state["scan"]).max())
+        ok = dc < 1e-3 and dp < 1e-3 and dq < 2e-3 and ds < 2e-3
         print(f"{'ok ' if ok else 'BAD'} {tag}: cost {dc:.1e} psi {dp:.1e} probe "
-              f"{dq:.1e}", flush=True)
+              f"{dq:.1e} scan {ds:.1e} px", flush=True)
         rbad += not ok
     except Exception as e:  # noqa: BLE001
         rbad += 1
