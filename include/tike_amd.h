@@ -38,7 +38,7 @@ extern "C" {
  * A binding compares tike_abi_version() of the loaded library with the
  * TIKE_ABI_VERSION it was written against before its first call
  * (tike_amd/_lib.py does; INTEGRATION.md shows the check). */
-#define TIKE_ABI_VERSION 14
+#define TIKE_ABI_VERSION 15
 
 /* sha256 (64 hex digits) of the sources the library was built from: the PMC
  * traffic files under profiles/ carry it, and bench.py withholds a traffic
@@ -1070,6 +1070,32 @@ int tike_lstsq_chunk_gradients(const void* psi, const float* scan, const void* p
                                void* objproj, void* chi0, void* m_probe_update,
                                float mpu_scale, float* object_acc, int nscan, int S, int det,
                                int H, int W, float fwd_scale, float inv_scale, void* stream);
+
+/* ---- the same chunk body followed by the shift estimate of its positions
+ * (cgrad with position_options): lstsq.py:545-579, summed over ALL probe modes
+ * as rpie.py:508-548 sketches, with the patch gradients of position.py:779-810
+ * fused -- tike_lstsq_chunk_gradients, then tike_rpie_position_sums on the
+ * objproj the chunk has just written (chi is whatever `model` makes it: with
+ * unmeasured_scaling = 1 the descent direction of the model's cost, 0 at the
+ * unmeasured pixels).  Arguments, shapes and supported sizes as in
+ * tike_lstsq_chunk_gradients, except that objproj may be given WITHOUT
+ * object_acc: the projection is formed for the sums and the scatter is
+ * skipped (object_acc needs objproj as before).  taps: HOST floats, radius
+ * taps_radius <= 4, as in tike_position_sums; intensity_work (det,det) f32:
+ * scratch for sum_s |P_s|^2 of a shared probe (may be NULL with
+ * eigen_weights); numerator, denominator (nscan,2) f32 are overwritten, in
+ * deterministic mode without atomics.  Both NULL: no sums, the entry is the
+ * chunk body alone (taps and intensity_work are not read); one NULL is an
+ * error.  With sums, objproj is required, H, W >= det + 2 and the positions
+ * must satisfy check_allowed_positions (position.py:600-628). */
+int tike_lstsq_chunk_gradients_positions(
+    const void* psi, const float* scan, const void* probe, const void* eigen_probe,
+    const float* eigen_weights, int num_eigen, int eigen_modes, const void* data, int data_u16,
+    const unsigned char* measured, int model, float unmeasured_scaling, long num_measured,
+    void* scratch, void* work, float* gscale, void* patches, float* costs, void* objproj,
+    void* chi0, void* m_probe_update, float mpu_scale, float* object_acc, int nscan, int S,
+    int det, int H, int W, float fwd_scale, float inv_scale, const float* taps, int taps_radius,
+    float* intensity_work, float* numerator, float* denominator, void* stream);
 
 /* ---- collectives: the per-minibatch gradient all-reduce over RCCL / xGMI,
  * one process (or thread) per GPU.  Replaces the serial peer-copy reduction of

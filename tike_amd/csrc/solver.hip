@@ -624,18 +624,14 @@ extern "C" int tike_lstsq_tail_finish(const float* tail3, const float* sums3, do
 
 // ------------------------------------------- the whole chunk body in one call
 // (lstsq.py:422-579): the five stage entries, stream-ordered.
-extern "C" int tike_lstsq_chunk_gradients(
+// chunk_body: what both entries below run once their own checks have passed.
+static int chunk_body(
     const void* psi, const float* scan, const void* probe, const void* eigen_probe,
     const float* eigen_weights, int num_eigen, int eigen_modes, const void* data, int data_u16,
     const unsigned char* measured, int model, float unmeasured_scaling, long num_measured,
     void* scratch, void* work, float* gscale, void* patches, float* costs, void* objproj,
     void* chi0, void* m_probe_update, float mpu_scale, float* object_acc, int nscan, int S,
     int det, int H, int W, float fwd_scale, float inv_scale, void* stream) {
-  TK_ENTER();
-  TK_CHECK_ARG(nscan >= 0 && S >= 1 && H >= 1 && W >= 1);
-  if (nscan == 0) return TK_OK;
-  TK_CHECK_ARG(psi && scan && probe && data && scratch && work && patches);
-  TK_CHECK_ARG(scratch != work && (object_acc == nullptr) == (objproj == nullptr));
   if (!((det == 128 && S <= 8) || (det == 256 && S <= 8) || (det == 512 && S <= 4)))
     return TK_ERR_UNSUPPORTED;
   TK_CHECK_ARG(gscale || det == 256);  // 256^2: the factor stays in registers
@@ -684,4 +680,56 @@ extern "C" int tike_lstsq_chunk_gradients(
   if (rc) return rc;
   if (object_acc) rc = tike_scatter_patches(objproj, scan, object_acc, nscan, det, H, W, stream);
   return rc;
+}
+
+extern "C" int tike_lstsq_chunk_gradients(
+    const void* psi, const float* scan, const void* probe, const void* eigen_probe,
+    const float* eigen_weights, int num_eigen, int eigen_modes, const void* data, int data_u16,
+    const unsigned char* measured, int model, float unmeasured_scaling, long num_measured,
+    void* scratch, void* work, float* gscale, void* patches, float* costs, void* objproj,
+    void* chi0, void* m_probe_update, float mpu_scale, float* object_acc, int nscan, int S,
+    int det, int H, int W, float fwd_scale, float inv_scale, void* stream) {
+  TK_ENTER();
+  TK_CHECK_ARG(nscan >= 0 && S >= 1 && H >= 1 && W >= 1);
+  if (nscan == 0) return TK_OK;
+  TK_CHECK_ARG(psi && scan && probe && data && scratch && work && patches);
+  TK_CHECK_ARG(scratch != work && (object_acc == nullptr) == (objproj == nullptr));
+  return chunk_body(psi, scan, probe, eigen_probe, eigen_weights, num_eigen, eigen_modes, data,
+                    data_u16, measured, model, unmeasured_scaling, num_measured, scratch, work,
+                    gscale, patches, costs, objproj, chi0, m_probe_update, mpu_scale, object_acc,
+                    nscan, S, det, H, W, fwd_scale, inv_scale, stream);
+}
+
+// The same chunk body, then the all-modes shift sums of the chunk's positions
+// (lstsq.py:545-579 summed over the modes as rpie.py:508-548 sketches, with
+// position.py:779-810 fused) from the objproj it has just written.  objproj
+// without object_acc: the projection is formed and the scatter is skipped.
+extern "C" int tike_lstsq_chunk_gradients_positions(
+    const void* psi, const float* scan, const void* probe, const void* eigen_probe,
+    const float* eigen_weights, int num_eigen, int eigen_modes, const void* data, int data_u16,
+    const unsigned char* measured, int model, float unmeasured_scaling, long num_measured,
+    void* scratch, void* work, float* gscale, void* patches, float* costs, void* objproj,
+    void* chi0, void* m_probe_update, float mpu_scale, float* object_acc, int nscan, int S,
+    int det, int H, int W, float fwd_scale, float inv_scale, const float* taps, int taps_radius,
+    float* intensity_work, float* numerator, float* denominator, void* stream) {
+  TK_ENTER();
+  TK_CHECK_ARG(nscan >= 0 && S >= 1 && H >= 1 && W >= 1);
+  TK_CHECK_ARG((numerator == nullptr) == (denominator == nullptr));
+  if (nscan == 0) return TK_OK;
+  TK_CHECK_ARG(psi && scan && probe && data && scratch && work && patches);
+  TK_CHECK_ARG(scratch != work && (objproj || !object_acc) && (objproj || !numerator));
+  if (numerator) {
+    // everything tike_rpie_position_sums would refuse, before the first launch
+    TK_CHECK_ARG(taps && taps_radius >= 0 && taps_radius <= 4 && H >= det + 2 && W >= det + 2);
+    TK_CHECK_ARG(intensity_work || eigen_weights);
+    TK_CHECK_ARG(!eigen_weights || num_eigen == 0 || (eigen_probe && eigen_modes >= 1));
+  }
+  int rc = chunk_body(psi, scan, probe, eigen_probe, eigen_weights, num_eigen, eigen_modes, data,
+                      data_u16, measured, model, unmeasured_scaling, num_measured, scratch, work,
+                      gscale, patches, costs, objproj, chi0, m_probe_update, mpu_scale,
+                      object_acc, nscan, S, det, H, W, fwd_scale, inv_scale, stream);
+  if (rc || !numerator) return rc;
+  return tike_rpie_position_sums(objproj, psi, scan, probe, 0, eigen_probe, eigen_weights,
+                                 num_eigen, eigen_modes, taps, taps_radius, intensity_work,
+                                 numerator, denominator, nscan, S, det, H, W, stream);
 }

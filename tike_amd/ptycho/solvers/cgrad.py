@@ -9,6 +9,17 @@ backtracking line search), the cost ``Ptycho.cost(..., model=...)``
 selects them), following the multi-GPU pattern of lamino/solvers/cgrad.py:58-92:
 the cost and the gradient are summed over ranks, every rank then takes the same
 step.
+
+Position correction (``position_options``) is composed the same way, from what
+the other two solvers do: per minibatch, before its first CG step and at the
+old positions, the least-squares shift estimate of every position summed over
+all probe modes (``lstsq.all_mode_position_sums``, rpie's estimator; with one
+mode lstsq.py:545-579) with chi = cgrad's own near-plane descent direction,
+-adj(gaussian_grad) or -1/2 adj(poisson_grad), 0 at unmeasured pixels; after
+the last minibatch one ``lstsq._update_position`` with ``alpha`` of the
+algorithm options, the allowed-positions test of rpie, and only then the new
+``parameters.scan``.  The sums need the object projection alone, which the
+gradient pass of the object writes anyway (``_PositionTerms``).
 """
 import logging
 
@@ -21,10 +32,12 @@ from ... import opt
 from ..._lib import check, lib
 from ...operators.propagation import fft_scales
 from ..exitwave import ExitWaveOptions
+from ..position import gaussian_derivative_taps
 from ._plan import MODELS
-from .lstsq import (SPLIT_FORWARD_SIZES, _get_nearplane_gradients, _workspace,
-                    chunk_positions, fused_gradients, global_count, mask_info,
-                    minibatch_key)
+from .lstsq import (SPLIT_FORWARD_SIZES, _get_nearplane_gradients,
+                    _update_position, _workspace, chunk_positions,
+                    fused_gradients, global_count, mask_info, minibatch_key)
+from .rpie import _positions_flag, _raise_unless_allowed
 
 
 logger = logging.getLogger(__name__)
@@ -53,6 +66,36 @@ def _cost_model(exitwave_options, det):
         return _ALL_MEASURED[key], model, det * det, None
     nmeasured, mask_u8 = mask_info(eo, det)
     return eo, model, nmeasured, mask_u8
+
+
+POISSON_POSITION_STEP = 0.5
+"""chi of the shift estimate under the Poisson model is this times cgrad's
+descent direction: 1 - d/I = (1 - sqrt(d/I)) (1 + sqrt(d/I)) ~ 2 (1 - sqrt(d/I))
+near the solution, so half the Poisson direction is the gaussian exit-wave
+difference there (it is also the reference's first Poisson step,
+exitwave.py `step_length_start`; the option itself is not read, as
+CgradOptions documents).  The numerator is linear in chi: applied to it once
+per epoch."""
+
+
+class _PositionTerms:
+    """(numerator, denominator) of the shift estimates of this rank's
+    positions, (N, 2) each, and which minibatch still owes its rows: the sums
+    are taken by the FIRST gradient evaluation of a minibatch -- at the
+    incoming iterate -- and by no later one (`take`)."""
+
+    def __init__(self, scan):
+        self.numerator = torch.zeros_like(scan)
+        self.denominator = torch.zeros_like(scan)
+        self.pending = False
+
+    def take(self):
+        """The two arrays if this minibatch's sums are still to be taken
+        (they count as taken from here on), else None."""
+        if not self.pending:
+            return None
+        self.pending = False
+        return self.numerator, self.denominator
 
 
 class _CostPlan:
@@ -94,6 +137,7 @@ class _CostPlan:
         direct = isinstance(data, torch.Tensor) and (
             self.split or data.dtype == torch.float32)
         self.pmask = pmask
+        self.lo = lo
         self.chunks = []
         for clo in range(lo, hi, chunk):
             chi = min(hi, clo + chunk)
@@ -162,10 +206,15 @@ class _CostPlan:
                 and fused_gradients(S, pw, det)
                 and all(c[3] is not None for c in self.chunks))
 
-    def gradients(self, op, comm, psi, probe, want_psi, want_probe):
+    def gradients(self, op, comm, psi, probe, want_psi, want_probe,
+                  position_terms=None):
         """(costs, -d cost / d psi or None, -d cost / d probe or None), the
         sums over the positions of all ranks -- what _get_nearplane_gradients
-        returns for this case, without its per-call set-up."""
+        returns for this case, without its per-call set-up.  position_terms:
+        (numerator, denominator) of all local positions; the rows of this
+        minibatch are filled chunk by chunk from the projection of the chunk
+        (tike_lstsq_chunk_gradients_positions), which is then formed whether
+        or not the object gradient is wanted."""
         S, pw, det, H, W = self.dims
         dev = psi.device
         ws = _workspace(op)
@@ -185,25 +234,37 @@ class _CostPlan:
                if want_probe else None)
         _, inv_scale = fft_scales(det, op.norm)
         st = A.stream_ptr()
-        lo = self.chunks[0][0]
+        lo = self.lo
+        if position_terms:
+            taps, taps_r = gaussian_derivative_taps(sigma=0.333)
+            inten = ws.get("probe_intensity", (pw, pw), torch.float32, dev)
         for clo, chi, sc, d, cost in self.chunks:
             n = chi - clo
-            check(
-                lib.tike_lstsq_chunk_gradients(
-                    A.ptr(psi), sc.data_ptr(), A.ptr(probe), None, None, 0, 0,
+            args = (A.ptr(psi), sc.data_ptr(), A.ptr(probe), None, None, 0, 0,
                     d.data_ptr(), self.u16, self.pmask, self.model, 1.0,
                     self.nmeasured, A.ptr(self.far), A.ptr(mid), A.ptr(gscale),
                     A.ptr(patches[clo - lo:chi - lo]), cost.data_ptr(),
-                    A.ptr(objproj) if want_psi else None, None, A.ptr(mpu), 1.0,
-                    A.ptr(acc), n, S, det, H, W, self.fwd_scale, inv_scale,
-                    st), "cgrad gradients")
+                    A.ptr(objproj) if want_psi or position_terms else None,
+                    None, A.ptr(mpu), 1.0, A.ptr(acc), n, S, det, H, W,
+                    self.fwd_scale, inv_scale)
+            if position_terms:
+                check(
+                    lib.tike_lstsq_chunk_gradients_positions(
+                        *args, taps.ctypes.data, taps_r, A.ptr(inten),
+                        A.ptr(position_terms[0][clo:chi]),
+                        A.ptr(position_terms[1][clo:chi]), st),
+                    "cgrad gradients + position shift sums")
+            else:
+                check(lib.tike_lstsq_chunk_gradients(*args, st),
+                      "cgrad gradients")
         if comm.collective and grads.numel():
             comm.Allreduce(grads)
         return self.costs, acc, mpu
 
 
 def _cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, *, want_psi,
-                   want_probe, want_grad, cm, read_cost=True, plan=None):
+                   want_probe, want_grad, cm, read_cost=True, plan=None,
+                   position_terms=None):
     """Global cost (mean over all positions of each pattern's mean over its
     measured pixels, the noise model of `cm`, _cost_model) of the minibatch
     [lo, hi) and, optionally, d cost / d psi and d cost / d probe
@@ -211,21 +272,24 @@ def _cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, *, want_psi,
 
     The gradient is the one lstsq_grad forms (the same kernels, whatever the
     detector size); a line-search probe (cost only) at 256^2 / 512^2 is the
-    split forward of that pipeline with nothing but the costs stored."""
+    split forward of that pipeline with nothing but the costs stored.
+    position_terms (with want_grad): (numerator, denominator) of the shift
+    estimates, rows [lo, hi) filled by this gradient pass."""
     dev = psi.device
     N = hi - lo
     S, pw = probe.shape[-3], probe.shape[-1]
     H, W = psi.shape[-2:]
     if want_grad and plan is not None and plan.supports_gradients():
         costs, acc, mpu = plan.gradients(op, comm, psi, probe, want_psi,
-                                         want_probe)
+                                         want_probe, position_terms)
         gpsi = -torch.complex(acc[0], acc[1])[None] if want_psi else None
         gprobe = -mpu if want_probe else None
     elif want_grad:
         g = _get_nearplane_gradients(
             data, psi, scan, probe, None, None, lo, hi, comm, num_batch=1,
             exitwave_options=cm[0], op=op, recover_psi=want_psi,
-            recover_probe=want_probe, need_chi0=False, plain=True)
+            recover_probe=want_probe, need_chi0=False, plain=True,
+            all_mode_position_terms=position_terms)
         costs = g["costs"]
         gpsi = gprobe = None
         if want_psi:
@@ -348,7 +412,8 @@ def _slot_policy(op):
 
 
 def _cg_enqueue(plan, op, comm, x, other, variable, num_iter, step_init,
-                count, data, scan, lo, hi, slots, bufs, linear=False):
+                count, data, scan, lo, hi, slots, bufs, linear=False,
+                positions=None):
     """Enqueue one conjugate-gradient call -- opt.conjugate_gradient
     (opt.py:312-380: Dai-Yuan directions, backtracking line search) for the
     object (variable 0) or the probe (variable 1) with every line search
@@ -358,7 +423,9 @@ def _cg_enqueue(plan, op, comm, x, other, variable, num_iter, step_init,
     captured as a graph).  step_init: device double[5] {0, step_length, 0, 0,
     0}; bufs: two iterates' worth of scratch.  Returns (the last iterate,
     device double[5 + num_iter]: the search state { fx, step, done, trials,
-    failures } followed by the running total of trials after every search)."""
+    failures } followed by the running total of trials after every search).
+    positions: the `_PositionTerms` of the epoch; the first gradient pass
+    takes the minibatch's sums if they are still owed."""
     dev = x.device
     S, pw, det, H, W = plan.dims
     N = hi - lo
@@ -388,8 +455,9 @@ def _cg_enqueue(plan, op, comm, x, other, variable, num_iter, step_init,
                                device=dev)
     for i in range(num_iter):
         a, b = (x, other) if variable == 0 else (other, x)  # psi, probe
-        costs, acc, mpu = plan.gradients(op, comm, a, b, variable == 0,
-                                         variable == 1)
+        costs, acc, mpu = plan.gradients(
+            op, comm, a, b, variable == 0, variable == 1,
+            positions.take() if positions is not None and i == 0 else None)
         check(
             lib.tike_cgrad_direction(
                 A.ptr(acc) if variable == 0 else None,
@@ -445,7 +513,7 @@ def _step_init(step_length, dev):
 
 def _cg_device(plan, op, comm, psi, probe, variable, num_iter, step_length,
                count, data, scan, lo, hi, slots=LINE_SEARCH_SLOTS,
-               linear=False):
+               linear=False, positions=None):
     """`_cg_enqueue` launched eagerly + its read-back.  Returns (x, mean
     cost, trials made by every search), or None when a search ran out of its
     slots -- the caller then repeats the call with more slots or with the
@@ -456,7 +524,7 @@ def _cg_device(plan, op, comm, psi, probe, variable, num_iter, step_length,
     return _cg_result(*_cg_enqueue(
         plan, op, comm, x, other, variable, num_iter,
         _step_init(step_length, x.device), count, data, scan, lo, hi, slots,
-        bufs, linear=linear))
+        bufs, linear=linear, positions=positions))
 
 
 USE_GRAPHS = _tuning.cgrad_graphs
@@ -507,12 +575,13 @@ def _every_rank(comm, op, lo, hi, mine):
 
 
 def _cg_on_device(plan, op, comm, psi, probe, variable, o, count, data, scan,
-                  lo, hi):
+                  lo, hi, positions=None):
     """One CG call on the device with the slot counts this reconstruction has
     learnt, replayed from a graph once the same call has been seen before; a
     call whose search runs out of slots is repeated once with every slot the
     entry allows before the host-side search takes over.  Returns (x, cost)
-    or None."""
+    or None.  positions: see `_cg_enqueue` (never with USE_GRAPHS: a replayed
+    graph would write the sums of the epoch it was captured in)."""
     policy = _slot_policy(op)
     x = psi if variable == 0 else probe
     other = probe if variable == 0 else psi
@@ -523,7 +592,7 @@ def _cg_on_device(plan, op, comm, psi, probe, variable, o, count, data, scan,
         if policy.linear_allowed(variable):
             r = _cg_device(plan, op, comm, psi, probe, variable, o.cg_iter,
                            o.step_length, count, data, scan, lo, hi,
-                           linear=True)
+                           linear=True, positions=positions)
             policy.linear_result(variable, r is not None)
         if r is not None:
             return r[0], r[1]
@@ -564,7 +633,7 @@ def _cg_on_device(plan, op, comm, psi, probe, variable, o, count, data, scan,
                 graphs[key] = False
             r = _cg_device(plan, op, comm, psi, probe, variable, o.cg_iter,
                            o.step_length, count, data, scan, lo, hi,
-                           slots=slots)
+                           slots=slots, positions=positions)
         else:
             r = _cg_result(*seen(x, other))
         if r is not None:
@@ -601,7 +670,9 @@ class _Evaluator:
 
 def cgrad(parameters, data, batches, comm, *, op, epoch):
     """One epoch: for every minibatch, `cg_iter` CG iterations on psi and
-    then (when probe recovery is on) on the probe."""
+    then (when probe recovery is on) on the probe; with position_options, one
+    position update after the last minibatch (every minibatch of the epoch
+    saw the old positions, as in lstsq_grad and rpie)."""
     o = parameters.algorithm_options
     if parameters.eigen_probe is not None or parameters.eigen_weights is not None:
         raise NotImplementedError("cgrad does not support eigen probes")
@@ -610,6 +681,17 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
                      and epoch >= parameters.probe_options.update_start)
     psi, probe, scan = parameters.psi, parameters.probe, parameters.scan
     cm = _cost_model(parameters.exitwave_options, op.detector_shape)
+    position_options = parameters.position_options
+    positions = None
+    if position_options is not None:
+        if position_options.use_position_regularization and epoch > 0:
+            # the affine pull that followed the last epoch moved the positions
+            # after they were tested (as rpie does at its entry)
+            _raise_unless_allowed(
+                float(_positions_flag(scan, psi, probe, comm)), scan, psi,
+                probe)
+        if epoch >= position_options.update_start:
+            positions = _PositionTerms(scan)
     batch_cost = []
     for batch_index, b in enumerate(batches):
         lo = int(b[0]) if len(b) else 0
@@ -633,18 +715,32 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
                          and _every_rank(comm, op, lo, hi, on_device))
         count = global_count(comm, op, lo, hi)
         done_psi = done_probe = False
+        if positions is not None:
+            positions.pending = True
+            # the object's first gradient pass writes the projection the sums
+            # need; without one (object not recovered, no CG iteration, or a
+            # CG call replayed from a graph) one extra gradient pass of the
+            # minibatch, nothing accumulated: every rank decides alike
+            if not (recover_psi and o.cg_iter >= 1
+                    and not (on_device and USE_GRAPHS)):
+                _cost_and_grad(op, comm, d, psi, s, probe, lo, hi,
+                               want_psi=False, want_probe=False,
+                               want_grad=True, cm=cm, read_cost=False,
+                               plan=plan, position_terms=positions.take())
         if recover_psi and on_device:
             r = _cg_on_device(plan, op, comm, psi, probe, 0, o, count, d, s,
-                              lo, hi)
+                              lo, hi, positions=positions)
             if r is not None:
                 psi, cost = r
                 done_psi = True
         if recover_psi and not done_psi:
             def run(x, want_grad):
-                r = _cost_and_grad(op, comm, d, x, s, probe, lo, hi,
-                                   want_psi=True, want_probe=False,
-                                   want_grad=want_grad, cm=cm,
-                                   read_cost=False, plan=plan)
+                r = _cost_and_grad(
+                    op, comm, d, x, s, probe, lo, hi, want_psi=True,
+                    want_probe=False, want_grad=want_grad, cm=cm,
+                    read_cost=False, plan=plan,
+                    position_terms=positions.take()
+                    if want_grad and positions is not None else None)
                 return r[0], r[1]
             ev = _Evaluator(run, finish)
             psi, cost = opt.conjugate_gradient(
@@ -673,13 +769,31 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
             cost = _cost_and_grad(op, comm, d, psi, s, probe, lo, hi, want_psi=False,
                                   want_probe=False, want_grad=False, cm=cm)[0]
         batch_cost.append(cost)
+    flag = None
+    if positions is not None:
+        # the minibatches above all used the old positions
+        numerator = positions.numerator
+        if cm[1] == MODELS["poisson"]:
+            numerator = POISSON_POSITION_STEP * numerator
+        scan = _update_position(scan, position_options, numerator,
+                                positions.denominator, comm, alpha=o.alpha,
+                                epoch=epoch)
+        # ... and the new ones must not reach a kernel unless every patch
+        # stays inside the object
+        flag = _positions_flag(scan, psi, probe, comm)
     if any(isinstance(c, torch.Tensor) for c in batch_cost):
         # device-side searches leave the cost on the device: one read-back
+        # (the allowed-positions flag travels with it)
         batch_cost = torch.stack([
             c.to(torch.float64) if isinstance(c, torch.Tensor) else
             torch.tensor(float(c), dtype=torch.float64, device=psi.device)
-            for c in batch_cost
+            for c in batch_cost + ([] if flag is None else [flag])
         ]).cpu().numpy()
+        if flag is not None:
+            batch_cost, flag = batch_cost[:-1], float(batch_cost[-1])
     o.costs.append([float(np.mean(batch_cost))])
+    if flag is not None:
+        _raise_unless_allowed(float(flag), scan, psi, probe)
+        parameters.scan = scan
     parameters.psi, parameters.probe = psi, probe
     return parameters

@@ -60,11 +60,16 @@ class CgradOptions(IterativeOptions):
     are all True means every pixel, whatever its shape; a mask with unmeasured
     pixels must have the data's shape.  ``unmeasured_pixels_scaling`` and
     ``step_length_{weight,usemodes,start}`` relax lstsq's / rpie's exit-wave
-    update, are no part of a cost and are ignored here."""
+    update, are no part of a cost and are ignored here.
+
+    ``alpha`` is the damping of the position step when ``position_options``
+    is set (``numerator / ((1 - alpha) denominator + alpha max(denominator))``,
+    as in lstsq_grad and rpie) and nothing else: the CG steps do not read it."""
     name: str = dataclasses.field(default="cgrad", init=False)
     batch_method: str = "compact"
     cg_iter: int = 4
     step_length: float = 1.0
+    alpha: float = 0.05
 
 
 @dataclasses.dataclass

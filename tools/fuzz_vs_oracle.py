@@ -3,7 +3,8 @@ detector 32 ... 256 of any factorisation (320 / 384 now and then), probe window
 <= detector, 1 ... 10 modes, none / one / two eigen probes on 1 ... 3 modes, masks
 with NaN counts, both noise models and both Poisson step rules, uint16 counts,
 probe-only runs, 1 ... 3 minibatches under both update rules -- two epochs,
-costs and final iterates.
+costs and final iterates; then rpie and cgrad problems, the latter also with
+position correction against the composition of tests/cgrad_positions.py.
 
     gpurun -- python tools/fuzz_vs_oracle.py [cases=60] [seed=0]
 
@@ -273,5 +274,73 @@ for case in range(ccases):
     except Exception as e:  # noqa: BLE001
         cbad += 1
         print(f"ERR {tag}: {type(e).__name__}: {str(e)[:240]}", flush=True)
-print(f"cgrad vs oracle: {ccases - cbad} of {ccases} agree")
-sys.exit(1 if bad or rbad or cbad else 0)
+print(f"cgrad vs oracle: {ccases - cbad} of {ccases} agree", flush=True)
+
+# ---- cgrad with position correction against the composition of
+# tests/cgrad_positions.py (shift sums at the incoming iterate of every
+# minibatch, one update per epoch): both noise models, masks, every gradient
+# route, object and / or probe recovered, at the tests' bars
+import cgrad_positions as cp  # noqa: E402
+import rpie_positions as rp  # noqa: E402
+
+pcases = max(4, cases // 4)
+pbad = 0
+for case in range(pcases):
+    det = int(rng.choice(SIZES))
+    pw = det if rng.random() < 0.7 else int(det - 2 * rng.integers(1, max(2, det // 6)))
+    S = int(rng.integers(1, 4))
+    N = int(rng.integers(6, 12))
+    cg_iter = int(rng.integers(1, 4))
+    model = "poisson" if rng.random() < 0.4 else "gaussian"
+    masked = bool(rng.random() < 0.4)
+    recover_psi = bool(rng.random() < 0.8)
+    recover_probe = bool(rng.random() < 0.7)
+    popts = dict(use_adaptive_moment=bool(rng.random() < 0.5),
+                 update_magnitude_limit=float(rng.choice((0.0, 0.5, 1.0))),
+                 use_position_regularization=bool(rng.random() < 0.3))
+    tag = (f"cgrad+positions det {det} pw {pw} S {S} N {N} cg_iter {cg_iter} "
+           f"{model} mask {masked} psi {recover_psi} probe {recover_probe}")
+    true, psi_true, probe, data, mask, prng = cp.problem(
+        det, pw, S, N, 12000 + case, masked=masked)
+    scan0 = (true + rp.jitter(prng, true.shape)).astype(np.float32)
+    psi0 = cp.start(psi_true)
+    batches = np.array_split(np.arange(N), 2)
+    params = tp.PtychoParameters(
+        probe=probe.copy(), psi=psi0.copy(), scan=scan0.copy(),
+        algorithm_options=tp.CgradOptions(num_batch=2, cg_iter=cg_iter,
+                                          num_iter=2, alpha=1.0,
+                                          batch_method="contiguous"),
+        probe_options=tp.ProbeOptions(init_rescale_from_measurements=False)
+        if recover_probe else None,
+        object_options=tp.ObjectOptions() if recover_psi else None,
+        position_options=tp.PositionOptions(scan0.copy(), **popts),
+        exitwave_options=tp.ExitWaveOptions(
+            measured_pixels=mask if masked else np.ones((pw, pw), bool),
+            noise_model=model))
+    try:
+        tike_amd.random.randomizer_np = np.random.default_rng(11)
+        with tp.Reconstruction(data, params, order=np.arange(N),
+                               batches=batches) as ctx:
+            ctx.iterate(2)
+            got = ctx.get_result()
+        state = dict(psi=psi0.copy(), probe=probe.copy(), scan=scan0.copy(),
+                     costs=[], position=rp.position_state(scan0, **popts))
+        state = cp.iterate(state, data, batches, 2, detector_shape=det,
+                           model=model, mask=mask, cg_iter=cg_iter, alpha=1.0,
+                           recover_psi=recover_psi,
+                           recover_probe=recover_probe,
+                           rng=np.random.default_rng(11))
+        ca = np.array(got.algorithm_options.costs).ravel()
+        cb = np.array([np.ravel(c)[0] for c in state["costs"]])
+        dc = float(np.max(np.abs(ca / cb - 1)))
+        ds = float(np.abs(got.scan - state["scan"]).max())
+        dp, dq = rel(got.psi, state["psi"]), rel(got.probe, state["probe"])
+        ok = dc < 1e-3 and ds < 2e-3 and dp < 1e-3 and dq < 1e-3
+        print(f"{'ok ' if ok else 'BAD'} {tag}: costs {dc:.1e} scan {ds:.1e} px "
+              f"psi {dp:.1e} probe {dq:.1e}", flush=True)
+        pbad += not ok
+    except Exception as e:  # noqa: BLE001
+        pbad += 1
+        print(f"ERR {tag}: {type(e).__name__}: {str(e)[:240]}", flush=True)
+print(f"cgrad + positions vs composition: {pcases - pbad} of {pcases} agree")
+sys.exit(1 if bad or rbad or cbad or pbad else 0)
