@@ -38,7 +38,7 @@ extern "C" {
  * A binding compares tike_abi_version() of the loaded library with the
  * TIKE_ABI_VERSION it was written against before its first call
  * (tike_amd/_lib.py does; INTEGRATION.md shows the check). */
-#define TIKE_ABI_VERSION 15
+#define TIKE_ABI_VERSION 16
 
 /* sha256 (64 hex digits) of the sources the library was built from: the PMC
  * traffic files under profiles/ carry it, and bench.py withholds a traffic
@@ -1096,6 +1096,28 @@ int tike_lstsq_chunk_gradients_positions(
     void* chi0, void* m_probe_update, float mpu_scale, float* object_acc, int nscan, int S,
     int det, int H, int W, float fwd_scale, float inv_scale, const float* taps, int taps_radius,
     float* intensity_work, float* numerator, float* denominator, void* stream);
+
+/* ---- position refinement by the gradient of intensity (Dwivedi et al. 2018):
+ * the sums of position.py:654-689 in one streaming pass.  far0, far_dx, far_dy
+ * (nscan,S,npix) c64: the far plane at the positions, at the positions moved by
+ * dx along the SECOND scan coordinate (the reference's scan + (0, dx)) and
+ * along the FIRST (scan + (dx, 0)).  data (nscan,npix) f32, or uint16 when
+ * data_u16 != 0.  Per pixel, with I = sum_s |far0_s|^2:
+ *   r = data - I
+ *   b = inv_dx * sum_s 2 Re((far0_s - far_dx_s) conj(far0_s))
+ *   a = the same with far_dy
+ * sums (nscan,5) f32 = (sum a^2, sum a b, sum b^2, sum a r, sum b r): the
+ * normal equations of lstsq([a, b], r) (position.py:685-689), overwritten.
+ * costs (nscan) f32 or NULL: mean((sqrt(I) - sqrt(data))^2), the gaussian
+ * cost of every pattern (objective.py:47-66).  I, a, b and the sums are
+ * formed in float64 (a r, b r and a b cancel over the pixels) and rounded
+ * once at the end.  Every input is read once; one
+ * workgroup per position, no atomics: two calls give the same bits.  No
+ * allocation.  TIKE_ERR_ARG for a NULL array, S < 1 or npix < 1; nscan == 0
+ * returns 0 without a launch. */
+int tike_position_pd_sums(const void* far0, const void* far_dx, const void* far_dy,
+                          const void* data, int data_u16, float inv_dx, float* sums,
+                          float* costs, long nscan, int S, long npix, void* stream);
 
 /* ---- collectives: the per-minibatch gradient all-reduce over RCCL / xGMI,
  * one process (or thread) per GPU.  Replaces the serial peer-copy reduction of

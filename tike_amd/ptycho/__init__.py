@@ -5,7 +5,8 @@ from .object import (ObjectOptions, get_absorbtion_image, get_padded_object,
                      positivity_constraint,
                      remove_object_ambiguity, smoothness_constraint)
 from .position import (AffineTransform, PositionOptions,
-                       affine_position_regularization, check_allowed_positions)
+                       affine_position_regularization, check_allowed_positions,
+                       position_pd_shifts, update_positions_pd)
 from .probe import (ProbeOptions, add_modes_cartesian_hermite,
                     add_modes_random_phase, adjust_probe_power,
                     apply_median_filter_abs_probe, constrain_center_peak,
@@ -24,6 +25,7 @@ __all__ = [
     "AffineTransform", "PositionOptions", "affine_position_regularization",
     "ProbeOptions", "PtychoParameters", "Reconstruction",
     "RpieOptions", "cgrad", "check_allowed_positions", "lstsq_grad",
+    "position_pd_shifts", "update_positions_pd",
     "reconstruct", "reconstruct_multigrid", "rpie", "simulate",
     "update_preconditioners",
 ]

@@ -33,7 +33,8 @@ from ..operators import Ptycho
 from . import _spawn, solvers
 from .object import (positivity_constraint, remove_object_ambiguity,
                      smoothness_constraint)
-from .position import (affine_position_regularization,
+from .position import (_pd_cost_sum, _pd_moved, _pd_solve, _pd_sums_device,
+                       affine_position_regularization,
                        check_allowed_positions,
                        estimate_global_transformation_ransac, ransac_subsets)
 from .probe import (apply_median_filter_abs_probe, constrain_center_peak,
@@ -469,6 +470,42 @@ class Reconstruction():
             logger.info("%10s cost is %+1.3e",
                         self.parameters.exitwave_options.noise_model,
                         np.mean(o.costs[-1]))
+
+    def update_positions_pd(self, dx=-1.0, step=0.05):
+        """One step of the gradient-of-intensity position refinement
+        (`position.update_positions_pd`, reference position.py:631-703) on
+        the context's own state, between `iterate` calls of any solver: the
+        resident (or host-kept) patterns in their order, the shared or eigen
+        probe, one or several slices.  Returns the mean gaussian cost at the
+        new positions.
+
+        In a process group the mean position that is held fixed, the
+        allowed-positions test and the cost are those of ALL ranks' positions:
+        every rank raises the reference's ValueError, or none, and every rank
+        returns the same cost.  `parameters.scan` is replaced only after the
+        test has passed.  `position_options` is neither needed nor touched."""
+        from .solvers.rpie import _positions_flag, _raise_unless_allowed
+        p, comm = self.parameters, self.comm
+        sums, _ = _pd_sums_device(self.operator, self.data, p.psi, p.probe,
+                                  p.scan, float(dx), p.eigen_probe,
+                                  p.eigen_weights)
+        grad = _pd_solve(sums)
+        count = torch.tensor([float(p.scan.shape[0])], dtype=torch.float64,
+                             device=p.scan.device)
+        totals = comm.Allreduce_f64(torch.cat([
+            p.scan.sum(0, dtype=torch.float64),
+            (p.scan.to(torch.float64) - step * grad.to(torch.float64)).sum(0),
+            count]))
+        moved = _pd_moved(p.scan, grad, step, totals[0:2], totals[2:4],
+                          totals[4])
+        _raise_unless_allowed(
+            float(_positions_flag(moved, p.psi, p.probe, comm)), moved, p.psi,
+            p.probe)
+        p.scan = moved
+        cost = comm.Allreduce_f64(torch.cat([
+            _pd_cost_sum(self.operator, self.data, p.psi, p.probe, moved,
+                         p.eigen_probe, p.eigen_weights).reshape(1), count]))
+        return float((cost[0] / cost[1]).item())
 
     def _apply_position_constraints(self):
         """Affine regularisation of the updated positions (ptycho.py:521-524,
