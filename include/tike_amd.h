@@ -38,7 +38,7 @@ extern "C" {
  * A binding compares tike_abi_version() of the loaded library with the
  * TIKE_ABI_VERSION it was written against before its first call
  * (tike_amd/_lib.py does; INTEGRATION.md shows the check). */
-#define TIKE_ABI_VERSION 16
+#define TIKE_ABI_VERSION 17
 
 /* sha256 (64 hex digits) of the sources the library was built from: the PMC
  * traffic files under profiles/ carry it, and bench.py withholds a traffic
@@ -1118,6 +1118,37 @@ int tike_lstsq_chunk_gradients_positions(
 int tike_position_pd_sums(const void* far0, const void* far_dx, const void* far_dy,
                           const void* data, int data_u16, float inv_dx, float* sums,
                           float* costs, long nscan, int S, long npix, void* stream);
+
+/* ---- fly scans: `fly` consecutive scan positions expose one detector frame
+ * (ptycho/ptycho.py:95-125, :128-179; operators/cupy/ptycho.py:104-125).
+ * Intensity, per-frame cost and far-plane gradient of a frame in one pass,
+ * shaped like tike_farplane_gradient.  farplane (nframe*fly,S,det,det) c64:
+ * frame f is exposed by positions f*fly .. f*fly+fly-1; data (nframe,det,det)
+ * f32, or uint16 when data_u16 != 0; measured (det,det) uint8 mask or NULL (all
+ * measured), num_measured its non-zero pixels.  Per pixel
+ *   I_f = sum_{j<fly} sum_{m<S} |farplane[f*fly+j][m]|^2
+ * intensity (nframe,det,det) = I and costs (nframe) = mean over the measured
+ * pixels of (sqrt(I) - sqrt(d))^2 (model 0, objective.py:11-15) or
+ * I - d log(I + 1e-9) (model 1, objective.py:72-74) are optional outputs (NULL
+ * to skip).  With apply_gradient every plane of the frame is overwritten by
+ *   -grad on measured pixels, (unmeasured_scaling-1)*farplane elsewhere,
+ * grad = farplane * (1 - sqrt(d)/(sqrt(I)+1e-9)) (objective.py:31-44) or
+ * farplane * (1 - d/(I+1e-9)) (objective.py:90-104), data and intensity
+ * broadcast over the positions and modes of the frame; without it the far
+ * plane is read once and never written.  Unmeasured counts (possibly NaN)
+ * are selected away by the mask.  One workgroup per frame, the cost summed in
+ * float64 in a fixed order, no atomics: two calls give the same bits.  With
+ * apply_gradient and fly*S <= 16 the planes stay in registers (one read, one
+ * write of the far plane); above, they are read a second time.  With fly == 1
+ * the results are those of tike_farplane_gradient.  No allocation.
+ * TIKE_ERR_ARG for NULL farplane or data, fly < 1, S < 1, det < 1, a model
+ * other than 0 / 1 or num_measured < 1; nframe == 0 returns 0 without a
+ * launch. */
+int tike_fly_farplane_gradient(void* farplane, const void* data, int data_u16,
+                               const unsigned char* measured, float* intensity, float* costs,
+                               int nframe, int fly, int S, int det, int model,
+                               int apply_gradient, float unmeasured_scaling, long num_measured,
+                               void* stream);
 
 /* ---- collectives: the per-minibatch gradient all-reduce over RCCL / xGMI,
  * one process (or thread) per GPU.  Replaces the serial peer-copy reduction of

@@ -1,0 +1,238 @@
+// Fly scans: `fly` consecutive scan positions expose one detector frame
+// (reference ptycho/ptycho.py:95-125 and :128-179; operators/cupy/ptycho.py:
+// 104-125).  Intensity, per-frame cost and the far-plane gradient factor of a
+// frame in ONE pass over its fly * S far planes:
+//   I_f = sum_{j < fly} sum_{m < S} |far[f * fly + j, m]|^2
+//   gaussian: cost terms (sqrt(I) - sqrt(d))^2, factor 1 - sqrt(d) / (sqrt(I) + 1e-9)
+//             (operators/cupy/objective.py:11-15, :31-44)
+//   poisson:  cost terms I - d log(I + 1e-9),   factor 1 - d / (I + 1e-9)
+//             (objective.py:72-74, :90-104)
+// with the frame's counts and intensity broadcast over j and m.
+//
+// Byte model per frame, P = fly * S planes of npix pixels: P * npix * 8 bytes of
+// far plane read once (and written once with apply_gradient), npix * 4 (or * 2)
+// bytes of counts, npix bytes of mask when there is one.
+#include "../../include/tike_amd.h"
+#include "common.h"
+
+namespace {
+
+// 16-byte accesses whose ADDRESS is only as aligned as an element (a plane
+// starts at a multiple of npix elements): see position_pd.hip.
+typedef float fly_f4 __attribute__((ext_vector_type(4), aligned(8)));  // two cf
+typedef float fly_d4 __attribute__((ext_vector_type(4), aligned(4)));  // four counts
+typedef unsigned short fly_h4 __attribute__((ext_vector_type(4), aligned(2)));
+typedef unsigned char fly_m4 __attribute__((ext_vector_type(4), aligned(1)));
+
+constexpr int FLY_PX = 4;  // pixels of a lane per sweep: two 16-byte far-plane loads
+
+// One pixel whose intensity is complete: its cost term into `cost` (measured
+// pixels only) and the factor the far plane is multiplied by, -(gradient
+// factor) on measured pixels and unmeasured_scaling - 1 elsewhere.  The count
+// of an unmeasured pixel may be NaN: selected away, never multiplied.
+template <int MODEL>
+__device__ __forceinline__ float fly_pixel(float I, float d, bool measured, float ums1,
+                                           double& cost) {
+  float term, g;
+  if (MODEL == 0) {
+    const float sI = sqrtf(I), sd = sqrtf(d);
+    const float diff = sI - sd;
+    term = diff * diff;
+    g = -(1.0f - sd / (sI + 1e-9f));
+  } else {
+    term = I - d * logf(I + 1e-9f);
+    g = -(1.0f - d / (I + 1e-9f));
+  }
+  cost += measured ? (double)term : 0.0;
+  return measured ? g : ums1;
+}
+
+__device__ __forceinline__ double fly_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// One workgroup per frame; a lane owns FLY_PX consecutive pixels per sweep.
+// R > 0 (with GRAD, P <= R): the P planes of those pixels stay in registers
+// between the intensity sum and the scaling -- the far plane is read from
+// memory once.  R == 0: the planes are read a second time for the scaling; the
+// second read follows the first within one sweep of the workgroup
+// (256 lanes * 4 pixels * 8 bytes * P).  The last npix % FLY_PX pixels are
+// taken one per lane.  The frame's cost is summed in float64 in a fixed order:
+// lane, wave shuffles, the four waves through LDS.
+template <int MODEL, bool GRAD, bool U16, int R>
+__global__ __launch_bounds__(256) void fly_farplane_gradient_kernel(
+    cf* __restrict__ farplane, const void* __restrict__ data_,
+    const unsigned char* __restrict__ mask, float* __restrict__ intensity,
+    float* __restrict__ costs, int P, long npix, float ums1, double inv_nmeasured) {
+  constexpr int PX = FLY_PX;
+  constexpr int RR = R > 0 ? R : 1;
+  __shared__ double red[4];
+  const long n = blockIdx.x;
+  cf* __restrict__ F = farplane + n * P * npix;
+  const float* __restrict__ d32 = U16 ? nullptr : (const float*)data_ + n * npix;
+  const unsigned short* __restrict__ d16 =
+      U16 ? (const unsigned short*)data_ + n * npix : nullptr;
+  double cost = 0.;
+  const long nvec = npix / PX;
+  for (long v = threadIdx.x; v < nvec; v += blockDim.x) {
+    const long p = v * PX;
+    // the counts and the mask are requested with the planes, not behind them
+    float d[PX];
+    if (U16) {
+      const fly_h4 c = *reinterpret_cast<const fly_h4*>(d16 + p);
+#pragma unroll
+      for (int k = 0; k < PX; ++k) d[k] = (float)c[k];
+    } else {
+      const fly_d4 c = *reinterpret_cast<const fly_d4*>(d32 + p);
+#pragma unroll
+      for (int k = 0; k < PX; ++k) d[k] = c[k];
+    }
+    bool measured[PX] = {true, true, true, true};
+    if (mask != nullptr) {
+      const fly_m4 m = *reinterpret_cast<const fly_m4*>(mask + p);
+#pragma unroll
+      for (int k = 0; k < PX; ++k) measured[k] = m[k] != 0;
+    }
+    float I[PX] = {0.f, 0.f, 0.f, 0.f};
+    fly_f4 r[RR][2];
+    if (GRAD && R > 0) {
+#pragma unroll
+      for (int j = 0; j < RR; ++j) {
+        if (j < P) {
+          const cf* at = F + j * npix + p;
+          r[j][0] = *reinterpret_cast<const fly_f4*>(at);
+          r[j][1] = *reinterpret_cast<const fly_f4*>(at + 2);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < RR; ++j) {
+        if (j < P) {
+          I[0] += r[j][0].x * r[j][0].x + r[j][0].y * r[j][0].y;
+          I[1] += r[j][0].z * r[j][0].z + r[j][0].w * r[j][0].w;
+          I[2] += r[j][1].x * r[j][1].x + r[j][1].y * r[j][1].y;
+          I[3] += r[j][1].z * r[j][1].z + r[j][1].w * r[j][1].w;
+        }
+      }
+    } else {
+      for (int j = 0; j < P; ++j) {
+        const cf* at = F + j * npix + p;
+        const fly_f4 a = *reinterpret_cast<const fly_f4*>(at);
+        const fly_f4 b = *reinterpret_cast<const fly_f4*>(at + 2);
+        I[0] += a.x * a.x + a.y * a.y;
+        I[1] += a.z * a.z + a.w * a.w;
+        I[2] += b.x * b.x + b.y * b.y;
+        I[3] += b.z * b.z + b.w * b.w;
+      }
+    }
+    float g[PX];
+#pragma unroll
+    for (int k = 0; k < PX; ++k) g[k] = fly_pixel<MODEL>(I[k], d[k], measured[k], ums1, cost);
+    if (intensity != nullptr) {
+      fly_d4 o;
+#pragma unroll
+      for (int k = 0; k < PX; ++k) o[k] = I[k];
+      *reinterpret_cast<fly_d4*>(intensity + n * npix + p) = o;
+    }
+    if (GRAD && R > 0) {
+#pragma unroll
+      for (int j = 0; j < RR; ++j) {
+        if (j < P) {
+          cf* at = F + j * npix + p;
+          fly_f4 a = r[j][0], b = r[j][1];
+          a.x *= g[0], a.y *= g[0], a.z *= g[1], a.w *= g[1];
+          b.x *= g[2], b.y *= g[2], b.z *= g[3], b.w *= g[3];
+          *reinterpret_cast<fly_f4*>(at) = a;
+          *reinterpret_cast<fly_f4*>(at + 2) = b;
+        }
+      }
+    } else if (GRAD) {
+      for (int j = 0; j < P; ++j) {
+        cf* at = F + j * npix + p;
+        fly_f4 a = *reinterpret_cast<const fly_f4*>(at);
+        fly_f4 b = *reinterpret_cast<const fly_f4*>(at + 2);
+        a.x *= g[0], a.y *= g[0], a.z *= g[1], a.w *= g[1];
+        b.x *= g[2], b.y *= g[2], b.z *= g[3], b.w *= g[3];
+        *reinterpret_cast<fly_f4*>(at) = a;
+        *reinterpret_cast<fly_f4*>(at + 2) = b;
+      }
+    }
+  }
+  // scalar tail: fewer than FLY_PX pixels, one per lane
+  for (long p = nvec * PX + threadIdx.x; p < npix; p += blockDim.x) {
+    const float dv = U16 ? (float)d16[p] : d32[p];
+    const bool measured = mask != nullptr ? mask[p] != 0 : true;
+    float I = 0.f;
+    for (int j = 0; j < P; ++j) I += norm2(F[j * npix + p]);
+    const float g = fly_pixel<MODEL>(I, dv, measured, ums1, cost);
+    if (intensity != nullptr) intensity[n * npix + p] = I;
+    if (GRAD)
+      for (int j = 0; j < P; ++j) F[j * npix + p] = F[j * npix + p] * g;
+  }
+  if (costs != nullptr) {
+    cost = fly_wave_sum(cost);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cost;
+    __syncthreads();
+    if (threadIdx.x == 0)
+      costs[n] = (float)(((red[0] + red[1]) + (red[2] + red[3])) * inv_nmeasured);
+  }
+}
+
+template <int MODEL, bool U16>
+void fly_launch(cf* far, const void* data, const unsigned char* measured, float* intensity,
+                float* costs, int nframe, int P, long npix, int apply_gradient, float ums1,
+                double inv, hipStream_t stream) {
+  const dim3 grid((unsigned)nframe), block(256);
+#define TK_FLY(G, R)                                                                        \
+  hipLaunchKernelGGL((fly_farplane_gradient_kernel<MODEL, G, U16, R>), grid, block, 0, stream, \
+                     far, data, measured, intensity, costs, P, npix, ums1, inv)
+  if (!apply_gradient)
+    TK_FLY(false, 0);
+  else if (P <= 4)
+    TK_FLY(true, 4);
+  else if (P <= 8)
+    TK_FLY(true, 8);
+  else if (P <= 16)
+    TK_FLY(true, 16);
+  else
+    TK_FLY(true, 0);
+#undef TK_FLY
+}
+
+}  // namespace
+
+extern "C" int tike_fly_farplane_gradient(void* farplane, const void* data, int data_u16,
+                                          const unsigned char* measured, float* intensity,
+                                          float* costs, int nframe, int fly, int S, int det,
+                                          int model, int apply_gradient,
+                                          float unmeasured_scaling, long num_measured,
+                                          void* stream_) {
+  TK_ENTER();
+  hipStream_t stream = (hipStream_t)stream_;
+  TK_CHECK_ARG(farplane && data);
+  TK_CHECK_ARG(nframe >= 0 && fly >= 1 && S >= 1 && det >= 1);
+  TK_CHECK_ARG(model == 0 || model == 1);
+  TK_CHECK_ARG(num_measured > 0);
+  TK_CHECK_ARG((long)fly * S <= 0x7fffffffL);
+  if (nframe == 0) return TK_OK;
+  const int P = fly * S;
+  const long npix = (long)det * det;
+  const double inv = 1.0 / (double)num_measured;
+  const float ums1 = unmeasured_scaling - 1.0f;
+  cf* far = (cf*)farplane;
+  if (model == 0 && data_u16)
+    fly_launch<0, true>(far, data, measured, intensity, costs, nframe, P, npix, apply_gradient,
+                        ums1, inv, stream);
+  else if (model == 0)
+    fly_launch<0, false>(far, data, measured, intensity, costs, nframe, P, npix, apply_gradient,
+                         ums1, inv, stream);
+  else if (data_u16)
+    fly_launch<1, true>(far, data, measured, intensity, costs, nframe, P, npix, apply_gradient,
+                        ums1, inv, stream);
+  else
+    fly_launch<1, false>(far, data, measured, intensity, costs, nframe, P, npix, apply_gradient,
+                         ums1, inv, stream);
+  TK_LAUNCH_CHECK();
+  return TK_OK;
+}

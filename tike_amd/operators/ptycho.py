@@ -245,13 +245,52 @@ class Ptycho(Operator):
                                     A.stream_ptr()), "Ptycho.adj (probe)")
         return A.like_input(psi_adj, kind), A.like_input(probe_adj, kind)
 
-    def _compute_intensity(self, data, psi, scan, probe):
-        """(intensity (N,det,det), farplane) -- ptycho.py:178-191."""
+    def fly_farplane_gradient(self, farplane, data, fly, *, model=0,
+                              measured=None, num_measured=None,
+                              intensity=None, costs=None, apply_gradient=False,
+                              unmeasured_scaling=1.0):
+        """`tike_fly_farplane_gradient` on device tensors: farplane
+        (FRAME * fly, 1, SHARED, det, det) complex64, frame f exposed by the
+        positions f * fly ... f * fly + fly - 1; data (FRAME, det, det) float32
+        or uint16; measured a (det, det) uint8 mask or None; intensity
+        (FRAME, det, det) and costs (FRAME) float32 outputs or None.  With
+        apply_gradient farplane becomes -gradient on the measured pixels."""
+        det = self.detector_shape
+        S = farplane.shape[-3]
+        nframe = data.shape[0]
+        assert farplane.shape[0] == nframe * fly, (farplane.shape, nframe, fly)
+        assert tuple(data.shape[1:]) == (det, det), data.shape
+        assert data.dtype in (torch.float32, torch.uint16), data.dtype
+        check(
+            lib.tike_fly_farplane_gradient(
+                A.ptr(farplane), A.ptr(data), int(data.dtype == torch.uint16),
+                A.ptr(measured), A.ptr(intensity), A.ptr(costs), nframe,
+                int(fly), S, det, int(model), int(bool(apply_gradient)),
+                float(unmeasured_scaling),
+                det * det if num_measured is None else int(num_measured),
+                A.stream_ptr()), "Ptycho.fly_farplane_gradient")
+        return farplane
+
+    def _compute_intensity(self, data, psi, scan, probe, fly=1):
+        """(intensity (FRAME,det,det), farplane) -- ptycho.py:178-191; with
+        fly > 1 a frame is the sum over `fly` consecutive positions
+        (ptycho.py:104-125)."""
         kind = psi
         far = self.fwd_device(A.to_device(probe, np.complex64),
                               A.to_device(scan, np.float32),
                               A.to_device(psi, np.complex64))
         N, _, S, det, _ = far.shape
+        if fly > 1:
+            if N % fly:
+                raise ValueError(
+                    f"{N} scan positions are not a multiple of fly={fly}")
+            intensity = torch.empty((N // fly, det, det), dtype=torch.float32,
+                                    device=far.device)
+            # (the counts are read by the cost and the gradient only: any
+            # array of the frames' shape serves)
+            self.fly_farplane_gradient(far, torch.zeros_like(intensity), fly,
+                                       intensity=intensity)
+            return A.like_input(intensity, kind), A.like_input(far, kind)
         intensity = torch.empty((N, det, det), dtype=torch.float32,
                                 device=far.device)
         check(
@@ -259,7 +298,28 @@ class Ptycho(Operator):
                                A.stream_ptr()), "Ptycho._compute_intensity")
         return A.like_input(intensity, kind), A.like_input(far, kind)
 
-    def cost(self, data, psi, scan, probe, *, model):
-        """ptycho.py:193-204."""
+    def cost(self, data, psi, scan, probe, *, model, fly=1):
+        """ptycho.py:193-204; with fly > 1 the mean over frames of the cost
+        of each frame's summed intensity."""
+        if fly > 1:
+            if model not in objective._MODELS:
+                raise ValueError(f"unknown noise model {model!r}")
+            kind = psi
+            far = self.fwd_device(A.to_device(probe, np.complex64),
+                                  A.to_device(scan, np.float32),
+                                  A.to_device(psi, np.complex64))
+            counts = A.to_device(data)
+            if counts.dtype not in (torch.float32, torch.uint16):
+                counts = counts.to(torch.float32)
+            if counts.shape[0] * fly != far.shape[0]:
+                raise ValueError(
+                    f"{counts.shape[0]} frames of fly={fly} do not match "
+                    f"{far.shape[0]} scan positions")
+            costs = torch.empty(counts.shape[0], dtype=torch.float32,
+                                device=far.device)
+            self.fly_farplane_gradient(far, counts.contiguous(), fly,
+                                       model=objective._MODELS[model],
+                                       costs=costs)
+            return A.like_input(costs.mean(), kind)
         intensity, _ = self._compute_intensity(data, psi, scan, probe)
         return getattr(objective, model)(data, intensity)

@@ -42,6 +42,7 @@ from .probe import (apply_median_filter_abs_probe, constrain_center_peak,
                     finite_probe_support, get_varying_probe, orthogonalize_eig,
                     power as probe_power,
                     rescale_probe_using_fixed_intensity_photons)
+from .solvers.cgrad import _refuse_fly
 from .solvers.lstsq import chunk_positions, mask_info
 from .._lib import check, lib
 
@@ -49,12 +50,18 @@ logger = logging.getLogger(__name__)
 
 
 def _intensity_chunks(operator, psi, scan, probe, eigen_probe=None,
-                      eigen_weights=None):
-    """Yield (lo, hi, intensity (n, det, det)) over chunks of positions."""
+                      eigen_weights=None, fly=1):
+    """Yield (lo, hi, intensity (n, det, det)) over chunks of frames; frame f
+    is the sum over the positions f * fly ... f * fly + fly - 1."""
     N = scan.shape[0]
     S = probe.shape[-3]
     det = operator.detector_shape
     chunk = chunk_positions(S, det)
+    if fly > 1:
+        if N % fly:
+            raise ValueError(
+                f"{N} scan positions are not a multiple of fly={fly}")
+        chunk = max(1, chunk // fly) * fly  # whole frames
     for lo in range(0, N, chunk):
         hi = min(N, lo + chunk)
         w = None if eigen_weights is None else eigen_weights[lo:hi]
@@ -63,12 +70,17 @@ def _intensity_chunks(operator, psi, scan, probe, eigen_probe=None,
                                scan=scan[lo:hi], psi=psi).contiguous()
         else:
             far = operator.fwd_device(probe, scan[lo:hi], psi, eigen_probe, w)
-        inten = torch.empty((hi - lo, det, det), dtype=torch.float32,
+        inten = torch.empty(((hi - lo) // fly, det, det), dtype=torch.float32,
                             device=psi.device)
-        check(
-            lib.tike_intensity(A.ptr(far), A.ptr(inten), hi - lo, S,
-                               det * det, A.stream_ptr()), "intensity")
-        yield lo, hi, inten
+        if fly > 1:
+            # (the counts are read by the cost and the gradient only)
+            operator.fly_farplane_gradient(far, torch.zeros_like(inten), fly,
+                                           intensity=inten)
+        else:
+            check(
+                lib.tike_intensity(A.ptr(far), A.ptr(inten), hi - lo, S,
+                                   det * det, A.stream_ptr()), "intensity")
+        yield lo // fly, hi // fly, inten
 
 
 def simulate(detector_shape, probe, scan, psi, fly=1, eigen_probe=None,
@@ -76,28 +88,22 @@ def simulate(detector_shape, probe, scan, psi, fly=1, eigen_probe=None,
     """Real-valued detector counts of simulated ptychography data
     (ptycho.py:128-179).  Returns (FRAME, det, det) float32 on the host."""
     check_allowed_positions(scan, psi, probe.shape)
-    det = int(detector_shape)
-    with Ptycho(det, probe.shape[-1], nz=psi.shape[-2], n=psi.shape[-1],
-                **kwargs) as operator:
-
-        def on_device(array, dtype):
-            return None if array is None else operator.asarray(array,
-                                                               dtype=dtype)
-
-        real, cplx = precision.floating, precision.cfloating
-        frames = [
-            inten for _, _, inten in _intensity_chunks(
-                operator, on_device(psi, cplx), on_device(scan, real),
-                on_device(probe, cplx), on_device(eigen_probe, cplx),
-                on_device(eigen_weights, real))
-        ]
-        counts = torch.cat(frames)
-        if fly > 1:  # `fly` consecutive positions expose one frame
-            counts = counts.reshape(-1, fly, det, det).sum(dim=1)
-        return operator.asnumpy(counts)
+    real, cplx = precision.floating, precision.cfloating
+    wanted = ((psi, cplx), (scan, real), (probe, cplx), (eigen_probe, cplx),
+              (eigen_weights, real))
+    with Ptycho(int(detector_shape), probe.shape[-1], nz=psi.shape[-2],
+                n=psi.shape[-1], **kwargs) as operator:
+        resident = [None if a is None else operator.asarray(a, dtype=t)
+                    for a, t in wanted]
+        # (`fly` consecutive positions expose one frame: summed by the kernel)
+        frames = torch.cat([
+            inten for _, _, inten in _intensity_chunks(operator, *resident,
+                                                       fly=int(fly))])
+        return operator.asnumpy(frames)
 
 
-def reconstruct(data, parameters, num_gpu=None, use_mpi=False, **kwargs):
+def reconstruct(data, parameters, num_gpu=None, use_mpi=False, *, fly=1,
+                **kwargs):
     """Solve the ptychography problem (ptycho.py:182-262).
 
     data (FRAME, WIDE, HIGH): measured intensities, FFT-shifted so that the
@@ -111,17 +117,30 @@ def reconstruct(data, parameters, num_gpu=None, use_mpi=False, **kwargs):
     process starts N child processes (one rank per GPU, RCCL) that shard the
     positions, and returns their result; a value that contradicts a running
     process group raises ValueError (`_spawn.resolve`).
+
+    fly (keyword only): scan positions per diffraction pattern.  With fly > 1
+    `data` holds one frame per `fly` consecutive rows of `parameters.scan`
+    (what `simulate(..., fly=fly)` produces); cgrad alone reconstructs such
+    data (see `Reconstruction`).
     """
     if use_mpi:
         raise NotImplementedError(
             "multi-node MPI is out of scope; launch one process per GPU "
             "with torchrun instead")
+    fly = _checked_fly(fly)
+    requested = _spawn.requested_devices(num_gpu)
+    if (fly > 1 and requested is not None and len(requested) > 1
+            and _spawn.world_size() == 1):
+        raise NotImplementedError(
+            f"fly={fly} with reconstruct(num_gpu={num_gpu!r}) from a plain "
+            "process: the ranks this call would start do not take fly-scan "
+            "data; launch one process per GPU with torchrun instead")
     how, where = _spawn.resolve(num_gpu)
     if how == "spawn":
         return _spawn.reconstruct_spawned(data, parameters, where, **kwargs)
     with Reconstruction(data, parameters,
                         num_gpu if where is None else (where,),
-                        use_mpi, **kwargs) as context:
+                        use_mpi, fly=fly, **kwargs) as context:
         context.iterate(parameters.algorithm_options.num_iter)
         result = context.get_result()
     return result
@@ -181,9 +200,78 @@ def _warn_invalid_data():
         "All data should be non-negative and finite.", UserWarning)
 
 
-def _check_data_shape(data, parameters):
+def _checked_fly(fly):
+    """`fly` as an int >= 1."""
+    if isinstance(fly, bool) or int(fly) != fly or int(fly) < 1:
+        raise ValueError(f"fly={fly!r}: expected an integer >= 1, the number "
+                         "of scan positions per diffraction pattern")
+    return int(fly)
+
+
+def _check_fly_supported(parameters, fly):
+    """A fly-scan reconstruction is cgrad's, with a shared probe, one slice
+    and fixed positions: everything else is refused by name."""
+    if fly <= 1:
+        return
+    name = parameters.algorithm_options.name
+    if name != "cgrad":
+        raise NotImplementedError(
+            f"fly={fly} with {name}: fly-scan data (several scan positions "
+            "per diffraction pattern) is reconstructed by cgrad only")
+    _refuse_fly(parameters, fly)
+
+
+def frame_centroids(scan_host, fly):
+    """Mean of the `fly` consecutive positions that expose every frame."""
+    scan_host = np.asarray(scan_host)
+    return scan_host.reshape(-1, fly, scan_host.shape[-1]).mean(axis=1)
+
+
+def expand_frames(frame_order, frame_batches, fly):
+    """Frame order and frame minibatches -> position order and position
+    minibatches: frame f stands for the positions f * fly + j, j ascending,
+    so a frame's positions stay consecutive and in acquisition order; the
+    batches are the frame batches scaled by `fly`."""
+    frame_order = np.asarray(frame_order, dtype=np.int64)
+    order = (frame_order[:, None] * fly
+             + np.arange(fly, dtype=np.int64)[None, :]).reshape(-1)
+    batches, start = [], 0
+    for b in frame_batches:
+        batches.append(np.arange(start * fly, (start + len(b)) * fly))
+        start += len(b)
+    return order, batches
+
+
+def collapse_to_frames(order, batches, fly):
+    """The inverse of `expand_frames` for an injected position order and its
+    batches; ValueError when they do not have that structure."""
+    order = np.asarray(order)
+    if len(order) % fly:
+        raise ValueError(
+            f"`order` lists {len(order)} positions, not a multiple of "
+            f"fly={fly}")
+    rows = order.reshape(-1, fly)
+    if not np.array_equal(
+            rows, rows[:, :1] + np.arange(fly)[None, :]) or np.any(
+                rows[:, 0] % fly):
+        raise ValueError(
+            f"with fly={fly}, `order` must list the positions of every frame "
+            "consecutively and ascending (f * fly, ..., f * fly + fly - 1)")
+    frame_batches, start = [], 0
+    for b in batches:
+        if len(b) % fly:
+            raise ValueError(
+                f"with fly={fly}, every batch must hold whole frames: a "
+                f"batch of {len(b)} positions is not a multiple of {fly}")
+        frame_batches.append(np.arange(start // fly, (start + len(b)) // fly))
+        start += len(b)
+    return rows[:, 0] // fly, frame_batches
+
+
+def _check_data_shape(data, parameters, fly=1):
     """The diffraction patterns against the forward model's shapes
-    (reference ptycho.py:303-331: same conditions, same messages)."""
+    (reference ptycho.py:303-331: same conditions, same messages; with
+    fly > 1 a pattern per `fly` scan positions)."""
     frames = tuple(int(n) for n in data.shape)
     window = tuple(int(n) for n in parameters.probe.shape[-2:])
     measured = parameters.exitwave_options.measured_pixels
@@ -199,7 +287,12 @@ def _check_data_shape(data, parameters):
          "where N >= 1 is the number of square diffraction patterns."),
         (frames[:1] == tuple(parameters.scan.shape[:1]),
          f"data shape {data.shape} and scan shape {parameters.scan.shape} "
-         "are incompatible. They should have the same leading dimension."),
+         "are incompatible. They should have the same leading dimension.")
+        if fly == 1 else
+        (len(frames) >= 1 and frames[0] * fly == int(parameters.scan.shape[0]),
+         f"data shape {data.shape}, scan shape {parameters.scan.shape} and "
+         f"fly={fly} are incompatible. The scan should hold fly positions "
+         "for every diffraction pattern."),
         (all(w <= d for w, d in zip(window, frames[-2:])),
          f"probe shape {parameters.probe.shape} "
          f"and data shape {data.shape} are incompatible. "
@@ -261,11 +354,21 @@ class Reconstruction():
         stream them to the GPU chunk by chunk (datasets larger than HBM; what
         the reference always does, communicators/stream.py:285-404) instead
         of holding them in HBM.  Results are identical.
+      fly: scan positions per diffraction pattern (default 1).  With fly > 1
+        pattern f is the incoherent sum of the scan rows f * fly ... f * fly +
+        fly - 1 (`simulate(..., fly=fly)`); frames are then the unit of
+        clustering, spatial sorting and rank sharing, `order` / `batches` list
+        positions with every frame's positions consecutive and ascending, and
+        the solver must be cgrad with a shared probe, one slice and no
+        position correction.
     """
+
+    fly = 1  # scan positions per diffraction pattern
 
     def __init__(self, data, parameters, num_gpu=None, use_mpi=False, *,
                  presharded=False, order=None, batches=None,
-                 spatial_sort=True, data_on_host=False, local_data=None):
+                 spatial_sort=True, data_on_host=False, local_data=None,
+                 fly=1):
         # a context lives in ONE process with ONE GPU: `num_gpu` must agree
         # with the process group it runs in (`reconstruct` is the entry that
         # starts ranks by itself)
@@ -280,7 +383,13 @@ class Reconstruction():
                 f"{len(_spawn.requested_devices(num_gpu))}`")
         if device is not None:
             torch.cuda.set_device(device)  # ptycho.py:344-345
-        _check_data_shape(data, parameters)
+        fly = self.fly = _checked_fly(fly)
+        _check_data_shape(data, parameters, fly)
+        _check_fly_supported(parameters, fly)
+        if fly > 1 and local_data is not None:
+            raise NotImplementedError(
+                f"fly={fly} with local_data (the ranks started by "
+                "reconstruct(num_gpu=N)) is not implemented")
         name = parameters.algorithm_options.name
         if not hasattr(solvers, name):
             raise NotImplementedError(
@@ -322,6 +431,7 @@ class Reconstruction():
                 parameters.object_options, "multislice_propagation_distance",
                 1e-9),
         )
+        self.operator.fly = fly  # (a rank without a frame reads it: cgrad)
         self.comm = Comm()
         self._pending_fits = []  # futures of deferred affine position fits
         self._free_snaps = []  # pinned host buffers of finished fits
@@ -331,16 +441,26 @@ class Reconstruction():
 
     # ------------------------------------------------------------- set-up
     def _shard(self, n_total):
-        """Global order and this rank's local order / batches."""
+        """Global order and this rank's local order / batches, of POSITIONS;
+        `self.local_frame_order`: the rows of `data` this rank holds, in its
+        local order (with fly == 1 the local order itself).  With fly > 1
+        everything is decided on frames -- clustering and spatial sorting on
+        the frame centroids, rank sharing on frame indices -- and expanded to
+        positions afterwards (`expand_frames`).  n_total: number of frames."""
         p = self._parameters_in
         o = p.algorithm_options
+        fly = self.fly
         scan_host = A.to_host(p.scan)
+        if fly > 1:
+            scan_host = frame_centroids(scan_host, fly)
         if (self._order_in is None) != (self._batches_in is None):
             raise ValueError("`order` and `batches` must be given together")
         if self._order_in is not None:
             order = np.asarray(self._order_in)
             batches = [np.asarray(b) for b in self._batches_in]
-            _check_batches(order, batches, n_total)
+            _check_batches(order, batches, n_total * fly)
+            if fly > 1:
+                order, batches = collapse_to_frames(order, batches, fly)
         else:
             order, batches = cluster.batches_contiguous(
                 scan_host, o.batch_method, o.num_batch)
@@ -352,14 +472,20 @@ class Reconstruction():
         # (concatenated batches): the RANSAC subsets of the affine position
         # fit are INDICES into it, and a fit whose rough 4-point models drop
         # some positions depends on which positions an index names
-        self.cluster_order = np.array(order, copy=True)
+        self.cluster_order = (np.array(order, copy=True) if fly == 1 else
+                              expand_frames(order, batches, fly)[0])
         if self._spatial_sort:
             order = spatially_sorted(scan_host, order, batches)
         if self._presharded or self.comm.size == 1:
-            return order, order, batches
-        local, local_batches = rank_share(order, batches, self.comm.size,
-                                          self.comm.rank)
-        return order, local, local_batches
+            local, local_batches = order, batches
+        else:
+            local, local_batches = rank_share(order, batches, self.comm.size,
+                                              self.comm.rank)
+        self.local_frame_order = local
+        if fly == 1:
+            return order, local, local_batches
+        return (expand_frames(order, batches, fly)[0],
+                *expand_frames(local, local_batches, fly))
 
     def __enter__(self):
         self.operator.__enter__()
@@ -385,14 +511,15 @@ class Reconstruction():
         # it arrived as <= 16-bit integers (ptycho.py:383-390)
         if self._data_on_host:
             from ..communicators.stream import PinnedData
-            rows = (A.to_host(data) if host is None else host)[self.local_order]
+            rows = (A.to_host(data) if host is None else host)[
+                self.local_frame_order]
             rows = (np.clip(rows, 0, None).astype(np.uint16)
                     if A.is_small_integer(rows.dtype) else
                     rows.astype(np.float32, copy=False))
             self.data = PinnedData(rows)
         else:
             self.data = A.data_to_device(data if A.is_device(data) else host,
-                                         order=self.local_order)
+                                         order=self.local_frame_order)
             if (host is not None and not on_host
                     and self.data.dtype == torch.float32
                     and A.has_invalid_counts(self.data)):
@@ -408,7 +535,8 @@ class Reconstruction():
         if (self.parameters.probe_options is not None and
                 self.parameters.probe_options.init_rescale_from_measurements):
             self.parameters = _rescale_probe(self.operator, self.comm,
-                                             self.data, self.parameters)
+                                             self.data, self.parameters,
+                                             fly=self.fly)
         return self
 
     def _enter_with_local_data(self):
@@ -421,10 +549,10 @@ class Reconstruction():
         if self._data_on_host:
             from ..communicators.stream import PinnedData
             self.data = PinnedData(np.asarray(self._local_data))
-        if self.data.shape[0] != len(self.local_order):
+        if self.data.shape[0] != len(self.local_frame_order):
             raise ValueError(
                 f"local_data holds {self.data.shape[0]} patterns, this rank's "
-                f"share is {len(self.local_order)}")
+                f"share is {len(self.local_frame_order)}")
         if (isinstance(self.data, torch.Tensor)
                 and self.data.dtype == torch.float32
                 and A.has_invalid_counts(self.data)):
@@ -485,6 +613,10 @@ class Reconstruction():
         returns the same cost.  `parameters.scan` is replaced only after the
         test has passed.  `position_options` is neither needed nor touched."""
         from .solvers.rpie import _positions_flag, _raise_unless_allowed
+        if self.fly > 1:
+            raise NotImplementedError(
+                f"fly={self.fly} with update_positions_pd: position "
+                "refinement of fly-scan data is not implemented")
         p, comm = self.parameters, self.comm
         sums, _ = _pd_sums_device(self.operator, self.data, p.psi, p.probe,
                                   p.scan, float(dx), p.eigen_probe,
@@ -743,14 +875,16 @@ def _apply_object_constraints(parameters):
     return parameters
 
 
-def _rescale_probe(operator, comm, data, parameters):
+def _rescale_probe(operator, comm, data, parameters, fly=1):
     """probe *= sqrt(sum(data) / sum(intensity)) over measured pixels and all
-    ranks (ptycho.py:873-972)."""
+    ranks (ptycho.py:873-972); with fly > 1 the intensity of a frame is the
+    sum over its positions and `data` is read by frame range."""
     nmeasured, mask_u8 = mask_info(parameters.exitwave_options,
                                    operator.detector_shape)
     sums = torch.zeros(2, dtype=torch.float64, device=parameters.psi.device)
     for lo, hi, inten in _intensity_chunks(operator, parameters.psi,
-                                           parameters.scan, parameters.probe):
+                                           parameters.scan, parameters.probe,
+                                           fly=fly):
         d = A.data_f32(data, lo, hi)
         if mask_u8 is not None:
             m = mask_u8.bool()

@@ -20,6 +20,13 @@ the last minibatch one ``lstsq._update_position`` with ``alpha`` of the
 algorithm options, the allowed-positions test of rpie, and only then the new
 ``parameters.scan``.  The sums need the object projection alone, which the
 gradient pass of the object writes anyway (``_PositionTerms``).
+
+Fly scans (``data`` holds one frame per ``fly`` consecutive positions,
+reference ptycho.py:95-125): the same conjugate gradient on the mean over
+FRAMES of each frame's mean cost over its measured pixels, the intensity of a
+frame being the sum over its positions and modes (``_fly_cost_and_grad``:
+forward, ``tike_fly_farplane_gradient``, adjoint, chunk by chunk over whole
+frames, line searches decided on the host).
 """
 import logging
 
@@ -668,14 +675,195 @@ class _Evaluator:
         return [g]
 
 
+def _fly_of(op, data, scan):
+    """Positions per frame, from the arrays a rank holds (the caller has
+    validated divisibility); a rank without a frame takes the context's."""
+    if data.shape[0] == 0:
+        return int(getattr(op, "fly", 1))
+    return scan.shape[0] // data.shape[0]
+
+
+def _refuse_fly(parameters, fly):
+    """What a fly-scan reconstruction cannot be combined with."""
+    if fly <= 1:
+        return
+    if parameters.position_options is not None:
+        raise NotImplementedError(
+            f"fly={fly} with position_options: position correction of "
+            "fly-scan data is not implemented")
+    if (parameters.eigen_probe is not None
+            or parameters.eigen_weights is not None):
+        raise NotImplementedError(
+            f"fly={fly} with eigen probes: a varying probe per position of "
+            "fly-scan data is not implemented")
+    if parameters.psi.shape[0] > 1:
+        raise NotImplementedError(
+            f"fly={fly} with several slices (psi.shape[0] = "
+            f"{parameters.psi.shape[0]}): multislice fly-scan "
+            "reconstruction is not implemented")
+
+
+def _fly_adjoint(op, far, probe, scan, psi, want_psi, want_probe):
+    """Ptycho.adj of a chunk's far plane (a workspace: overwritten):
+    (psi_adj (1, H, W) or None, probe_adj summed over the positions
+    (1, 1, S, pw, pw) or None)."""
+    N, S = scan.shape[0], probe.shape[-3]
+    pw, det = op.probe_shape, op.detector_shape
+    H, W = psi.shape[-2:]
+    dev = psi.device
+    if op.fused_adjoint_shapes(S):
+        psi_adj, probe_adj = op.adj_device(far, probe, scan, psi)
+        return (psi_adj if want_psi else None,
+                probe_adj.sum(dim=0, keepdim=True) if want_probe else None)
+    st = A.stream_ptr()
+    chi = far if pw == det else torch.empty(
+        (N, 1, S, pw, pw), dtype=torch.complex64, device=dev)
+    check(
+        lib.tike_ifft2_crop(A.ptr(far), A.ptr(far), A.ptr(chi), N * S, det, pw,
+                            fft_scales(det, op.norm)[1], st),
+        "cgrad fly adjoint (ifft2)")
+    psi_adj = probe_adj = None
+    if want_psi:
+        psi_adj = torch.zeros_like(psi)
+        check(
+            lib.tike_conv_adj(A.ptr(chi), A.ptr(scan), A.ptr(probe), 0,
+                              A.ptr(psi_adj), N, S, pw, pw, H, W, st),
+            "cgrad fly adjoint (object)")
+    if want_probe:
+        each = torch.empty((N, 1, S, pw, pw), dtype=torch.complex64,
+                           device=dev)
+        check(
+            lib.tike_conv_adj_probe(A.ptr(chi), A.ptr(scan), A.ptr(psi),
+                                    A.ptr(each), N, S, pw, pw, H, W, st),
+            "cgrad fly adjoint (probe)")
+        probe_adj = each.sum(dim=0, keepdim=True)
+    return psi_adj, probe_adj
+
+
+def _fly_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, fly, *,
+                       want_psi, want_probe, want_grad, cm):
+    """(sum of this rank's per-frame costs, a device scalar; d cost / d psi or
+    None; d cost / d probe or None -- unnormalised adjoints summed over the
+    ranks) of the positions [lo, hi), whole frames: the data rows
+    [lo / fly, hi / fly).  Per chunk of whole frames: the forward operator,
+    `tike_fly_farplane_gradient` (costs only for a line-search probe: the far
+    plane is read once and not written) and, for a gradient, the adjoint of
+    the far plane it left."""
+    assert lo % fly == 0 and hi % fly == 0, (lo, hi, fly)
+    _, model, nmeasured, mask = cm
+    dev = psi.device
+    S, det = probe.shape[-3], op.detector_shape
+    N = hi - lo
+    ws = _workspace(op)
+    chunk = max(1, chunk_positions(S, det) // fly) * fly  # whole frames
+    far_all = ws.get("far", (min(chunk, max(N, 1)), 1, S, det, det),
+                     torch.complex64, dev)
+    costs = ws.get("costs", (max(N // fly, 1),), torch.float32, dev)[:N // fly]
+    n_obj = psi.numel() * 2 if want_grad and want_psi else 0
+    n_prb = probe.numel() * 2 if want_grad and want_probe else 0
+    grads = torch.zeros(n_obj + n_prb, dtype=torch.float32, device=dev)
+    gpsi = (torch.view_as_complex(grads[:n_obj].view(*psi.shape, 2))
+            if n_obj else None)
+    gprobe = (torch.view_as_complex(grads[n_obj:].view(*probe.shape, 2))
+              if n_prb else None)
+    for clo in range(lo, hi, chunk):
+        chi = min(hi, clo + chunk)
+        sc = scan[clo:chi]
+        far = far_all[:chi - clo]
+        op.fwd_device(probe, sc, psi, out=far)
+        d = data[clo // fly:chi // fly]
+        if d.dtype not in (torch.float32, torch.uint16):
+            d = d.to(torch.float32)
+        op.fly_farplane_gradient(
+            far, d, fly, model=model, measured=mask, num_measured=nmeasured,
+            costs=costs[(clo - lo) // fly:(chi - lo) // fly],
+            apply_gradient=want_grad)
+        if want_grad:
+            # the far plane now holds MINUS the gradient
+            a, b = _fly_adjoint(op, far, probe, sc, psi, want_psi, want_probe)
+            if gpsi is not None:
+                gpsi -= a
+            if gprobe is not None:
+                gprobe -= b
+    if comm.collective and grads.numel():
+        comm.Allreduce(grads)
+    return costs.sum(dtype=torch.float64), gpsi, gprobe
+
+
+def _fly_epoch(parameters, data, batches, comm, *, op, epoch, fly, cm):
+    """One cgrad epoch on fly-scan data: `opt.conjugate_gradient` with the
+    host-side line search for the object, then the probe, per minibatch."""
+    o = parameters.algorithm_options
+    recover_psi = parameters.object_options is not None
+    recover_probe = (parameters.probe_options is not None
+                     and epoch >= parameters.probe_options.update_start)
+    psi, probe, scan = parameters.psi, parameters.probe, parameters.scan
+    batch_cost = []
+    for batch_index, b in enumerate(batches):
+        lo = int(b[0]) if len(b) else 0
+        hi = lo + len(b)
+        if lo % fly or hi % fly:
+            raise ValueError(
+                f"minibatch [{lo}, {hi}) does not hold whole frames of "
+                f"fly={fly} positions")
+        comm.minibatch = batch_index
+        # the mean is over the FRAMES of all ranks
+        frames = global_count(comm, op, lo, hi) / fly
+
+        def finish(total):
+            if comm.collective:
+                total = comm.Allreduce_scalars([total], total.device)[0]
+            return float(total.item()) / frames
+
+        def run_for(variable):
+            def run(x, want_grad):
+                r = _fly_cost_and_grad(
+                    op, comm, data, x if variable == 0 else psi, scan,
+                    probe if variable == 0 else x, lo, hi, fly,
+                    want_psi=variable == 0, want_probe=variable == 1,
+                    want_grad=want_grad, cm=cm)
+                return r[0], r[1 + variable]
+            return run
+
+        cost = None
+        if recover_psi:
+            ev = _Evaluator(run_for(0), finish)
+            psi, cost = opt.conjugate_gradient(
+                torch, x=psi, cost_function=ev.cost, grad=ev.grad,
+                dir_multi=lambda x: x[0], num_iter=o.cg_iter,
+                step_length=o.step_length)
+        if recover_probe:
+            ev = _Evaluator(run_for(1), finish)
+            probe, cost = opt.conjugate_gradient(
+                torch, x=probe, cost_function=ev.cost, grad=ev.grad,
+                dir_multi=lambda x: x[0], num_iter=o.cg_iter,
+                step_length=o.step_length)
+        if cost is None:
+            cost = finish(_fly_cost_and_grad(
+                op, comm, data, psi, scan, probe, lo, hi, fly, want_psi=False,
+                want_probe=False, want_grad=False, cm=cm)[0])
+        batch_cost.append(cost)
+    o.costs.append([float(np.mean(batch_cost))])
+    parameters.psi, parameters.probe = psi, probe
+    return parameters
+
+
 def cgrad(parameters, data, batches, comm, *, op, epoch):
     """One epoch: for every minibatch, `cg_iter` CG iterations on psi and
     then (when probe recovery is on) on the probe; with position_options, one
     position update after the last minibatch (every minibatch of the epoch
     saw the old positions, as in lstsq_grad and rpie)."""
     o = parameters.algorithm_options
+    fly = _fly_of(op, data, parameters.scan)
+    _refuse_fly(parameters, fly)
     if parameters.eigen_probe is not None or parameters.eigen_weights is not None:
         raise NotImplementedError("cgrad does not support eigen probes")
+    if fly > 1:
+        # the device line searches, _CostPlan's fused routes and graph capture
+        # form the intensity per position: not taken
+        return _fly_epoch(
+            parameters, data, batches, comm, op=op, epoch=epoch, fly=fly,
+            cm=_cost_model(parameters.exitwave_options, op.detector_shape))
     recover_psi = parameters.object_options is not None
     recover_probe = (parameters.probe_options is not None
                      and epoch >= parameters.probe_options.update_start)
