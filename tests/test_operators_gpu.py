@@ -4,6 +4,7 @@ fixtures, and the reference's own known-answer / adjoint-identity tests."""
 import numpy as np
 import pytest
 
+import lstsq_tail as lt
 from util import assert_close, relerr, COST_RTOL
 
 pytestmark = pytest.mark.gpu
@@ -1299,13 +1300,8 @@ def test_step_statistics_on_pairs_vs_numpy(oracle, pw, N, eigen, border):
     Pn = w[:, 0, 0, None, None] * P0
     if eigen:
         Pn = Pn + w[:, 1, 0, None, None] * E[0, 0, 0]
-    dOP, dPO, OP = G * Pn, mpu[0, 0, 0] * O, O * P0
     tot = lambda a: a.reshape(N, -1).sum(axis=1)
-    a2 = tot(dOP * np.conj(dPO))
-    want = np.stack([tot(np.abs(dOP)**2), tot(np.abs(dPO)**2), a2.real, a2.imag,
-                     tot((np.conj(dOP) * chi0).real),
-                     tot((np.conj(dPO) * chi0).real),
-                     tot((np.conj(OP) * chi0).real), tot(np.abs(OP)**2)], 1)
+    want = lt.step_stats(G, O, chi0, P0, Pn, mpu[0, 0, 0])
     d = {k: A.to_device(v) for k, v in dict(
         psi=psi, gobj=gobj, probe=probe, mpu=mpu, chi0=chi0, scan=scan, O=O,
         w=w).items()}
@@ -1325,7 +1321,8 @@ def test_step_statistics_on_pairs_vs_numpy(oracle, pw, N, eigen, border):
     if eigen:
         R = np.conj(O) * chi0 - mpu[0, 0, 0]
         np.testing.assert_allclose(
-            eproj.cpu().numpy(), tot((np.conj(R) * E[0, 0, 0]).real),
+            eproj.cpu().numpy(), lt.eigen_proj(O, chi0, mpu[0, 0, 0],
+                                               E[0, 0, 0]),
             rtol=2e-4, atol=2e-5 * np.abs(tot(np.abs(R))).max())
 
 
@@ -1346,12 +1343,7 @@ def test_eigen_position_sums_on_pairs_vs_numpy(oracle, pw, N, border):
     psi = rc(rng, HW, HW)
     chi0, mpu, E = rc(rng, N, pw, pw), rc(rng, pw, pw), rc(rng, pw, pw)
     O = _patches(oracle, psi, scan, pw)
-    R = np.conj(O) * chi0 - mpu
-    phi = O * E
-    tot = lambda a: a.reshape(N, -1).sum(axis=1)
-    re = tot(R * np.conj(E))
-    want = np.stack([tot((np.conj(R) * E).real), tot((chi0 * np.conj(phi)).real),
-                     tot(np.abs(phi)**2), re.real, re.imag], 1)
+    want = lt.position_sums5(O, chi0, mpu, E)
     d = {k: A.to_device(v) for k, v in dict(psi=psi, chi0=chi0, mpu=mpu, E=E,
                                             scan=scan, O=O).items()}
     sums = torch.full((N, 5), np.nan, dtype=torch.float32, device="cuda")

@@ -77,13 +77,15 @@ def _epoch(tp, problem, det, num_batch, fused, monkeypatch):
     (256, 8, 21, 2),   # an odd minibatch: its last position takes the fallback
     (128, 8, 18, 2),
     (256, 4, 13, 1),
+    (128, 8, 300, 1),  # above 256 positions: a second round of every
+                       # one-workgroup loop over the minibatch
 ])
 def test_fused_tail_equals_staged_tail(tp, det, S, N, num_batch, monkeypatch):
     problem = _headline_problem(tp, det, S, N, seed=det + S + N)
     staged, n_staged = _epoch(tp, problem, det, num_batch, False, monkeypatch)
     fused, n_fused = _epoch(tp, problem, det, num_batch, True, monkeypatch)
     assert n_staged == 0 and n_fused in (0, num_batch)
-    if det == 256:  # the fused pass 2 of the c3 route
+    if det == 256 or N > 256:  # the fused pass 2 of the c3 route
         assert n_fused == num_batch
     np.testing.assert_allclose(np.array(fused.algorithm_options.costs),
                                np.array(staged.algorithm_options.costs),

@@ -197,7 +197,11 @@ extern "C" int tike_eigen_weights0(float* weights, const float* stats, int B, in
                                    int m, float* norms, void* stream) {
   TK_ENTER();
   TK_CHECK_ARG(B >= 0 && C >= 0 && S >= 1 && m >= 0 && m < S);
-  if (B == 0) return TK_OK;
+  if (B == 0) {  // an empty share: its sums are zero, and the caller all-reduces them
+    if (C > 0 && norms)
+      return (int)hipMemsetAsync(norms, 0, sizeof(float) * (size_t)C, (hipStream_t)stream);
+    return TK_OK;
+  }
   TK_CHECK_ARG(weights && stats && (C == 0 || norms));
   hipLaunchKernelGGL(eigen_weights0_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, weights,
                      stats, B, C, S, m, norms);
