@@ -228,7 +228,7 @@ __device__ __forceinline__ void fft2_rows_from_columns(cf* __restrict__ lds, con
   __syncthreads();
 }
 
-// ---- a whole 128 x 128 tile in LDS (fwd128_lds_kernel of ptycho.hip, the
+// ---- a whole 128 x 128 tile in LDS (fwd128_lds_kernel of forward.hip, the
 // prime-factor sub-tile kernel of pfa.hip)
 constexpr int TK_L128_LS = 136;
 // Column offset of row `row` inside the LDS tile (element (row, col) lives at

@@ -24,6 +24,29 @@ int tk_ifft2_pass2_products(cf* work, const cf* psi, const float* scan, const cf
                             cf* chi0, int out, int nscan, int S, int det, int H, int W,
                             float inv_scale, hipStream_t stream);
 
+// csrc/forward.hip: the 128^2 forward operator, whole tile in LDS (a launch with
+// *skip != 0 returns at once), and pass 1 of the 256^2 / 512^2 forward operator
+// alone, which leaves the column-pass input of every tile in `scratch`
+int launch_fwd128_lds(const cf* psi, const float* scan, const TkProbe& probe, cf* farplane,
+                      float* intensity, int nscan, int S, int H, int W, float scale,
+                      hipStream_t stream, cf* patches, const int* skip = nullptr);
+int tk_fwd_pass1(const void* psi, const float* scan, const void* probe, int probe_per_scan,
+                 const void* unique_probe, const void* eigen_probe, const float* eigen_weights,
+                 int num_eigen, int eigen_modes, void* scratch, void* patches, int nscan, int S,
+                 int pw, int det, int H, int W, hipStream_t stream, const int* skip,
+                 bool keep = false);
+// csrc/ptycho.hip: intensity, per-pattern cost and gradient factor from
+// that column-pass input, or from a stored far plane
+int tk_fwd_gradient_scale(const void* scratch, const void* data, int data_u16,
+                          const unsigned char* measured, float* gscale, float* intensity,
+                          float* costs, void* farplane, int nscan, int S, int det, float scale,
+                          int model, float unmeasured_scaling, long num_measured,
+                          hipStream_t stream, const int* skip);
+int tk_farplane_gradient(void* farplane, const float* data, const unsigned char* measured,
+                         float* intensity, float* costs, int nscan, int S, int det, int model,
+                         int apply_gradient, float unmeasured_scaling, long num_measured,
+                         hipStream_t stream, const int* skip);
+
 // ---- deterministic mode (tike_set_deterministic, fft2.hip).  Off: sums that
 // several workgroups contribute to are float atomics (the reference's scheme,
 // operators/cupy/convolution.cu:51-66): their order, and with it the last bits

@@ -5,7 +5,7 @@
 // :157-165, loop body :79-144), and the CuPy elementwise passes of
 // convolution.py:58-154.  These are the general-shape kernels behind the
 // Patch / Convolution operator API (any patch width, padding, nrepeat,
-// broadcast K); the solver's hot loop uses the fused kernels in ptycho.hip.
+// broadcast K); the solver's hot loop uses the fused kernels in forward.hip.
 #include "common.h"
 #include "tike_amd.h"
 

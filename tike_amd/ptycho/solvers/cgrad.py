@@ -341,7 +341,7 @@ acceptance rule, results equal to the trial-by-trial search up to float32
 rounding, for about half the work (c2: 1.1 ms of trials per search -> 0.6 ms).
 False: the trial-by-trial device search (tike_cgrad_line_search)."""
 
-LINEAR_STEPS = 16  # TK_LS_STEPS x TK_LS_PASSES of csrc/ptycho.hip
+LINEAR_STEPS = 16  # TK_LS_STEPS x TK_LS_PASSES of csrc/cgrad_search.hip
 
 
 class _SlotPolicy:

@@ -1,5 +1,5 @@
 """Static instruction mix of one kernel of a csrc/*.hip file, per basic block
-(cross-compiled, no GPU): python tools/kernel_mix.py ptycho.hip <mangled-name substring> [min VALU]"""
+(cross-compiled, no GPU): python tools/kernel_mix.py forward.hip <mangled-name substring> [min VALU]"""
 import collections
 import os
 import re
