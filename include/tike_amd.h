@@ -99,6 +99,15 @@ int tike_conv_adj_probe(const void* nearplane, const float* scan, const void* ps
                         void* probe_adj, int nscan, int S, int pw, int det, int H, int W,
                         void* stream);
 
+/* The largest gridDim.y of a launch on the current device
+ * (hipDeviceAttributeMaxGridDimY), 0 when it cannot be read.  Entries that put
+ * a position, tile or group count into gridDim.y (tike_farplane_gradient,
+ * tike_gradient_scale, tike_scale_modes, tike_scatter_patches,
+ * tike_psi_preconditioner, tike_scatter_amplitudes, the 128^2 costs of
+ * tike_cgrad_line_search_linear) launch in slices of at most this many; tests
+ * size their batches from it. */
+int tike_max_grid_dim_y(void);
+
 /* ---- Propagation: replaces cuFFT behind CachedFFT._fft2/_ifft2
  * (operators/cupy/propagation.py:43-73, cache.py:66-82).
  * ntile tiles of n x n c64; out may alias in (overwrite); every element is

@@ -43,6 +43,7 @@ _d = ctypes.c_double
 
 _PROTOTYPES = {
     "tike_abi_version": [],
+    "tike_max_grid_dim_y": [],
     "tike_init": [],
     "tike_set_deterministic": [_i, _p, _l],
     "tike_patch_fwd": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],

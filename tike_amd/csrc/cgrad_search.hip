@@ -671,12 +671,16 @@ static int tk_cgrad_line_search_linear(int variable, const void* x, const void* 
           if (rc) return rc;
         }
         const long npix = (long)det * det;
-        const dim3 grid((unsigned)((npix + TK_FG_PIX - 1) / TK_FG_PIX), (unsigned)m);
+        // the chunk's positions in gridDim.y, in slices of at most the device's
+        // limit (`at`: first position of the slice within the chunk)
+        TK_GRID_Y_LIMIT(ymax);
+        const unsigned gx = (unsigned)((npix + TK_FG_PIX - 1) / TK_FG_PIX);
         const float* dchunk = (const float*)data + (size_t)lo * npix;
 #define TK_LSF(FIRST, M, MK)                                                                  \
   hipLaunchKernelGGL((ls_ksteps_farplane_kernel<FIRST, M, MK>), grid, dim3(256), 0, stream,      \
-                     (const cf*)far_a, (const cf*)far_b, dchunk, measured, costs_k + lo,          \
-                     (long)nscan, S, npix, inv, row1, state, part ? part + lo : part)
+                     (const cf*)far_a + at * S * npix, (const cf*)far_b + at * S * npix,          \
+                     dchunk + at * npix, measured, costs_k + lo + at, (long)nscan, S, npix, inv,  \
+                     row1, state, part ? part + lo + at : part)
 #define TK_LSF_M(FIRST)          \
   do {                           \
     if (model == 0 && !mk)       \
@@ -688,10 +692,13 @@ static int tk_cgrad_line_search_linear(int variable, const void* x, const void* 
     else                         \
       TK_LSF(FIRST, 1, true);    \
   } while (0)
-        if (pass == 0)
-          TK_LSF_M(true);
-        else
-          TK_LSF_M(false);
+        for (long at = 0; at < m; at += ymax) {
+          const dim3 grid(gx, (unsigned)(m - at < ymax ? m - at : ymax));
+          if (pass == 0)
+            TK_LSF_M(true);
+          else
+            TK_LSF_M(false);
+        }
 #undef TK_LSF_M
 #undef TK_LSF
         if (part)

@@ -42,6 +42,24 @@ extern "C" const char* tike_build_id(void) { return TIKE_BUILD_ID; }
 
 extern "C" int tike_init(void) { return tk_twiddles() ? TK_OK : (int)hipErrorNotInitialized; }
 
+// ------------------------------------------------------------ launch limits
+long tk_max_grid_y() {
+  constexpr int MAXDEV = 64;
+  // per device; 0 = not read yet.  Written without a lock: every thread that
+  // finds 0 reads the same attribute and stores the same value
+  static int cached[MAXDEV] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  if (dev >= 0 && dev < MAXDEV && cached[dev] > 0) return cached[dev];
+  int v = 0;
+  if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxGridDimY, dev) != hipSuccess || v < 1)
+    return 0;
+  if (dev >= 0 && dev < MAXDEV) cached[dev] = v;
+  return v;
+}
+
+extern "C" int tike_max_grid_dim_y(void) { return (int)tk_max_grid_y(); }
+
 // ------------------------------------------------------- deterministic mode
 static bool g_det_on = false;
 static float* g_det_scratch = nullptr;

@@ -47,6 +47,14 @@ int tk_farplane_gradient(void* farplane, const float* data, const unsigned char*
                          int apply_gradient, float unmeasured_scaling, long num_measured,
                          hipStream_t stream, const int* skip);
 
+// csrc/fft2.hip: the largest gridDim.y of a launch on the current device
+// (hipDeviceAttributeMaxGridDimY; 0: the attribute could not be read).  Launches
+// that put a position / tile count into y walk it in slices of at most this.
+long tk_max_grid_y();
+#define TK_GRID_Y_LIMIT(var)                           \
+  const long var = tk_max_grid_y();                    \
+  if (var < 1) return (int)hipErrorInvalidDevice
+
 // ---- deterministic mode (tike_set_deterministic, fft2.hip).  Off: sums that
 // several workgroups contribute to are float atomics (the reference's scheme,
 // operators/cupy/convolution.cu:51-66): their order, and with it the last bits

@@ -416,9 +416,15 @@ extern "C" int tike_scatter_patches(const void* objproj, const float* scan, floa
   }
   int nstrip, wmax, threads;
   tk_group_geometry(pw, &nstrip, &wmax, &threads);
-  const dim3 grid(nstrip, (nscan + TK_GROUP - 1) / TK_GROUP);
-  hipLaunchKernelGGL(scatter_patches_kernel, grid, dim3(threads), 0, (hipStream_t)stream,
-                     (const cf*)objproj, scan, acc, nscan, pw, H, W, wmax);
+  // groups of positions in gridDim.y, in slices of at most the device's limit
+  TK_GRID_Y_LIMIT(ymax);
+  const long span = ymax * TK_GROUP, P = (long)pw * pw;
+  for (long lo = 0; lo < nscan; lo += span) {
+    const int m = (int)(nscan - lo < span ? nscan - lo : span);
+    const dim3 grid(nstrip, (m + TK_GROUP - 1) / TK_GROUP);
+    hipLaunchKernelGGL(scatter_patches_kernel, grid, dim3(threads), 0, (hipStream_t)stream,
+                       (const cf*)objproj + lo * P, scan + 2 * lo, acc, m, pw, H, W, wmax);
+  }
   TK_LAUNCH_CHECK();
   return TK_OK;
 }
@@ -450,9 +456,14 @@ extern "C" int tike_psi_preconditioner(const float* probe_amp, const float* scan
   }
   int nstrip, wmax, threads;
   tk_group_geometry(pw, &nstrip, &wmax, &threads);
-  const dim3 grid(nstrip, (nscan + TK_GROUP - 1) / TK_GROUP);
-  hipLaunchKernelGGL(psi_precond_kernel, grid, dim3(threads), 0, (hipStream_t)stream, probe_amp,
-                     scan, (float*)out, nscan, pw, H, W, wmax);
+  TK_GRID_Y_LIMIT(ymax);  // groups in gridDim.y, in slices of at most the limit
+  const long span = ymax * TK_GROUP;
+  for (long lo = 0; lo < nscan; lo += span) {
+    const int m = (int)(nscan - lo < span ? nscan - lo : span);
+    const dim3 grid(nstrip, (m + TK_GROUP - 1) / TK_GROUP);
+    hipLaunchKernelGGL(psi_precond_kernel, grid, dim3(threads), 0, (hipStream_t)stream,
+                       probe_amp, scan + 2 * lo, (float*)out, m, pw, H, W, wmax);
+  }
   TK_LAUNCH_CHECK();
   return TK_OK;
 }
@@ -486,9 +497,14 @@ extern "C" int tike_scatter_amplitudes(const float* amp, const float* scan, floa
   }
   int nstrip, wmax, threads;
   tk_group_geometry(pw, &nstrip, &wmax, &threads);
-  const dim3 grid(nstrip, (nscan + TK_GROUP - 1) / TK_GROUP);
-  hipLaunchKernelGGL(scatter_amplitudes_kernel, grid, dim3(threads), 0, (hipStream_t)stream, amp,
-                     scan, out, nscan, pw, H, W, wmax);
+  TK_GRID_Y_LIMIT(ymax);  // groups in gridDim.y, in slices of at most the limit
+  const long span = ymax * TK_GROUP, P = (long)pw * pw;
+  for (long lo = 0; lo < nscan; lo += span) {
+    const int m = (int)(nscan - lo < span ? nscan - lo : span);
+    const dim3 grid(nstrip, (m + TK_GROUP - 1) / TK_GROUP);
+    hipLaunchKernelGGL(scatter_amplitudes_kernel, grid, dim3(threads), 0, (hipStream_t)stream,
+                       amp + lo * P, scan + 2 * lo, out, m, pw, H, W, wmax);
+  }
   TK_LAUNCH_CHECK();
   return TK_OK;
 }

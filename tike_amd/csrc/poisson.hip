@@ -545,8 +545,11 @@ extern "C" int tike_scale_modes(void* farplane, const float* mode_scale,
   TK_CHECK_ARG(farplane && mode_scale);
   const long npix = (long)det * det;
   const unsigned gx = (unsigned)((npix + 1023) / 1024);
-  hipLaunchKernelGGL(scale_modes_kernel, dim3(gx, (unsigned)ntile), dim3(256), 0, stream,
-                     (cf*)farplane, mode_scale, measured, npix);
+  TK_GRID_Y_LIMIT(ymax);  // tiles in gridDim.y, in slices of at most the limit
+  for (long lo = 0; lo < ntile; lo += ymax)
+    hipLaunchKernelGGL(scale_modes_kernel,
+                       dim3(gx, (unsigned)(ntile - lo < ymax ? ntile - lo : ymax)), dim3(256), 0,
+                       stream, (cf*)farplane + lo * npix, mode_scale + lo, measured, npix);
   TK_LAUNCH_CHECK();
   return TK_OK;
 }

@@ -420,23 +420,34 @@ int tk_farplane_gradient(void* farplane, const float* data, const unsigned char*
   TK_CHECK_ARG(farplane && data);
   const float inv = 1.0f / (float)num_measured;
   const long npix = (long)det * det;
-  const dim3 grid((unsigned)((npix + TK_FG_PIX - 1) / TK_FG_PIX), (unsigned)nscan), block(256);
+  // positions in gridDim.y, in slices of at most the device's limit: every
+  // pointer (and the cost sink) advanced to the slice's first position
+  TK_GRID_Y_LIMIT(ymax);
+  const unsigned gx = (unsigned)((npix + TK_FG_PIX - 1) / TK_FG_PIX);
+  const dim3 block(256);
   TkCostSink sink{costs, nullptr, 0};
   if (skip == nullptr) {
-    int rc = tk_cost_sink(costs, nscan, (int)grid.x, stream, &sink);
+    int rc = tk_cost_sink(costs, nscan, (int)gx, stream, &sink);
     if (rc) return rc;
   } else if (costs) {
     hipError_t e = hipMemsetAsync(costs, 0, sizeof(float) * (size_t)nscan, stream);
     if (e != hipSuccess) return (int)e;
   }
 #define TK_FG(M, G)                                                                          \
-  hipLaunchKernelGGL((farplane_gradient_kernel<M, G>), grid, block, 0, stream, (cf*)farplane, \
-                     data, measured, intensity, sink, nscan, S, det, unmeasured_scaling, inv,     \
-                     skip)
-  if (model == 0 && apply_gradient) TK_FG(0, true);
-  if (model == 0 && !apply_gradient) TK_FG(0, false);
-  if (model == 1 && apply_gradient) TK_FG(1, true);
-  if (model == 1 && !apply_gradient) TK_FG(1, false);
+  hipLaunchKernelGGL((farplane_gradient_kernel<M, G>), grid, block, 0, stream,               \
+                     (cf*)farplane + lo * S * npix, data + lo * npix, measured,              \
+                     intensity ? intensity + lo * npix : intensity, part, m, S, det,         \
+                     unmeasured_scaling, inv, skip)
+  for (long lo = 0; lo < nscan; lo += ymax) {
+    const int m = (int)(nscan - lo < ymax ? nscan - lo : ymax);
+    const dim3 grid(gx, (unsigned)m);
+    const TkCostSink part{sink.costs ? sink.costs + lo : nullptr,
+                          sink.part ? sink.part + lo * sink.nslots : nullptr, sink.nslots};
+    if (model == 0 && apply_gradient) TK_FG(0, true);
+    if (model == 0 && !apply_gradient) TK_FG(0, false);
+    if (model == 1 && apply_gradient) TK_FG(1, true);
+    if (model == 1 && !apply_gradient) TK_FG(1, false);
+  }
 #undef TK_FG
 #undef TK_FG_K
   TK_LAUNCH_CHECK();
@@ -503,16 +514,26 @@ extern "C" int tike_gradient_scale(const float* intensity, const float* data,
   TK_CHECK_ARG(intensity && data && gscale);
   const float inv = 1.0f / (float)num_measured;
   const long npix = (long)det * det;
-  const dim3 grid((unsigned)((npix + TK_FG_PIX - 1) / TK_FG_PIX), (unsigned)nscan), block(256);
+  TK_GRID_Y_LIMIT(ymax);  // positions in gridDim.y, in slices of at most the limit
+  const unsigned gx = (unsigned)((npix + TK_FG_PIX - 1) / TK_FG_PIX);
+  const dim3 block(256);
   TkCostSink sink;
-  int rc = tk_cost_sink(costs, nscan, (int)grid.x, stream, &sink);
+  int rc = tk_cost_sink(costs, nscan, (int)gx, stream, &sink);
   if (rc) return rc;
-  if (model == 0)
-    hipLaunchKernelGGL((gradient_scale_kernel<0>), grid, block, 0, stream, intensity, data,
-                       measured, gscale, sink, det, unmeasured_scaling, inv);
-  else
-    hipLaunchKernelGGL((gradient_scale_kernel<1>), grid, block, 0, stream, intensity, data,
-                       measured, gscale, sink, det, unmeasured_scaling, inv);
+  for (long lo = 0; lo < nscan; lo += ymax) {
+    const dim3 grid(gx, (unsigned)(nscan - lo < ymax ? nscan - lo : ymax));
+    const TkCostSink part{sink.costs ? sink.costs + lo : nullptr,
+                          sink.part ? sink.part + lo * sink.nslots : nullptr, sink.nslots};
+    const float* I = intensity + lo * npix;
+    const float* d = data + lo * npix;
+    float* g = gscale + lo * npix;
+    if (model == 0)
+      hipLaunchKernelGGL((gradient_scale_kernel<0>), grid, block, 0, stream, I, d, measured, g,
+                         part, det, unmeasured_scaling, inv);
+    else
+      hipLaunchKernelGGL((gradient_scale_kernel<1>), grid, block, 0, stream, I, d, measured, g,
+                         part, det, unmeasured_scaling, inv);
+  }
   TK_LAUNCH_CHECK();
   return tk_cost_finish(sink, nscan, stream);
 }
