@@ -15,7 +15,7 @@
 //      right comes from the neighbouring lane), overwrites the value with
 //      conj(O) chi and leaves conj(P) chi -- summed over the modes through LDS
 //      -- in `objproj` (nscan,pw,pw),
-//   3. the grouped footprint scatter of lstsq.hip (tike_scatter_patches) into a
+//   3. the grouped footprint scatter of scatter.hip (tike_scatter_patches) into a
 //      planar accumulator; one psi-sized kernel interleaves it at the end.
 // chi is never stored; HBM sees the far plane once (read), probe_adj once
 // (write) when a sub-batch's intermediate stays in the Infinity Cache.
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(N, (N <= 256 ? 4 : 2)) void plain_pass1_kernel(
 }
 
 // ------------------------------------- inverse pass 2 + both adjoint products
-// Same decomposition as ifft2_pass2_gradients_kernel (lstsq.hip): a workgroup
+// Same decomposition as ifft2_pass2_gradients_kernel (lstsq_gradients.hip): a workgroup
 // owns the RB rows {ya + 16 yb} x 64 * CW columns of the tile and walks a chunk
 // of positions; its four waves are MW mode-waves x CW column-waves, lane =
 // column; wave (mw, cw) handles modes {mw, mw + MW, ...}.  `work` holds the

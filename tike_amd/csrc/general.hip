@@ -3,7 +3,7 @@
 // mixed-radix engine plans (n = 2^a 3^b 5^c 7^d 11^e 13^f <= 4096) -- what the
 // reference runs at one speed through cuFFT (ptycho/solvers/lstsq.py:422-579)
 // and the fused power-of-two kernels of forward.hip, ptycho.hip and
-// lstsq.hip do not serve.
+// lstsq_gradients.hip do not serve.
 // Until round 5 these shapes took the unfused round-1 path: patch x probe
 // stored zero-padded, two generic transforms in place, a gradient pass over
 // the stored far plane, two more transforms, a crop, then chi read back by the

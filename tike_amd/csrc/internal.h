@@ -47,6 +47,19 @@ int tk_farplane_gradient(void* farplane, const float* data, const unsigned char*
                          int apply_gradient, float unmeasured_scaling, long num_measured,
                          hipStream_t stream, const int* skip);
 
+// csrc/lstsq_gradients.hip: positions per chunk of a sum over positions (also
+// the eigen pixel updates of csrc/lstsq.hip) and, in deterministic mode, where
+// the chunks leave their partial sums
+int probe_chunk(int nscan, long len = 0, float** part = nullptr);
+
+// read by the probe preconditioner (csrc/lstsq_gradients.hip), the minibatch
+// tail (lstsq.hip) and position correction (position_sums.hip): defined once,
+// so that one replacement flips all three
+#ifndef TK_STATS_PAIRS
+#define TK_STATS_PAIRS 1  // build switch of the A/B (tools/build_variant.py)
+#endif
+static const bool g_stats_pairs = TK_STATS_PAIRS != 0;
+
 // csrc/fft2.hip: the largest gridDim.y of a launch on the current device
 // (hipDeviceAttributeMaxGridDimY; 0: the attribute could not be read).  Launches
 // that put a position / tile count into y walk it in slices of at most this.
