@@ -38,7 +38,7 @@ extern "C" {
  * A binding compares tike_abi_version() of the loaded library with the
  * TIKE_ABI_VERSION it was written against before its first call
  * (tike_amd/_lib.py does; INTEGRATION.md shows the check). */
-#define TIKE_ABI_VERSION 17
+#define TIKE_ABI_VERSION 18
 
 /* sha256 (64 hex digits) of the sources the library was built from: the PMC
  * traffic files under profiles/ carry it, and bench.py withholds a traffic
@@ -726,6 +726,29 @@ int tike_fft2_pass2_inplace(void* tiles, long ntile, int det, int inverse, float
  * (tike_fresnel_colpass, tike_fwd_grad_ifft2_pass1[_slices]).  psi (H,W). */
 int tike_slice_step(void* wave, const void* psi, const float* scan, void* farplane1, int nscan,
                     int S, int det, int H, int W, float scale, void* stream);
+
+/* The step BACK through a slice, the mirror of tike_slice_step: the exact
+ * adjoint of patch x incident probe followed by a Fresnel step
+ * (operators/cupy/multislice.py:144-194, without its division by the number
+ * of slices).  work (nscan,S,det,det) = the input of an inverse pass 2 (the
+ * output of tike_fft2_pass1(inverse) behind the last slice, of
+ * tike_fresnel_colpass(adjoint) behind any other); with g = inv_scale * (pass 2
+ * of work), which never goes to memory,
+ *   objproj[n]      = sum_s conj(beam[n][s]) * g[n][s]     (nscan,det,det): the
+ *                     input of tike_scatter_patches
+ *   farplane1[n][s] = forward pass 1 of conj(patch_n(psi)) * g[n][s]: the input
+ *                     of the next tike_fresnel_colpass(adjoint).
+ * beam (nscan,S,det,det): the incident probes tike_slice_step kept.  work, beam
+ * and psi (H,W) are only read; no output may alias another array.  objproj is
+ * summed over the modes in registers: no atomics.  objproj may be NULL (only
+ * the wave for the slice in front is wanted): beam is then not read and may
+ * be NULL too.  det in {128, 256}, S <= 8; TIKE_ERR_UNSUPPORTED otherwise,
+ * where the same step is tike_ifft2_pass2_products(keep_chi != 0) (inverse
+ * pass 2 in place + objproj) -> tike_conv_adj_probe (conj(patch) x wave) ->
+ * tike_fft2_pass1. */
+int tike_slice_step_back(const void* work, const void* psi, const float* scan, const void* beam,
+                         void* objproj, void* farplane1, int nscan, int S, int det, int H, int W,
+                         float inv_scale, void* stream);
 
 /* pass 2 of the S modes of every position with the illumination
  * amplitude[n] = sum_s |wave[n][s] * scale|^2 formed from the registers

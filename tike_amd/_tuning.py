@@ -21,6 +21,10 @@ the tests that compare two routes.
   TIKE_MS_SLICE_STEP=0 / TIKE_MS_FIRST_STORED=0 / TIKE_MS_STEP_BACK=0
                             multislice rpie: the unfused slice step / the
                             gathered first slice / the step back as written
+  TIKE_CGRAD_MS_FUSED=0 / TIKE_CGRAD_MS_STEP_BACK=0
+                            multislice cgrad: the general operators slice by
+                            slice / the step back through a slice as the three
+                            launches `tike_slice_step_back` replaces
   TIKE_CGRAD_GRAPHS=1       cgrad: replay captured HIP graphs (slower on ROCm 7.2)
   TIKE_FWD_SUB_MIB=n        Ptycho.fwd / adj: far-plane MiB per sub-batch
 """
@@ -46,6 +50,8 @@ precond_chunk = _int("TIKE_PRECOND_CHUNK", 512)
 multislice_slice_step = _flag("TIKE_MS_SLICE_STEP", True)
 multislice_first_stored = _flag("TIKE_MS_FIRST_STORED", True)
 multislice_step_back = _flag("TIKE_MS_STEP_BACK", True)
+cgrad_multislice_fused = _flag("TIKE_CGRAD_MS_FUSED", True)
+cgrad_multislice_step_back = _flag("TIKE_CGRAD_MS_STEP_BACK", True)
 cgrad_graphs = _flag("TIKE_CGRAD_GRAPHS", False)
 fwd_sub_mib = (float(os.environ["TIKE_FWD_SUB_MIB"])
                if os.environ.get("TIKE_FWD_SUB_MIB") else None)

@@ -334,6 +334,145 @@ __global__ __launch_bounds__(N, N == 512 ? 1 : 3) void slice_step_n_kernel(
   }
 }
 
+// ---- the step BACK through a slice: the mirror of tike_slice_step -----------
+// The exact adjoint of e_d = patch(O_d) x beam_d followed by a Fresnel step
+// (multislice.py:144-194) needs, behind slice d, g = inverse pass 2 of the
+// hand-off and from it  objproj = sum_s conj(beam_s) g_s  (-> the scatter: the
+// slice's object gradient) and  w_s = conj(patch) g_s, which the adjoint
+// Fresnel step then carries to the slice in front.  A work item = (position,
+// q) as in slice_step_[n_]kernel: the inverse column stage leaves the rows
+// {rp + RB y2} of every mode in registers -- the rows of NG forward pass-1
+// groups -- so conj(patch) x g starts the next transform where it stands and g
+// never goes to memory.  The patch is gathered once per item (both branches of
+// the gather as in the forward kernel), objproj is summed over the modes in
+// registers and written once: no atomics.  work and beam are only read.
+// PROJ = false (objproj NULL: the probe's gradient alone is wanted): the
+// incident probes are not read and nothing is summed.
+template <int N, bool PROJ>
+__global__ __launch_bounds__(N, 2) void slice_step_back_kernel(const cf* __restrict__ work, const cf* __restrict__ psi,
+                            const float* __restrict__ scan, const cf* __restrict__ beam,
+                            cf* __restrict__ objproj, cf* __restrict__ far, long nscan, int S,
+                            int H, int W, float scale, const cf* __restrict__ twtab) {
+  using G2 = Fft2Geom<N>;
+  using It = TkSliceItem<N>;
+  constexpr int RB = It::RB;
+  __shared__ cf lds[G2::LDS_ELEMS + FftTwLds<N>::ELEMS];
+  cf* twl = lds + G2::LDS_ELEMS;
+  FftTwLds<N>::fill(twl, twtab);
+  __syncthreads();
+  const int t = threadIdx.x;
+  const long total = (long)H * W;
+  for (long w = blockIdx.x; w < nscan * It::NI; w += gridDim.x) {
+    const int q = (int)(w % It::NI);
+    const long n = nscan - 1 - w / It::NI;  // descending: the pass before wrote ascending
+    int line = threadIdx.x / G2::T, j = threadIdx.x % G2::T;
+    asm volatile("" : "+v"(line), "+v"(j));
+    const FftTwLds<N> tw{twl, j};
+    const TkCorner c = tk_corner(scan, n);
+    // conj(object patch) at the rows rp + RB y2 of every group, column t
+    cf O[It::NG][16];
+    const bool interior = c.sy >= 0 && c.sx >= 0 && c.sy + N < H && c.sx + N < W &&
+                          total < (1L << 28);
+#pragma unroll
+    for (int g = 0; g < It::NG; ++g) {
+      const int rp = q + 16 * g;
+      if (interior) {  // uniform
+        typedef float tk_v4f __attribute__((ext_vector_type(4)));
+        const unsigned row_bytes = (unsigned)W * 8u;
+        const unsigned off0 = (unsigned)((c.sy + rp) * W + c.sx + t) * 8u;
+#pragma unroll
+        for (int yh = 0; yh < 16; yh += 8) {
+          tk_v4f u4[8], l4[8];
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            const unsigned off = off0 + (unsigned)(RB * (yh + i)) * row_bytes;
+            __builtin_memcpy(&u4[i], reinterpret_cast<const char*>(psi) + off, 16);
+            __builtin_memcpy(&l4[i], reinterpret_cast<const char*>(psi) + off + row_bytes, 16);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            cf o = mk(u4[i].x * c.w00, u4[i].y * c.w00);
+            o.x += u4[i].z * c.w01;
+            o.y += u4[i].w * c.w01;
+            o.x += l4[i].x * c.w10;
+            o.y += l4[i].y * c.w10;
+            o.x += l4[i].z * c.w11;
+            o.y += l4[i].w * c.w11;
+            O[g][yh + i] = conjf(o);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      } else {
+#pragma unroll
+        for (int y2 = 0; y2 < 16; ++y2) {
+          const int y = c.sy + rp + RB * y2, x = c.sx + t;
+          const bool ok = y >= 0 && y < H && x >= 0 && x < W;
+          const int yc = y < 0 ? 0 : (y >= H ? H - 1 : y);
+          const int xc = x < 0 ? 0 : (x >= W ? W - 1 : x);
+          const cf o = tk_gather(psi, (long)yc * W + xc, W, total, c);
+          O[g][y2] = ok ? conjf(o) : mk(0.f, 0.f);
+        }
+      }
+    }
+    cf acc[It::NG][16];
+#pragma unroll
+    for (int g = 0; g < It::NG; ++g)
+#pragma unroll
+      for (int y2 = 0; y2 < 16; ++y2) acc[g][y2] = mk(0.f, 0.f);
+    for (int s = 0; s < S; ++s) {
+      const long tile = (n * S + s) * (long)N * N;
+      cf v[It::NG][16];
+#pragma unroll
+      for (int f = 0; f < It::NF; ++f) {
+        const int k1 = q + It::NI * f;
+        const cf* __restrict__ p = work + tile + (long)k1 * N + t;
+        const cf* __restrict__ b = beam + tile + (long)k1 * N + t;
+        cf u[RB];
+#pragma unroll
+        for (int r = 0; r < RB; ++r) u[r] = tk_ld_stream(p + (long)(16 * r) * N);
+        Dft<RB, true>::run(u);
+        // (the incident probe eight rows at a time, after the butterfly: all
+        // RB requests in flight beside it would not fit the register budget)
+#pragma unroll
+        for (int kh = 0; kh < RB; kh += 8) {
+          cf bm[8];
+          if (PROJ) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) bm[i] = tk_ld_stream(b + (long)(16 * (kh + i)) * N);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            const int k2 = kh + i, g = It::group(f, k2), y2 = It::y2(f, k2);
+            const cf gk = u[k2] * scale;  // g at row k1 + 16 k2 = rp + RB y2
+            if (PROJ) acc[g][y2] = acc[g][y2] + conjf(bm[i]) * gk;
+            v[g][y2] = O[g][y2] * gk;
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+#pragma unroll
+      for (int g = 0; g < It::NG; ++g) {
+        const int rp = q + 16 * g;
+        Dft<16, false>::run(v[g]);
+#pragma unroll
+        for (int ya = 1; ya < 16; ++ya) v[g][ya] = mul_tw<false>(v[g][ya], twtab[N + rp * ya]);
+        fft2_rows_from_columns<N, false, true>(lds, tw, line, j, v[g],
+                                               far + tile + (long)(16 * rp) * N);
+      }
+    }
+    if (PROJ) {
+#pragma unroll
+      for (int g = 0; g < It::NG; ++g) {
+        cf* __restrict__ o = objproj + n * (long)N * N + (long)(q + 16 * g) * N + t;
+#pragma unroll
+        for (int y2 = 0; y2 < 16; ++y2) tk_st_stream(o + (long)(RB * y2) * N, acc[g][y2]);
+      }
+    }
+  }
+}
+
 // Pass 2 alone, in place: rows {k1 + 16 r} of a tile in, the same rows out.
 // Work item = (tile, k1, 256-column block), tiles in descending order.
 template <int N, bool INV>
@@ -492,6 +631,46 @@ extern "C" int tike_slice_step(void* wave, const void* psi, const float* scan, v
   hipLaunchKernelGGL(slice_step_kernel, dim3(tk_grid((long)nscan * 16, 8)), dim3(256), 0, stream,
                      (cf*)wave, (const cf*)psi, scan, (cf*)farplane1, (long)nscan, S, H, W, scale,
                      tw);
+  TK_LAUNCH_CHECK();
+  return TK_OK;
+}
+
+extern "C" int tike_slice_step_back(const void* work, const void* psi, const float* scan,
+                                    const void* beam, void* objproj, void* farplane1, int nscan,
+                                    int S, int det, int H, int W, float inv_scale,
+                                    void* stream_) {
+  TK_ENTER();
+  hipStream_t stream = (hipStream_t)stream_;
+  TK_CHECK_ARG(nscan >= 0 && S >= 1 && det >= 1 && H >= 1 && W >= 1);
+  if (nscan == 0) return TK_OK;
+  TK_CHECK_ARG(work && psi && scan && farplane1 && work != farplane1);
+  TK_CHECK_ARG(objproj == nullptr ||
+               (beam && beam != farplane1 && objproj != farplane1 && objproj != work &&
+                objproj != beam));
+  // (512^2: conj(patch), the mode sum and a radix-32 butterfly are 192 registers
+  // of values alone; at the 256 of two waves per SIMD the kernel spills --
+  // DESIGN.md -- so that size takes the three launches this one replaces)
+  if ((det != 128 && det != 256) || S > 8) return TK_ERR_UNSUPPORTED;
+  const cf* tw = tk_twiddles();
+  if (!tw) return (int)hipErrorNotInitialized;
+#define TK_SB_P(N, PER, PROJ)                                                                \
+  hipLaunchKernelGGL((slice_step_back_kernel<N, PROJ>),                                      \
+                     dim3(tk_grid((long)nscan * TkSliceItem<N>::NI, PER)), dim3(N), 0,       \
+                     stream, (const cf*)work, (const cf*)psi, scan, (const cf*)beam,         \
+                     (cf*)objproj, (cf*)farplane1, (long)nscan, S, H, W, inv_scale, tw)
+#define TK_SB(N, PER)            \
+  do {                           \
+    if (objproj != nullptr)      \
+      TK_SB_P(N, PER, true);     \
+    else                         \
+      TK_SB_P(N, PER, false);    \
+  } while (0)
+  if (det == 128)
+    TK_SB(128, 16);
+  else
+    TK_SB(256, 8);
+#undef TK_SB_P
+#undef TK_SB
   TK_LAUNCH_CHECK();
   return TK_OK;
 }

@@ -102,12 +102,18 @@ class Multislice(Operator):
                 "this fused path handles single-slice objects only "
                 f"(psi.shape[0] == 1); got {tuple(psi.shape)}.")
 
-    def _check_slices(self, psi):
-        assert psi.ndim == 3
-        if len(psi) > 1 and self.detector_shape != self.probe_shape:
+    @staticmethod
+    def check_slice_shapes(slices, detector_shape, probe_shape):
+        """The ValueError of several slices with probe window != detector."""
+        if slices > 1 and detector_shape != probe_shape:
             raise ValueError(
                 "a multislice object needs detector_shape == probe_shape "
                 "(the propagated exit wave is the next slice's probe)")
+
+    def _check_slices(self, psi):
+        assert psi.ndim == 3
+        self.check_slice_shapes(len(psi), self.detector_shape,
+                                self.probe_shape)
 
     def _incident_probes(self, probe, scan, psi):
         """The probe that falls on slice 0, 1, ...: the exit wave of a slice,

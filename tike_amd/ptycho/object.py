@@ -100,12 +100,15 @@ def get_padded_object(scan, probe, extra: int = 0):
     return psi, scan + (1 + extra) - first
 
 
-def remove_object_ambiguity(psi, probe, preconditioner):
-    """Normalise the object / probe scaling ambiguity (object.py:324-335)."""
+def remove_object_ambiguity(psi, probe, preconditioner, slices=1):
+    """Normalise the object / probe scaling ambiguity (object.py:324-335).
+    slices: how many object slices the wave passes that are divided by the
+    norm; the probe takes the norm to that power, so that the exit wave -- and
+    with it a solver's cost -- is unchanged (1: the reference's rule)."""
     W = preconditioner.real
     W = W / linalg.mnorm(W)
     object_norm = 2 * torch.sqrt(torch.mean(torch.square(psi.abs()) * W))
-    return psi / object_norm, probe * object_norm
+    return psi / object_norm, probe * object_norm**slices
 
 
 def get_absorbtion_image(data, scan, *, rescale=1.0, method="cubic"):

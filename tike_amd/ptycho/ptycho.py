@@ -29,7 +29,7 @@ from .. import _arrays as A
 from .. import cluster
 from .. import precision
 from ..communicators import Comm
-from ..operators import Ptycho
+from ..operators import Multislice, Ptycho
 from . import _spawn, solvers
 from .object import (positivity_constraint, remove_object_ambiguity,
                      smoothness_constraint)
@@ -42,7 +42,7 @@ from .probe import (apply_median_filter_abs_probe, constrain_center_peak,
                     finite_probe_support, get_varying_probe, orthogonalize_eig,
                     power as probe_power,
                     rescale_probe_using_fixed_intensity_photons)
-from .solvers.cgrad import _refuse_fly
+from .solvers.cgrad import _refuse_fly, _refuse_multislice
 from .solvers.lstsq import chunk_positions, mask_info
 from .._lib import check, lib
 
@@ -395,10 +395,15 @@ class Reconstruction():
             raise NotImplementedError(
                 f"solver {name!r} is not available in tike_amd "
                 "(available: lstsq_grad, rpie, cgrad)")
-        if parameters.psi.shape[0] > 1 and name != "rpie":
+        if parameters.psi.shape[0] > 1 and name not in ("rpie", "cgrad"):
             raise NotImplementedError(
                 "multislice objects (psi.shape[0] > 1) are reconstructed by "
-                "rpie only, as in the reference")
+                "rpie (as in the reference) and by cgrad only")
+        if parameters.psi.shape[0] > 1 and name == "cgrad":
+            _refuse_multislice(parameters)
+            Multislice.check_slice_shapes(parameters.psi.shape[0],
+                                          data.shape[-1],
+                                          parameters.probe.shape[-1])
         if use_mpi:
             raise NotImplementedError(
                 "multi-node MPI is out of scope; launch one process per GPU "
@@ -870,8 +875,12 @@ def _apply_object_constraints(parameters):
     due = len(o.costs) % o.rescale_period == 0
     if (due and o.name != "dm" and o.rescale_method == "mean_of_abs_object"
             and oo.preconditioner is not None):
+        # (cgrad descends a stated cost: with several slices the probe takes
+        # the norm once per slice, which leaves the exit wave as it was; rpie
+        # keeps the reference's rule)
         parameters.psi, parameters.probe = remove_object_ambiguity(
-            parameters.psi, parameters.probe, oo.preconditioner)
+            parameters.psi, parameters.probe, oo.preconditioner,
+            slices=parameters.psi.shape[0] if o.name == "cgrad" else 1)
     return parameters
 
 

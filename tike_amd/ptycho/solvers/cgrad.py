@@ -27,6 +27,16 @@ FRAMES of each frame's mean cost over its measured pixels, the intensity of a
 frame being the sum over its positions and modes (``_fly_cost_and_grad``:
 forward, ``tike_fly_farplane_gradient``, adjoint, chunk by chunk over whole
 frames, line searches decided on the host).
+
+Objects of several slices (``psi.shape[0] > 1``, probe window = detector): the
+same cost on the far field behind the last slice, e_d = patch(O_d) x beam_d,
+beam_{d+1} = Fresnel(e_d), and its EXACT gradient -- the adjoint taken back
+through every slice, conj(patch) x wave between two transforms
+(``tike_slice_step_back``), WITHOUT the division by the number of slices that
+``Multislice.adj`` keeps from the reference (``_multislice_cost_and_grad``).
+One conjugate gradient moves all slices at once, then one the probe; the cost
+is not linear in the far plane along an object direction any more, so every
+line search is decided on the host (``_multislice_epoch``).
 """
 import logging
 
@@ -37,6 +47,7 @@ from ... import _tuning
 from ... import _arrays as A
 from ... import opt
 from ..._lib import check, lib
+from ...operators.multislice import fused_slices
 from ...operators.propagation import fft_scales
 from ..exitwave import ExitWaveOptions
 from ..position import gaussian_derivative_taps
@@ -848,6 +859,295 @@ def _fly_epoch(parameters, data, batches, comm, *, op, epoch, fly, cm):
     return parameters
 
 
+MULTISLICE_FUSED = _tuning.cgrad_multislice_fused
+"""128^2, 256^2 or 512^2 tiles, probe window = detector, at most 8 modes: a
+multislice gradient runs on the two-pass kernels.  False: the general route
+(Convolution / FresnelSpectProp / the transforms slice by slice), which is
+also the route of every other shape."""
+
+MULTISLICE_STEP_BACK_FUSED = _tuning.cgrad_multislice_step_back
+"""The step back through a slice as ONE launch (`tike_slice_step_back`; 128^2
+and 256^2).  False, and always at 512^2: `tike_ifft2_pass2_products(keep_chi)`
+-> `tike_conv_adj_probe` -> `tike_fft2_pass1`."""
+
+
+def _refuse_multislice(parameters):
+    """What a multislice cgrad reconstruction cannot be combined with (fly
+    scans are refused by `_refuse_fly`)."""
+    D = parameters.psi.shape[0]
+    if D <= 1:
+        return
+    if parameters.position_options is not None:
+        raise NotImplementedError(
+            f"cgrad with several slices (psi.shape[0] = {D}) and "
+            "position_options: position correction of a multislice object is "
+            "not implemented for cgrad")
+    if (parameters.eigen_probe is not None
+            or parameters.eigen_weights is not None):
+        raise NotImplementedError(
+            f"cgrad with several slices (psi.shape[0] = {D}) and eigen "
+            "probes: a varying probe per position is not implemented for "
+            "cgrad")
+
+
+def _multislice_chunk_fused(op, psi, sc, probe, d32, costs, cm, want_grad,
+                            acc, pacc, bufs):
+    """One chunk on the fused kernels (module docstring; csrc/multislice.hip).
+    acc (D, 2, H, W) float32 or None and pacc (S, pw, pw) complex64 or None
+    receive MINUS the gradients of the chunk."""
+    _, model, nmeasured, mask = cm
+    D, (H, W) = psi.shape[0], psi.shape[-2:]
+    n, S, det = sc.shape[0], probe.shape[-3], op.detector_shape
+    far, mid, beams, objproj = bufs
+    far, mid, objproj = far[:n], mid[:n], objproj[:n]
+    st = A.stream_ptr()
+    fwd_scale, inv_scale = fft_scales(det, op.norm)
+    prop = op.diffraction.propagation._propagator((det, det), psi.device)
+    check(
+        lib.tike_fwd_pass1(A.ptr(psi[0]), A.ptr(sc), A.ptr(probe), 0, None,
+                           None, None, 0, 0, A.ptr(far), None, n, S, det, det,
+                           H, W, st), "multislice cgrad: first slice, pass 1")
+    for d in range(1, D):
+        check(
+            lib.tike_fresnel_colpass(A.ptr(far), A.ptr(prop), 0,
+                                     A.ptr(beams[d - 1, :n]), n * S, det,
+                                     fwd_scale * inv_scale, st),
+            "multislice cgrad: Fresnel step, column passes")
+        check(
+            lib.tike_slice_step(A.ptr(beams[d - 1, :n]), A.ptr(psi[d]),
+                                A.ptr(sc), A.ptr(far), n, S, det, H, W, 1.0,
+                                st),
+            "multislice cgrad: Fresnel step, last pass + next slice")
+    check(lib.tike_fft2_pass2_inplace(A.ptr(far), n * S, det, 0, fwd_scale, st),
+          "multislice cgrad: far field")
+    check(
+        lib.tike_farplane_gradient(A.ptr(far), A.ptr(d32), A.ptr(mask), None,
+                                   A.ptr(costs), n, S, det, model,
+                                   int(want_grad), 1.0, nmeasured, st),
+        "multislice cgrad: cost + far-plane gradient")
+    if not want_grad:
+        return
+    # the far plane holds MINUS the gradient, 0 at unmeasured pixels
+    check(lib.tike_fft2_pass1(A.ptr(far), A.ptr(mid), n * S, det, 1, st),
+          "multislice cgrad: inverse pass 1")
+    one_launch = MULTISLICE_STEP_BACK_FUSED and det in (128, 256)
+    for d in range(D - 1, 0, -1):
+        beam = beams[d - 1, :n]
+        if one_launch:
+            # (no object gradient wanted: no projection, the beams unread)
+            check(
+                lib.tike_slice_step_back(A.ptr(mid), A.ptr(psi[d]), A.ptr(sc),
+                                         A.ptr(beam),
+                                         A.ptr(objproj) if acc is not None
+                                         else None, A.ptr(far), n, S, det, H,
+                                         W, inv_scale, st),
+                "multislice cgrad: step back through a slice")
+        else:
+            check(
+                lib.tike_ifft2_pass2_products(
+                    A.ptr(mid), A.ptr(psi[d]), A.ptr(sc), A.ptr(beam), 1,
+                    A.ptr(objproj), None, 1.0, None, 1, n, S, det, H, W,
+                    inv_scale, st),
+                "multislice cgrad: inverse pass 2 + object projection")
+            # (beam d - 1 is dead from here on: it takes conj(patch) x wave)
+            check(
+                lib.tike_conv_adj_probe(A.ptr(mid), A.ptr(sc), A.ptr(psi[d]),
+                                        A.ptr(beam), n, S, det, det, H, W, st),
+                "multislice cgrad: conj(patch) x wave")
+            check(lib.tike_fft2_pass1(A.ptr(beam), A.ptr(far), n * S, det, 0,
+                                      st),
+                  "multislice cgrad: step back, pass 1")
+        if acc is not None:
+            check(
+                lib.tike_scatter_patches(A.ptr(objproj), A.ptr(sc),
+                                         A.ptr(acc[d]), n, det, H, W, st),
+                "multislice cgrad: object gradient of a slice")
+        check(
+            lib.tike_fresnel_colpass(A.ptr(far), A.ptr(prop), 1, A.ptr(mid),
+                                     n * S, det, fwd_scale, st),
+            "multislice cgrad: adjoint Fresnel step, column passes")
+    check(
+        lib.tike_ifft2_pass2_products(
+            A.ptr(mid), A.ptr(psi[0]), A.ptr(sc), A.ptr(probe), 0,
+            A.ptr(objproj), A.ptr(pacc), 1.0, None, 0, n, S, det, H, W,
+            inv_scale, st),
+        "multislice cgrad: first slice, inverse pass 2 + both products")
+    if acc is not None:
+        check(
+            lib.tike_scatter_patches(A.ptr(objproj), A.ptr(sc), A.ptr(acc[0]),
+                                     n, det, H, W, st),
+            "multislice cgrad: object gradient of the first slice")
+
+
+def _multislice_chunk_general(op, psi, sc, probe, d32, costs, cm, want_grad,
+                              gpsi, gprobe):
+    """One chunk through the general operators, any probe window = detector
+    size.  gpsi (D, H, W) / gprobe (1, 1, S, pw, pw) complex64 or None
+    receive MINUS the gradients of the chunk."""
+    _, model, nmeasured, mask = cm
+    D = psi.shape[0]
+    n, S, det = sc.shape[0], probe.shape[-3], op.detector_shape
+    conv, fresnel = op.diffraction.diffraction, op.diffraction.propagation
+    beams = [probe[0]]  # (1, S, pw, pw), then (n, S, pw, pw)
+    for d in range(D):
+        wave = conv.fwd(psi=psi[d], scan=sc, probe=beams[d])
+        if d + 1 < D:
+            beams.append(fresnel.fwd(wave, overwrite=True))
+    far = op.propagation.fwd(wave, overwrite=True)
+    check(
+        lib.tike_farplane_gradient(A.ptr(far), A.ptr(d32), A.ptr(mask), None,
+                                   A.ptr(costs), n, S, det, model,
+                                   int(want_grad), 1.0, nmeasured,
+                                   A.stream_ptr()),
+        "multislice cgrad: cost + far-plane gradient")
+    if not want_grad:
+        return
+    wave = op.propagation.adj(far, overwrite=True)
+    for d in range(D - 1, -1, -1):
+        if gpsi is not None:
+            # (Convolution.adj adds into the array it is given)
+            conv.adj(nearplane=wave, scan=sc, probe=beams[d], psi=gpsi[d])
+        if d == 0 and gprobe is None:
+            break
+        wave = conv.adj_probe(nearplane=wave, scan=sc, psi=psi[d])
+        if d > 0:
+            wave = fresnel.adj(wave, overwrite=True)
+        else:
+            gprobe += wave.sum(dim=0)[None, None]
+
+
+def _multislice_chunk(op, psi, probe):
+    """Positions per chunk of `_multislice_cost_and_grad`.  Fused route: far +
+    mid + D - 1 sets of incident probes within HALF the HBM that is free right
+    now, as rpie's fused multislice chunks are sized (asked once per
+    minibatch: every evaluation of its line searches then splits alike)."""
+    from . import lstsq as L
+    D = psi.shape[0]
+    S, pw, det = probe.shape[-3], probe.shape[-1], op.detector_shape
+    if (L.CHUNK_POSITIONS_OVERRIDE
+            or not (MULTISLICE_FUSED and fused_slices(pw, det, S))):
+        return chunk_positions(S, det)
+    budget = 1 << 34
+    if psi.device.type == "cuda":
+        free = torch.cuda.mem_get_info(psi.device)[0]
+        held = sum(t.numel() * t.element_size() for name, t in
+                   getattr(_workspace(op), "buffers", {}).items()
+                   if name.startswith("ms_"))
+        budget = min(budget, (free + held) // 2)
+    return max(64, budget // ((D + 1) * S * det * det * 8))
+
+
+def _multislice_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, *,
+                              want_psi, want_probe, want_grad, cm, chunk=None):
+    """(sum of this rank's per-pattern costs, a device scalar; d cost / d psi
+    (D, H, W) or None; d cost / d probe or None -- unnormalised adjoints
+    summed over the ranks, as `_cost_and_grad` returns them) of the positions
+    [lo, hi) for an object of several slices: the exact adjoint through every
+    slice, no division by the number of slices.  Chunk by chunk (`chunk`
+    positions each; None: `_multislice_chunk`); a line-search probe (want_grad
+    False) stops behind the cost."""
+    op.diffraction._check_slices(psi)
+    dev = psi.device
+    D, (H, W) = psi.shape[0], psi.shape[-2:]
+    S, pw, det = probe.shape[-3], probe.shape[-1], op.detector_shape
+    N = hi - lo
+    ws = _workspace(op)
+    fused = MULTISLICE_FUSED and fused_slices(pw, det, S)
+    want_psi, want_probe = want_grad and want_psi, want_grad and want_probe
+    if chunk is None:
+        chunk = _multislice_chunk(op, psi, probe)
+    if fused:
+        nmax = max(1, min(chunk, N))
+        bufs = (ws.get("ms_far", (nmax, S, det, det), torch.complex64, dev),
+                ws.get("ms_mid", (1, nmax, S, det, det), torch.complex64,
+                       dev)[0],
+                ws.get("ms_beams", (max(D - 1, 1), nmax, S, pw, pw),
+                       torch.complex64, dev),
+                ws.get("ms_objproj", (nmax, pw, pw), torch.complex64, dev))
+    n_obj = 2 * D * H * W if want_psi else 0
+    costs = ws.get("costs", (max(N, 1),), torch.float32, dev)[:N]
+    n_prb = 2 * probe.numel() if want_probe else 0
+    grads = torch.zeros(n_obj + n_prb, dtype=torch.float32, device=dev)
+    gprobe = (torch.view_as_complex(grads[n_obj:].view(*probe.shape, 2))
+              if n_prb else None)
+    if fused:  # planar accumulators of the grouped scatter
+        acc = grads[:n_obj].view(D, 2, H, W) if n_obj else None
+    else:
+        gpsi = (torch.view_as_complex(grads[:n_obj].view(D, H, W, 2))
+                if n_obj else None)
+    for clo in range(lo, hi, chunk):
+        chi = min(hi, clo + chunk)
+        sc = scan[clo:chi]
+        d32 = A.data_f32(data, clo, chi)
+        c = costs[clo - lo:chi - lo]
+        if fused:
+            _multislice_chunk_fused(
+                op, psi, sc, probe, d32, c, cm, want_grad, acc,
+                gprobe[0, 0] if gprobe is not None else None, bufs)
+        else:
+            _multislice_chunk_general(op, psi, sc, probe, d32, c, cm,
+                                      want_grad, gpsi, gprobe)
+    if comm.collective and grads.numel():
+        comm.Allreduce(grads)
+    # the accumulators hold MINUS the gradients
+    if fused:
+        gpsi = -torch.complex(acc[:, 0], acc[:, 1]) if n_obj else None
+    elif n_obj:
+        gpsi = -gpsi
+    return (costs.sum(dtype=torch.float64), gpsi,
+            -gprobe if gprobe is not None else None)
+
+
+def _multislice_epoch(parameters, data, batches, comm, *, op, epoch, cm):
+    """One cgrad epoch on an object of several slices:
+    `opt.conjugate_gradient` with the host-side line search over ALL slices at
+    once, then over the probe, per minibatch."""
+    o = parameters.algorithm_options
+    recover_psi = parameters.object_options is not None
+    recover_probe = (parameters.probe_options is not None
+                     and epoch >= parameters.probe_options.update_start)
+    psi, probe, scan = parameters.psi, parameters.probe, parameters.scan
+    batch_cost = []
+    for batch_index, b in enumerate(batches):
+        lo = int(b[0]) if len(b) else 0
+        hi = lo + len(b)
+        comm.minibatch = batch_index
+        finish = lambda total: _finish_cost(total, comm, op, lo, hi)
+        chunk = _multislice_chunk(op, psi, probe)
+
+        def run_for(variable):
+            def run(x, want_grad):
+                r = _multislice_cost_and_grad(
+                    op, comm, data, x if variable == 0 else psi, scan,
+                    probe if variable == 0 else x, lo, hi,
+                    want_psi=variable == 0, want_probe=variable == 1,
+                    want_grad=want_grad, cm=cm, chunk=chunk)
+                return r[0], r[1 + variable]
+            return run
+
+        cost = None
+        if recover_psi:
+            ev = _Evaluator(run_for(0), finish)
+            psi, cost = opt.conjugate_gradient(
+                torch, x=psi, cost_function=ev.cost, grad=ev.grad,
+                dir_multi=lambda x: x[0], num_iter=o.cg_iter,
+                step_length=o.step_length)
+        if recover_probe:
+            ev = _Evaluator(run_for(1), finish)
+            probe, cost = opt.conjugate_gradient(
+                torch, x=probe, cost_function=ev.cost, grad=ev.grad,
+                dir_multi=lambda x: x[0], num_iter=o.cg_iter,
+                step_length=o.step_length)
+        if cost is None:
+            cost = finish(_multislice_cost_and_grad(
+                op, comm, data, psi, scan, probe, lo, hi, want_psi=False,
+                want_probe=False, want_grad=False, cm=cm, chunk=chunk)[0])
+        batch_cost.append(cost)
+    o.costs.append([float(np.mean(batch_cost))])
+    parameters.psi, parameters.probe = psi, probe
+    return parameters
+
+
 def cgrad(parameters, data, batches, comm, *, op, epoch):
     """One epoch: for every minibatch, `cg_iter` CG iterations on psi and
     then (when probe recovery is on) on the probe; with position_options, one
@@ -856,8 +1156,16 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
     o = parameters.algorithm_options
     fly = _fly_of(op, data, parameters.scan)
     _refuse_fly(parameters, fly)
+    _refuse_multislice(parameters)
     if parameters.eigen_probe is not None or parameters.eigen_weights is not None:
         raise NotImplementedError("cgrad does not support eigen probes")
+    if parameters.psi.shape[0] > 1:
+        # the cost is not linear in the far plane along an object direction:
+        # the device line searches, _CostPlan's routes and graph capture are
+        # not taken
+        return _multislice_epoch(
+            parameters, data, batches, comm, op=op, epoch=epoch,
+            cm=_cost_model(parameters.exitwave_options, op.detector_shape))
     if fly > 1:
         # the device line searches, _CostPlan's fused routes and graph capture
         # form the intensity per position: not taken
