@@ -879,8 +879,10 @@ int tike_cgrad_direction(const float* update_planar, const void* update_complex,
  *             the new iterate); not accepted: done = 0, step = the next length
  *             to try, failures += 1; trials counts the cost evaluations made
  *   count     positions over all ranks (the mean's denominator x det^2 is the
- *             kernels'); skip: one device int of scratch; costs (nscan) f32 and
- *             scratch (chunk,S,det,det) c64 workspaces. */
+ *             kernels'); skip: one device int of scratch; scratch
+ *             (chunk,S,det,det) c64 workspace; costs (nscan) f32: on return each
+ *             pattern's cost at the LAST trial made (the accepted one, or the
+ *             last slot's), as xs is that trial's iterate. */
 int tike_cgrad_line_search(int variable, const void* x, const void* d, void* xs,
                            const void* other, const float* scan, const void* data,
                            int data_u16, void* scratch, float* costs, int nscan, int chunk,
@@ -916,6 +918,9 @@ int tike_cgrad_line_search_masked(int variable, const void* x, const void* d, vo
  * formed with the accepted step (xs = x when none was).  Candidates, rule and
  * state as tike_cgrad_line_search, results equal up to float32 rounding; the
  * cost at x that decides is the one formed here (state[0] on entry is ignored).
+ * costs_k holds 17 rows of nscan per-pattern costs -- row 0 at x, rows 1..8 the
+ * first pass, rows 9..16 the second -- and one word behind them; when the first
+ * pass accepts, rows 9..16 of costs_k (and of sums, after stage 3) are zero.
  *   far_a   (chunk,S,det,det) c64: with a_valid != 0 and nscan <= chunk it holds
  *           what the gradient pass at x left in its `scratch` (the forward
  *           hand-off of x; at 128^2 the far plane of x) and is read as it is;
@@ -926,7 +931,8 @@ int tike_cgrad_line_search_masked(int variable, const void* x, const void* d, vo
  *   stage 0: the whole search (one rank; sums unused).  Several ranks -- the cost
  *   sums must be all-reduced between a cost pass and its decision; count is the
  *   number of positions over all ranks --: stage 1 = first cost pass, leaving this
- *   rank's row sums in sums (17 doubles); [all-reduce sums]; 2 = first decision
+ *   rank's row sums 0..8 in sums (17 doubles; rows 9..16 of sums are untouched by
+ *   stage 1, rows 0..8 by stage 3); [all-reduce sums]; 2 = first decision
  *   from sums; 3 = second cost pass -> sums; [all-reduce]; 4 = second decision,
  *   then xs.  The same arguments in every stage. */
 int tike_cgrad_line_search_linear(int variable, const void* x, const void* d, void* xs,

@@ -21,6 +21,21 @@
 #include "ptycho_shared.h"
 #include "fwd_grad_resident.h"
 
+// The cost slots of a speculative launch (a line-search trial enqueued ahead of
+// the decisions), zeroed for the atomics -- unless the launch is skipped: a
+// trial behind the accepted one leaves the costs of the last trial made.
+__global__ __launch_bounds__(256) void zero_costs_unless_skipped_kernel(
+    float* __restrict__ costs, long n, const int* __restrict__ skip) {
+  if (*skip != 0) return;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += gridDim.x * 256L) costs[i] = 0.f;
+}
+
+static void tk_zero_costs_unless_skipped(float* costs, long n, const int* skip,
+                                         hipStream_t stream) {
+  hipLaunchKernelGGL(zero_costs_unless_skipped_kernel, dim3(tk_grid((n + 255) / 256, 1)),
+                     dim3(256), 0, stream, costs, n, skip);
+}
+
 // The column pass as a pure read stream: one workgroup per (position, k1)
 // forms F[k1 + 16 k2] of every mode in registers (radix-16 over the rows
 // 16 r + k1 of the hand-off), accumulates I = sum_s |F_s|^2 and emits the
@@ -132,8 +147,7 @@ int tk_fwd_gradient_scale(const void* scratch, const void* data, int data_u16,
     int rc = tk_cost_sink(costs, nscan, 16 * (det / 256), stream, &sink);
     if (rc) return rc;
   } else if (costs) {
-    hipError_t e = hipMemsetAsync(costs, 0, sizeof(float) * (size_t)nscan, stream);
-    if (e != hipSuccess) return (int)e;
+    tk_zero_costs_unless_skipped(costs, nscan, skip, stream);
   }
   const long nitem = (long)nscan * 16 * (det / 256);
   const float inv = 1.0f / (float)num_measured;
@@ -430,8 +444,7 @@ int tk_farplane_gradient(void* farplane, const float* data, const unsigned char*
     int rc = tk_cost_sink(costs, nscan, (int)gx, stream, &sink);
     if (rc) return rc;
   } else if (costs) {
-    hipError_t e = hipMemsetAsync(costs, 0, sizeof(float) * (size_t)nscan, stream);
-    if (e != hipSuccess) return (int)e;
+    tk_zero_costs_unless_skipped(costs, nscan, skip, stream);
   }
 #define TK_FG(M, G)                                                                          \
   hipLaunchKernelGGL((farplane_gradient_kernel<M, G>), grid, block, 0, stream,               \
