@@ -38,7 +38,7 @@ extern "C" {
  * A binding compares tike_abi_version() of the loaded library with the
  * TIKE_ABI_VERSION it was written against before its first call
  * (tike_amd/_lib.py does; INTEGRATION.md shows the check). */
-#define TIKE_ABI_VERSION 18
+#define TIKE_ABI_VERSION 19
 
 /* sha256 (64 hex digits) of the sources the library was built from: the PMC
  * traffic files under profiles/ carry it, and bench.py withholds a traffic
@@ -1187,6 +1187,44 @@ int tike_fly_farplane_gradient(void* farplane, const void* data, int data_u16,
                                int nframe, int fly, int S, int det, int model,
                                int apply_gradient, float unmeasured_scaling, long num_measured,
                                void* stream);
+
+/* ---- differentiable intensity model (tike_amd/autograd.py; no reference
+ * counterpart): an upstream gradient applied to a far plane.
+ *   farplane[f][j][p] *= scale * table[f][p]      f < nframe, j < P, p < npix
+ * farplane (nframe,P,npix) c64 in place; table (nframe,npix) f32, shared by
+ * the P planes of a frame (P = fly * S: the positions and modes that expose
+ * frame f).  The factor is formed once per pixel (one float32 rounding) and
+ * multiplies both parts of every plane (one rounding each).  The far plane is
+ * read once and written once with 16-byte accesses, the last npix % 4 pixels
+ * of a frame one per lane; any P.  No allocation.  For detector sizes without
+ * tike_ifft2_crop_scaled, which applies such a table while it loads.
+ * TIKE_ERR_ARG for a NULL array, P < 1, npix < 1 or more workgroups than one
+ * launch holds; nframe == 0 returns 0 without a launch. */
+int tike_farplane_scale(void* farplane, const float* table, long nframe, int P, long npix,
+                        float scale, void* stream);
+
+/* ---- the exact gradient of the bilinear patch gather with respect to the
+ * scan positions (no reference counterpart: tike_position_sums,
+ * tike_rpie_position_sums and tike_position_pd_sums ESTIMATE a shift).
+ * objproj (nscan,pw,pw) c64 = the gradient that reaches the patches
+ * (tike_lstsq_gradients: sum_s conj(P_s) chi_n,s); scan (nscan,2) f32; psi
+ * (H,W) c64.  With (sy, sx) = floor(scan[n]), (fy, fx) the fractions and, for
+ * patch pixel (y, x), O00 = psi[sy+y][sx+x], O01 = psi[sy+y][sx+x+1], O10 =
+ * psi[sy+y+1][sx+x], O11 = psi[sy+y+1][sx+x+1] (the taps of convolution.cu:
+ * 101-134, weights (1-fx)(1-fy), fx(1-fy), (1-fx)fy, fx fy):
+ *   Dy = (1-fx)(O10 - O00) + fx (O11 - O01)
+ *   Dx = (1-fy)(O01 - O00) + fy (O11 - O10)
+ *   grad[n] = ( sum_px Re(Dy conj(objproj_n)), sum_px Re(Dx conj(objproj_n)) )
+ * -- the derivative of the patch with the integer part of the position held
+ * fixed; scan column 0 is y.  grad (nscan,2) f32, overwritten.  The products
+ * are float32, the sums float64 in a fixed order (they cancel down to a
+ * thousandth of their absolute terms) and rounded once at the end; one
+ * workgroup per position, no atomics: two calls give the same bits.  A tap
+ * outside the object counts as zero; nothing outside the arrays is read for
+ * any position.  No allocation.  TIKE_ERR_ARG for a NULL array, pw < 1, H < 1,
+ * W < 1 or nscan > 2^31 - 1; nscan == 0 returns 0 without a launch. */
+int tike_scan_gradient(const void* objproj, const float* scan, const void* psi, float* grad,
+                       long nscan, int pw, int H, int W, void* stream);
 
 /* ---- collectives: the per-minibatch gradient all-reduce over RCCL / xGMI,
  * one process (or thread) per GPU.  Replaces the serial peer-copy reduction of

@@ -1,0 +1,196 @@
+// The two kernels the differentiable intensity model (tike_amd/autograd.py)
+// adds to the operators: the upstream gradient applied to a far plane, and the
+// EXACT gradient of the bilinear patch gather with respect to the scan
+// positions.  No reference counterpart: the reference takes its derivatives
+// from hand-written adjoints and has no d/d scan.
+//
+//   tike_farplane_scale   farplane[f][j][p] *= scale * table[f][p]
+//   tike_scan_gradient    grad[n] = sum_px Re( (Dy_n, Dx_n) conj(objproj_n) )
+//
+// Byte models.  tike_farplane_scale, per frame of P planes of npix pixels:
+// P * npix * 8 bytes of far plane read once and written once, npix * 4 bytes
+// of table.  tike_scan_gradient, per position: pw^2 * 8 bytes of objproj read
+// once and (pw + 1)^2 * 8 bytes of object (mostly served from cache: the
+// footprints of neighbouring positions overlap), 8 bytes written.
+#include "../../include/tike_amd.h"
+#include "common.h"
+
+namespace {
+
+// 16-byte accesses whose ADDRESS is only as aligned as an element (a plane
+// starts at a multiple of npix elements): see position_pd.hip.
+typedef float ag_f4 __attribute__((ext_vector_type(4), aligned(8)));  // two cf
+typedef float ag_t4 __attribute__((ext_vector_type(4), aligned(4)));  // four factors
+
+constexpr int AG_PX = 4;  // pixels of a lane: two 16-byte far-plane accesses per plane
+
+// A lane owns AG_PX consecutive pixels of one frame: their factors are loaded
+// once and stay in registers over the P planes.  The last npix % AG_PX pixels
+// of a frame are taken one per lane by the lanes behind the last vector.
+// `bpf` workgroups serve a frame.
+__global__ __launch_bounds__(256) void farplane_scale_kernel(cf* __restrict__ farplane,
+                                                             const float* __restrict__ table,
+                                                             int P, long npix, float scale,
+                                                             long bpf) {
+  const long f = (long)blockIdx.x / bpf;
+  const long v = ((long)blockIdx.x % bpf) * blockDim.x + threadIdx.x;
+  cf* __restrict__ F = farplane + f * P * npix;
+  const float* __restrict__ T = table + f * npix;
+  const long nvec = npix / AG_PX;
+  if (v < nvec) {
+    const long p = v * AG_PX;
+    ag_t4 t = *reinterpret_cast<const ag_t4*>(T + p);
+    t *= scale;
+#pragma unroll 4
+    for (int j = 0; j < P; ++j) {
+      cf* at = F + j * npix + p;
+      ag_f4 a = *reinterpret_cast<const ag_f4*>(at);
+      ag_f4 b = *reinterpret_cast<const ag_f4*>(at + 2);
+      a.x *= t.x, a.y *= t.x, a.z *= t.y, a.w *= t.y;
+      b.x *= t.z, b.y *= t.z, b.z *= t.w, b.w *= t.w;
+      *reinterpret_cast<ag_f4*>(at) = a;
+      *reinterpret_cast<ag_f4*>(at + 2) = b;
+    }
+    return;
+  }
+  // scalar tail: fewer than AG_PX pixels, one per lane
+  const long p = nvec * AG_PX + (v - nvec);
+  if (p >= npix) return;
+  const float t = T[p] * scale;
+  for (int j = 0; j < P; ++j) F[j * npix + p] = F[j * npix + p] * t;
+}
+
+__device__ __forceinline__ double ag_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ cf ag_lane_up(cf v) {  // lane i receives lane i + 1
+  return mk(__shfl_down(v.x, 1, 64), __shfl_down(v.y, 1, 64));
+}
+
+constexpr int AG_COLS = 63;  // patch columns of a wave: lane 63 is the halo column
+constexpr int AG_ROWS = 8;   // patch rows of a strip
+
+// One workgroup per position.  The patch is cut into items of AG_ROWS rows x
+// AG_COLS columns, dealt to the four waves in turn.  A lane owns one OBJECT
+// column of its item and walks down the strip: AG_ROWS + 1 object rows, each
+// loaded once -- row y + 1 of pixel row y is row y of pixel row y + 1, and a
+// row serves Dy and Dx alike -- and the tap to the right comes from the next
+// lane by wave shuffle (lane 63 only feeds lane 62).  With the taps
+//   O00 = psi[sy + y][sx + x], O01 the pixel to its right, O10 the pixel below,
+//   O11 below right, and the weights of tk_corner,
+//   Dy = (1 - fx)(O10 - O00) + fx (O11 - O01)      d patch / d scan[n][0]
+//   Dx = (1 - fy)(O01 - O00) + fy (O11 - O10)      d patch / d scan[n][1]
+// (the integer part of the position held fixed).  Every load is unconditional
+// (clamped address, value selected): a tap outside the object counts as zero
+// and nothing outside the arrays is touched, whatever the positions.
+//
+// The products are float32; the sums are float64 in a fixed order (lane, wave
+// shuffles, the four waves through LDS).  The terms cancel over the patch down
+// to a thousandth of their absolute sum, so float32 rounding of a running sum,
+// harmless against the terms, is not harmless against the result
+// (position_pd.hip has the same reason).
+__global__ __launch_bounds__(256) void scan_gradient_kernel(const cf* __restrict__ objproj,
+                                                            const float* __restrict__ scan,
+                                                            const cf* __restrict__ psi,
+                                                            float* __restrict__ grad, int pw,
+                                                            int H, int W) {
+  __shared__ double red[4][2];
+  const long n = blockIdx.x;
+  const cf* __restrict__ q = objproj + n * pw * pw;
+  const float py = scan[2 * n], px = scan[2 * n + 1];
+  const float fy0 = floorf(py), fx0 = floorf(px);
+  const float fy = py - fy0, fx = px - fx0;
+  const long sy = (long)fy0, sx = (long)fx0;
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int nseg = (pw + AG_COLS - 1) / AG_COLS;
+  const int nstrip = (pw + AG_ROWS - 1) / AG_ROWS;
+  double gy = 0., gx = 0.;
+  for (int item = wave; item < nseg * nstrip; item += 4) {  // uniform in a wave
+    const int x = (item % nseg) * AG_COLS + lane;  // patch column; x == pw: the last right tap
+    const int y0 = (item / nseg) * AG_ROWS;
+    const long X = sx + x;
+    const bool okx = X >= 0 && X < W;
+    const long Xc = X < 0 ? 0 : (X < W ? X : W - 1);
+    const bool pixel = lane < AG_COLS && x < pw;
+    const int xq = x < pw ? x : pw - 1;
+    cf o[AG_ROWS + 1], qq[AG_ROWS];
+#pragma unroll
+    for (int j = 0; j <= AG_ROWS; ++j) {
+      const long Y = sy + y0 + j;
+      const bool ok = okx && Y >= 0 && Y < H;
+      const long Yc = Y < 0 ? 0 : (Y < H ? Y : H - 1);
+      const cf v = psi[Yc * W + Xc];
+      o[j] = ok ? v : mk(0.f, 0.f);
+    }
+#pragma unroll
+    for (int j = 0; j < AG_ROWS; ++j) {
+      const int yq = y0 + j < pw ? y0 + j : pw - 1;
+      qq[j] = tk_ld_stream(q + (long)yq * pw + xq);
+    }
+    cf right = ag_lane_up(o[0]);
+#pragma unroll
+    for (int j = 0; j < AG_ROWS; ++j) {
+      const cf o00 = o[j], o01 = right, o10 = o[j + 1];
+      const cf o11 = ag_lane_up(o10);
+      right = o11;
+      const float dyr = (1.0f - fx) * (o10.x - o00.x) + fx * (o11.x - o01.x);
+      const float dyi = (1.0f - fx) * (o10.y - o00.y) + fx * (o11.y - o01.y);
+      const float dxr = (1.0f - fy) * (o01.x - o00.x) + fy * (o11.x - o10.x);
+      const float dxi = (1.0f - fy) * (o01.y - o00.y) + fy * (o11.y - o10.y);
+      const float ty = dyr * qq[j].x + dyi * qq[j].y;  // Re(Dy conj(objproj))
+      const float tx = dxr * qq[j].x + dxi * qq[j].y;
+      const bool live = pixel && y0 + j < pw;
+      gy += live ? (double)ty : 0.;
+      gx += live ? (double)tx : 0.;
+    }
+  }
+  gy = ag_wave_sum(gy);
+  gx = ag_wave_sum(gx);
+  if (lane == 0) {
+    red[wave][0] = gy;
+    red[wave][1] = gx;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const int i = threadIdx.x;
+    grad[2 * n + i] = (float)((red[0][i] + red[1][i]) + (red[2][i] + red[3][i]));
+  }
+}
+
+}  // namespace
+
+extern "C" int tike_farplane_scale(void* farplane, const float* table, long nframe, int P,
+                                   long npix, float scale, void* stream_) {
+  TK_ENTER();
+  hipStream_t stream = (hipStream_t)stream_;
+  TK_CHECK_ARG(farplane && table);
+  TK_CHECK_ARG(nframe >= 0 && P >= 1 && npix >= 1);
+  if (nframe == 0) return TK_OK;
+  // lanes of a frame: one per vector of AG_PX pixels, one per pixel of the tail
+  const long lanes = npix / AG_PX + npix % AG_PX;
+  const long bpf = (lanes + 255) / 256;
+  TK_CHECK_ARG(bpf <= 0x7fffffffL / nframe);  // the workgroups of all frames: grid.x
+  hipLaunchKernelGGL(farplane_scale_kernel, dim3((unsigned)(nframe * bpf)), dim3(256), 0, stream,
+                     (cf*)farplane, table, P, npix, scale, bpf);
+  TK_LAUNCH_CHECK();
+  return TK_OK;
+}
+
+extern "C" int tike_scan_gradient(const void* objproj, const float* scan, const void* psi,
+                                  float* grad, long nscan, int pw, int H, int W,
+                                  void* stream_) {
+  TK_ENTER();
+  hipStream_t stream = (hipStream_t)stream_;
+  TK_CHECK_ARG(objproj && scan && psi && grad);
+  TK_CHECK_ARG(nscan >= 0 && pw >= 1 && H >= 1 && W >= 1);
+  if (nscan == 0) return TK_OK;
+  TK_CHECK_ARG(nscan <= 0x7fffffffL);  // one workgroup per position: grid.x
+  hipLaunchKernelGGL(scan_gradient_kernel, dim3((unsigned)nscan), dim3(256), 0, stream,
+                     (const cf*)objproj, scan, (const cf*)psi, grad, pw, H, W);
+  TK_LAUNCH_CHECK();
+  return TK_OK;
+}
