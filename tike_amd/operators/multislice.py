@@ -63,6 +63,55 @@ def next_incident_probe(psi_slice, scan, beam, scratch, out, propagator,
     return out
 
 
+def fused_forward(psi, scan, probe, per_position, far, beams, propagator,
+                  scale, stored=None):
+    """The way forward through every slice as far as pass 1 of the LAST
+    slice's transform, left in `far` (n, S, det, det): `tike_fwd_pass1` on
+    slice 0, then per slice behind it `tike_fresnel_colpass` (column passes x
+    propagator -> inverse pass 1) -> `tike_slice_step` (the step's last pass,
+    x the slice's patch, pass 1 of the next transform).  beams
+    (D - 1, nmax, S, det, det) receives the probe incident on slice d in
+    beams[d - 1, :n].  per_position: `probe` holds one probe per position;
+    stored (n, det, det), if given, receives the patches of slice 0; scale =
+    forward x inverse normalisation."""
+    from .._lib import check, lib
+    n = scan.shape[0]
+    S, det = far.shape[-3], far.shape[-1]
+    H, W = psi.shape[-2:]
+    st = A.stream_ptr()
+    check(
+        lib.tike_fwd_pass1(A.ptr(psi[0]), A.ptr(scan), A.ptr(probe),
+                           per_position, None, None, None, 0, 0, A.ptr(far),
+                           A.ptr(stored), n, S, det, det, H, W, st),
+        "first slice, pass 1")
+    for d in range(1, psi.shape[0]):
+        beam = A.ptr(beams[d - 1, :n])
+        check(
+            lib.tike_fresnel_colpass(A.ptr(far), A.ptr(propagator), 0, beam,
+                                     n * S, det, scale, st),
+            "Fresnel step: column passes")
+        check(
+            lib.tike_slice_step(beam, A.ptr(psi[d]), A.ptr(scan), A.ptr(far),
+                                n, S, det, H, W, 1.0, st),
+            "Fresnel step: last pass + next slice, pass 1")
+
+
+def chunk_within_hbm(ws, device, planes, S, det):
+    """Positions per chunk of a fused multislice minibatch whose chunk holds
+    `planes` complex64 arrays of (S, det, det) per position: within HALF the
+    HBM that is free right now (ranks that share a GPU, smaller parts, a
+    resident dataset) plus what the `ms_*` buffers of the workspace `ws` hold
+    already, at most 16 GiB, at least 64 positions."""
+    budget = 1 << 34
+    if device.type == "cuda":
+        free = torch.cuda.mem_get_info(device)[0]
+        held = sum(t.numel() * t.element_size() for name, t in
+                   getattr(ws, "buffers", {}).items()
+                   if name.startswith("ms_"))
+        budget = min(budget, (free + held) // 2)
+    return max(64, budget // (planes * S * det * det * 8))
+
+
 class Multislice(Operator):
     """Multiple-slice wavefield propagation."""
 

@@ -21,24 +21,35 @@ algorithm options, the allowed-positions test of rpie, and only then the new
 ``parameters.scan``.  The sums need the object projection alone, which the
 gradient pass of the object writes anyway (``_PositionTerms``).
 
-Fly scans (``data`` holds one frame per ``fly`` consecutive positions,
-reference ptycho.py:95-125): the same conjugate gradient on the mean over
-FRAMES of each frame's mean cost over its measured pixels, the intensity of a
-frame being the sum over its positions and modes (``_fly_cost_and_grad``:
-forward, ``tike_fly_farplane_gradient``, adjoint, chunk by chunk over whole
-frames, line searches decided on the host).
+One epoch loop (``cgrad()``) serves three kinds of minibatch, each behind
+``_Minibatch``.  Per minibatch and per recovered variable (the object, then
+the probe) it runs one conjugate-gradient call -- on the device where the
+minibatch offers that and the search succeeds (``_cg_on_device``), else
+``_host_cg``, the ONE ``opt.conjugate_gradient`` of this module -- and, when
+no variable is recovered, one cost-only evaluation.
 
-Objects of several slices (``psi.shape[0] > 1``, probe window = detector): the
-same cost on the far field behind the last slice, e_d = patch(O_d) x beam_d,
-beam_{d+1} = Fresnel(e_d), and its EXACT gradient -- the adjoint taken back
-through every slice, conj(patch) x wave between two transforms
-(``tike_slice_step_back``), WITHOUT the division by the number of slices that
-``Multislice.adj`` keeps from the reference (``_multislice_cost_and_grad``).
-One conjugate gradient moves all slices at once, then one the probe; the cost
-is not linear in the far plane along an object direction any more, so every
-line search is decided on the host (``_multislice_epoch``).
+* plain (``_CostPlan`` + ``_cost_and_grad``): one pattern per position, a
+  single slice.  The only kind with device line searches, graph capture and
+  position sums.
+* fly scans (``data`` holds one frame per ``fly`` consecutive positions,
+  reference ptycho.py:95-125): the mean over FRAMES of each frame's mean cost
+  over its measured pixels, the intensity of a frame being the sum over its
+  positions and modes (``_fly_cost_and_grad``: forward,
+  ``tike_fly_farplane_gradient``, adjoint, chunk by chunk over whole frames).
+  The device searches form the intensity per position: every line search is
+  decided on the host.
+* objects of several slices (``psi.shape[0] > 1``, probe window = detector):
+  the same cost on the far field behind the last slice, e_d = patch(O_d) x
+  beam_d, beam_{d+1} = Fresnel(e_d), and its EXACT gradient -- the adjoint
+  taken back through every slice, conj(patch) x wave between two transforms
+  (``tike_slice_step_back``), WITHOUT the division by the number of slices
+  that ``Multislice.adj`` keeps from the reference
+  (``_multislice_cost_and_grad``).  One conjugate gradient moves all slices at
+  once, then one the probe; the cost is not linear in the far plane along an
+  object direction any more: every line search is decided on the host.
 """
 import logging
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -47,10 +58,12 @@ from ... import _tuning
 from ... import _arrays as A
 from ... import opt
 from ..._lib import check, lib
-from ...operators.multislice import fused_slices
+from ...operators.multislice import (chunk_within_hbm, fused_forward,
+                                     fused_slices)
 from ...operators.propagation import fft_scales
 from ..exitwave import ExitWaveOptions
 from ..position import gaussian_derivative_taps
+from . import lstsq as L
 from ._plan import MODELS
 from .lstsq import (SPLIT_FORWARD_SIZES, _get_nearplane_gradients,
                     _update_position, _workspace, chunk_positions,
@@ -63,14 +76,21 @@ logger = logging.getLogger(__name__)
 _ALL_MEASURED = {}
 
 
+class _CostModel(NamedTuple):
+    """What cgrad minimises (`_cost_model`; unpacks as the 4-tuple it was)."""
+    options: ExitWaveOptions  # what the gradient passes read
+    model: int  # MODELS
+    nmeasured: int  # measured pixels per pattern
+    mask: Optional[torch.Tensor]  # uint8 (det, det); None: every pixel
+
+
 def _cost_model(exitwave_options, det):
-    """What cgrad minimises, from the caller's exit-wave options: (options the
-    gradient passes read, model 0 / 1, measured pixels per pattern, uint8 mask
-    or None).  A mask whose pixels are all measured means every pixel, whatever
-    its shape (the probe-shaped default); one with unmeasured pixels must be
-    (det, det) -- mask_info raises otherwise.  The exit-wave relaxations of
-    lstsq / rpie (unmeasured_pixels_scaling, step_length_*) are no part of a
-    cost and are not read."""
+    """The `_CostModel` of the caller's exit-wave options.  A mask whose
+    pixels are all measured means every pixel, whatever its shape (the
+    probe-shaped default); one with unmeasured pixels must be (det, det) --
+    mask_info raises otherwise.  The exit-wave relaxations of lstsq / rpie
+    (unmeasured_pixels_scaling, step_length_*) are no part of a cost and are
+    not read."""
     eo = exitwave_options
     if eo.noise_model not in MODELS:
         raise ValueError(f"unknown noise model {eo.noise_model!r}")
@@ -81,9 +101,9 @@ def _cost_model(exitwave_options, det):
             _ALL_MEASURED[key] = ExitWaveOptions(
                 measured_pixels=np.ones((det, det), dtype=bool),
                 noise_model=eo.noise_model)
-        return _ALL_MEASURED[key], model, det * det, None
+        return _CostModel(_ALL_MEASURED[key], model, det * det, None)
     nmeasured, mask_u8 = mask_info(eo, det)
-    return eo, model, nmeasured, mask_u8
+    return _CostModel(eo, model, nmeasured, mask_u8)
 
 
 POISSON_POSITION_STEP = 0.5
@@ -94,6 +114,25 @@ difference there (it is also the reference's first Poisson step,
 exitwave.py `step_length_start`; the option itself is not read, as
 CgradOptions documents).  The numerator is linear in chi: applied to it once
 per epoch."""
+
+
+def _gradient_buffer(psi, probe, want_psi, want_probe, planar=None):
+    """The ONE zeroed float32 buffer in which an evaluation sums MINUS its
+    gradients -- the object's first, then the probe's, so that one
+    `comm.Allreduce` sums both over the ranks -- and its views: (buffer,
+    object view or None, probe view or None).  Views are complex64, shaped
+    like psi and probe; planar: the shape, (..., 2, H, W), of a float32 object
+    view instead (the accumulators of the grouped scatter)."""
+    n_obj = 2 * psi.numel() if want_psi else 0
+    n_prb = 2 * probe.numel() if want_probe else 0
+    grads = torch.zeros(n_obj + n_prb, dtype=torch.float32, device=psi.device)
+    obj = prb = None
+    if want_psi:
+        obj = (grads[:n_obj].view(planar) if planar else
+               torch.view_as_complex(grads[:n_obj].view(*psi.shape, 2)))
+    if want_probe:
+        prb = torch.view_as_complex(grads[n_obj:].view(*probe.shape, 2))
+    return grads, obj, prb
 
 
 class _PositionTerms:
@@ -123,11 +162,10 @@ class _CostPlan:
     and one reduction -- at BASELINE configs[0] (256 positions of 128^2) the
     Python between the launches was most of the epoch."""
 
-    def __init__(self, op, data, scan, lo, hi, S, pw, H, W, dev, cm):
-        det = op.detector_shape
-        # the cost model (_cost_model)
-        self.options, self.model, self.nmeasured, self.mask = cm
-        pmask = A.ptr(self.mask) if self.mask is not None else None
+    def __init__(self, op, data, psi, scan, probe, lo, hi, cm):
+        det, dev = op.detector_shape, psi.device
+        S, pw, (H, W) = probe.shape[-3], probe.shape[-1], psi.shape[-2:]
+        self.model, self.nmeasured = cm.model, cm.nmeasured
         N = hi - lo
         ws = _workspace(op)
         self.split = det in SPLIT_FORWARD_SIZES
@@ -137,7 +175,6 @@ class _CostPlan:
         # detector sizes p x 2^k (round 6): the prime-factor launches of the
         # gradient pipeline with nothing but the costs stored -- sub-tile
         # transforms + the p x p combine, no far plane in natural order
-        from . import lstsq as L
         self.pfa = (not self.split and L.PFA_ROUTE and L.GENERAL_FUSED
                     and L.pfa_gradients(S, pw, det))
         self.pfa_lds = bool(self.pfa and L.PFA_SUBTILES_IN_LDS
@@ -154,7 +191,7 @@ class _CostPlan:
         # resident data that the cost kernel of this size reads as it is
         direct = isinstance(data, torch.Tensor) and (
             self.split or data.dtype == torch.float32)
-        self.pmask = pmask
+        self.pmask = A.ptr(cm.mask)
         self.lo = lo
         self.chunks = []
         for clo in range(lo, hi, chunk):
@@ -244,12 +281,8 @@ class _CostPlan:
         N = self.costs.shape[0]
         patches = ws.get("patches", (max(N, 1), pw, pw), torch.complex64, dev)
         objproj = ws.get("objproj", (n_max, pw, pw), torch.complex64, dev)
-        n_obj = 2 * H * W if want_psi else 0
-        n_prb = 2 * probe.numel() if want_probe else 0
-        grads = torch.zeros(n_obj + n_prb, dtype=torch.float32, device=dev)
-        acc = grads[:n_obj].view(2, H, W) if want_psi else None
-        mpu = (torch.view_as_complex(grads[n_obj:].view(*probe.shape, 2))
-               if want_probe else None)
+        grads, acc, mpu = _gradient_buffer(psi, probe, want_psi, want_probe,
+                                           planar=(2, H, W))
         _, inv_scale = fft_scales(det, op.norm)
         st = A.stream_ptr()
         lo = self.lo
@@ -293,43 +326,36 @@ def _cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, *, want_psi,
     split forward of that pipeline with nothing but the costs stored.
     position_terms (with want_grad): (numerator, denominator) of the shift
     estimates, rows [lo, hi) filled by this gradient pass."""
-    dev = psi.device
-    N = hi - lo
-    S, pw = probe.shape[-3], probe.shape[-1]
-    H, W = psi.shape[-2:]
     if want_grad and plan is not None and plan.supports_gradients():
         costs, acc, mpu = plan.gradients(op, comm, psi, probe, want_psi,
                                          want_probe, position_terms)
-        gpsi = -torch.complex(acc[0], acc[1])[None] if want_psi else None
-        gprobe = -mpu if want_probe else None
     elif want_grad:
         g = _get_nearplane_gradients(
             data, psi, scan, probe, None, None, lo, hi, comm, num_batch=1,
-            exitwave_options=cm[0], op=op, recover_psi=want_psi,
+            exitwave_options=cm.options, op=op, recover_psi=want_psi,
             recover_probe=want_probe, need_chi0=False, plain=True,
             all_mode_position_terms=position_terms)
-        costs = g["costs"]
-        gpsi = gprobe = None
-        if want_psi:
-            gpsi = -torch.complex(g["object_acc"][0], g["object_acc"][1])[None]
-        if want_probe:
-            gprobe = -g["m_probe_update"]
+        costs, acc, mpu = g["costs"], g.get("object_acc"), g.get(
+            "m_probe_update")
     else:
-        gpsi = gprobe = None
-        plan = plan or _CostPlan(op, data, scan, lo, hi, S, pw, H, W, dev, cm)
+        plan = plan or _CostPlan(op, data, psi, scan, probe, lo, hi, cm)
         costs = plan.run(data, psi, probe)
+    # the accumulators hold MINUS the gradients
+    gpsi = (-torch.complex(acc[0], acc[1])[None]
+            if want_grad and want_psi else None)
+    gprobe = -mpu if want_grad and want_probe else None
     total = costs.sum(dtype=torch.float64)  # device scalar (this rank)
     if read_cost:
         return _finish_cost(total, comm, op, lo, hi), gpsi, gprobe
     return total, gpsi, gprobe
 
 
-def _finish_cost(total, comm, op, lo, hi):
-    """Mean cost over the positions of ALL ranks, on the host: one (all-)
-    reduction and one read-back."""
+def _finish_cost(total, comm, op, lo, hi, fly=1):
+    """Mean cost over the positions -- fly scans: the FRAMES -- of ALL ranks,
+    on the host: one (all-)reduction and one read-back."""
     if comm.collective:
         total = comm.Allreduce_scalars([total], total.device)[0]
-    return float(total.item()) / global_count(comm, op, lo, hi)
+    return float(total.item()) / (global_count(comm, op, lo, hi) / fly)
 
 
 DEVICE_LINE_SEARCH = True
@@ -663,29 +689,6 @@ def _cg_on_device(plan, op, comm, psi, probe, variable, o, count, data, scan,
     return None
 
 
-class _Evaluator:
-    """cost / gradient callbacks of one conjugate-gradient call.  The gradient
-    pass forms the cost of its argument as well: it is kept ON THE DEVICE and
-    read back only if the line search asks for the cost of that very array
-    (opt.line_search does, for its starting point) -- which then costs neither
-    a forward pass nor, for the other gradient evaluations, a host
-    synchronisation."""
-
-    def __init__(self, run, finish):
-        self._run, self._finish = run, finish
-        self._x = self._total = None
-
-    def cost(self, x):
-        if x is self._x:
-            return self._finish(self._total)
-        return self._finish(self._run(x, False)[0])
-
-    def grad(self, x):
-        total, g = self._run(x, True)
-        self._x, self._total = x, total
-        return [g]
-
-
 def _fly_of(op, data, scan):
     """Positions per frame, from the arrays a rank holds (the caller has
     validated divisibility); a rank without a frame takes the context's."""
@@ -694,24 +697,45 @@ def _fly_of(op, data, scan):
     return scan.shape[0] // data.shape[0]
 
 
+_REFUSALS = (
+    # (the kind of minibatch, what it cannot be combined with, message), the
+    # most specific wording first
+    ("fly", "positions", "fly={fly} with position_options: position "
+     "correction of fly-scan data is not implemented"),
+    ("fly", "eigen", "fly={fly} with eigen probes: a varying probe per "
+     "position of fly-scan data is not implemented"),
+    ("fly", "slices", "fly={fly} with several slices (psi.shape[0] = {D}): "
+     "multislice fly-scan reconstruction is not implemented"),
+    ("slices", "positions", "cgrad with several slices (psi.shape[0] = {D}) "
+     "and position_options: position correction of a multislice object is "
+     "not implemented for cgrad"),
+    ("slices", "eigen", "cgrad with several slices (psi.shape[0] = {D}) and "
+     "eigen probes: a varying probe per position is not implemented for "
+     "cgrad"),
+    ("any", "eigen", "cgrad does not support eigen probes"),
+)
+
+
+def _refuse(parameters, fly, kinds=("fly", "slices", "any")):
+    """NotImplementedError for the first row of `_REFUSALS` that applies."""
+    D = parameters.psi.shape[0]
+    has = dict(any=True, fly=fly > 1, slices=D > 1,
+               positions=parameters.position_options is not None,
+               eigen=(parameters.eigen_probe is not None
+                      or parameters.eigen_weights is not None))
+    for kind, other, message in _REFUSALS:
+        if kind in kinds and has[kind] and has[other]:
+            raise NotImplementedError(message.format(fly=fly, D=D))
+
+
 def _refuse_fly(parameters, fly):
     """What a fly-scan reconstruction cannot be combined with."""
-    if fly <= 1:
-        return
-    if parameters.position_options is not None:
-        raise NotImplementedError(
-            f"fly={fly} with position_options: position correction of "
-            "fly-scan data is not implemented")
-    if (parameters.eigen_probe is not None
-            or parameters.eigen_weights is not None):
-        raise NotImplementedError(
-            f"fly={fly} with eigen probes: a varying probe per position of "
-            "fly-scan data is not implemented")
-    if parameters.psi.shape[0] > 1:
-        raise NotImplementedError(
-            f"fly={fly} with several slices (psi.shape[0] = "
-            f"{parameters.psi.shape[0]}): multislice fly-scan "
-            "reconstruction is not implemented")
+    _refuse(parameters, fly, ("fly",))
+
+
+def _refuse_multislice(parameters):
+    """What a multislice object cannot be combined with (fly scans: above)."""
+    _refuse(parameters, 1, ("slices",))
 
 
 def _fly_adjoint(op, far, probe, scan, psi, want_psi, want_probe):
@@ -761,7 +785,6 @@ def _fly_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, fly, *,
     plane is read once and not written) and, for a gradient, the adjoint of
     the far plane it left."""
     assert lo % fly == 0 and hi % fly == 0, (lo, hi, fly)
-    _, model, nmeasured, mask = cm
     dev = psi.device
     S, det = probe.shape[-3], op.detector_shape
     N = hi - lo
@@ -770,13 +793,8 @@ def _fly_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, fly, *,
     far_all = ws.get("far", (min(chunk, max(N, 1)), 1, S, det, det),
                      torch.complex64, dev)
     costs = ws.get("costs", (max(N // fly, 1),), torch.float32, dev)[:N // fly]
-    n_obj = psi.numel() * 2 if want_grad and want_psi else 0
-    n_prb = probe.numel() * 2 if want_grad and want_probe else 0
-    grads = torch.zeros(n_obj + n_prb, dtype=torch.float32, device=dev)
-    gpsi = (torch.view_as_complex(grads[:n_obj].view(*psi.shape, 2))
-            if n_obj else None)
-    gprobe = (torch.view_as_complex(grads[n_obj:].view(*probe.shape, 2))
-              if n_prb else None)
+    grads, gpsi, gprobe = _gradient_buffer(
+        psi, probe, want_grad and want_psi, want_grad and want_probe)
     for clo in range(lo, hi, chunk):
         chi = min(hi, clo + chunk)
         sc = scan[clo:chi]
@@ -786,7 +804,8 @@ def _fly_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, fly, *,
         if d.dtype not in (torch.float32, torch.uint16):
             d = d.to(torch.float32)
         op.fly_farplane_gradient(
-            far, d, fly, model=model, measured=mask, num_measured=nmeasured,
+            far, d, fly, model=cm.model, measured=cm.mask,
+            num_measured=cm.nmeasured,
             costs=costs[(clo - lo) // fly:(chi - lo) // fly],
             apply_gradient=want_grad)
         if want_grad:
@@ -801,64 +820,6 @@ def _fly_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, fly, *,
     return costs.sum(dtype=torch.float64), gpsi, gprobe
 
 
-def _fly_epoch(parameters, data, batches, comm, *, op, epoch, fly, cm):
-    """One cgrad epoch on fly-scan data: `opt.conjugate_gradient` with the
-    host-side line search for the object, then the probe, per minibatch."""
-    o = parameters.algorithm_options
-    recover_psi = parameters.object_options is not None
-    recover_probe = (parameters.probe_options is not None
-                     and epoch >= parameters.probe_options.update_start)
-    psi, probe, scan = parameters.psi, parameters.probe, parameters.scan
-    batch_cost = []
-    for batch_index, b in enumerate(batches):
-        lo = int(b[0]) if len(b) else 0
-        hi = lo + len(b)
-        if lo % fly or hi % fly:
-            raise ValueError(
-                f"minibatch [{lo}, {hi}) does not hold whole frames of "
-                f"fly={fly} positions")
-        comm.minibatch = batch_index
-        # the mean is over the FRAMES of all ranks
-        frames = global_count(comm, op, lo, hi) / fly
-
-        def finish(total):
-            if comm.collective:
-                total = comm.Allreduce_scalars([total], total.device)[0]
-            return float(total.item()) / frames
-
-        def run_for(variable):
-            def run(x, want_grad):
-                r = _fly_cost_and_grad(
-                    op, comm, data, x if variable == 0 else psi, scan,
-                    probe if variable == 0 else x, lo, hi, fly,
-                    want_psi=variable == 0, want_probe=variable == 1,
-                    want_grad=want_grad, cm=cm)
-                return r[0], r[1 + variable]
-            return run
-
-        cost = None
-        if recover_psi:
-            ev = _Evaluator(run_for(0), finish)
-            psi, cost = opt.conjugate_gradient(
-                torch, x=psi, cost_function=ev.cost, grad=ev.grad,
-                dir_multi=lambda x: x[0], num_iter=o.cg_iter,
-                step_length=o.step_length)
-        if recover_probe:
-            ev = _Evaluator(run_for(1), finish)
-            probe, cost = opt.conjugate_gradient(
-                torch, x=probe, cost_function=ev.cost, grad=ev.grad,
-                dir_multi=lambda x: x[0], num_iter=o.cg_iter,
-                step_length=o.step_length)
-        if cost is None:
-            cost = finish(_fly_cost_and_grad(
-                op, comm, data, psi, scan, probe, lo, hi, fly, want_psi=False,
-                want_probe=False, want_grad=False, cm=cm)[0])
-        batch_cost.append(cost)
-    o.costs.append([float(np.mean(batch_cost))])
-    parameters.psi, parameters.probe = psi, probe
-    return parameters
-
-
 MULTISLICE_FUSED = _tuning.cgrad_multislice_fused
 """128^2, 256^2 or 512^2 tiles, probe window = detector, at most 8 modes: a
 multislice gradient runs on the two-pass kernels.  False: the general route
@@ -871,31 +832,11 @@ and 256^2).  False, and always at 512^2: `tike_ifft2_pass2_products(keep_chi)`
 -> `tike_conv_adj_probe` -> `tike_fft2_pass1`."""
 
 
-def _refuse_multislice(parameters):
-    """What a multislice cgrad reconstruction cannot be combined with (fly
-    scans are refused by `_refuse_fly`)."""
-    D = parameters.psi.shape[0]
-    if D <= 1:
-        return
-    if parameters.position_options is not None:
-        raise NotImplementedError(
-            f"cgrad with several slices (psi.shape[0] = {D}) and "
-            "position_options: position correction of a multislice object is "
-            "not implemented for cgrad")
-    if (parameters.eigen_probe is not None
-            or parameters.eigen_weights is not None):
-        raise NotImplementedError(
-            f"cgrad with several slices (psi.shape[0] = {D}) and eigen "
-            "probes: a varying probe per position is not implemented for "
-            "cgrad")
-
-
 def _multislice_chunk_fused(op, psi, sc, probe, d32, costs, cm, want_grad,
                             acc, pacc, bufs):
     """One chunk on the fused kernels (module docstring; csrc/multislice.hip).
     acc (D, 2, H, W) float32 or None and pacc (S, pw, pw) complex64 or None
     receive MINUS the gradients of the chunk."""
-    _, model, nmeasured, mask = cm
     D, (H, W) = psi.shape[0], psi.shape[-2:]
     n, S, det = sc.shape[0], probe.shape[-3], op.detector_shape
     far, mid, beams, objproj = bufs
@@ -903,27 +844,13 @@ def _multislice_chunk_fused(op, psi, sc, probe, d32, costs, cm, want_grad,
     st = A.stream_ptr()
     fwd_scale, inv_scale = fft_scales(det, op.norm)
     prop = op.diffraction.propagation._propagator((det, det), psi.device)
-    check(
-        lib.tike_fwd_pass1(A.ptr(psi[0]), A.ptr(sc), A.ptr(probe), 0, None,
-                           None, None, 0, 0, A.ptr(far), None, n, S, det, det,
-                           H, W, st), "multislice cgrad: first slice, pass 1")
-    for d in range(1, D):
-        check(
-            lib.tike_fresnel_colpass(A.ptr(far), A.ptr(prop), 0,
-                                     A.ptr(beams[d - 1, :n]), n * S, det,
-                                     fwd_scale * inv_scale, st),
-            "multislice cgrad: Fresnel step, column passes")
-        check(
-            lib.tike_slice_step(A.ptr(beams[d - 1, :n]), A.ptr(psi[d]),
-                                A.ptr(sc), A.ptr(far), n, S, det, H, W, 1.0,
-                                st),
-            "multislice cgrad: Fresnel step, last pass + next slice")
+    fused_forward(psi, sc, probe, 0, far, beams, prop, fwd_scale * inv_scale)
     check(lib.tike_fft2_pass2_inplace(A.ptr(far), n * S, det, 0, fwd_scale, st),
           "multislice cgrad: far field")
     check(
-        lib.tike_farplane_gradient(A.ptr(far), A.ptr(d32), A.ptr(mask), None,
-                                   A.ptr(costs), n, S, det, model,
-                                   int(want_grad), 1.0, nmeasured, st),
+        lib.tike_farplane_gradient(A.ptr(far), A.ptr(d32), A.ptr(cm.mask),
+                                   None, A.ptr(costs), n, S, det, cm.model,
+                                   int(want_grad), 1.0, cm.nmeasured, st),
         "multislice cgrad: cost + far-plane gradient")
     if not want_grad:
         return
@@ -984,7 +911,6 @@ def _multislice_chunk_general(op, psi, sc, probe, d32, costs, cm, want_grad,
     """One chunk through the general operators, any probe window = detector
     size.  gpsi (D, H, W) / gprobe (1, 1, S, pw, pw) complex64 or None
     receive MINUS the gradients of the chunk."""
-    _, model, nmeasured, mask = cm
     D = psi.shape[0]
     n, S, det = sc.shape[0], probe.shape[-3], op.detector_shape
     conv, fresnel = op.diffraction.diffraction, op.diffraction.propagation
@@ -995,9 +921,9 @@ def _multislice_chunk_general(op, psi, sc, probe, d32, costs, cm, want_grad,
             beams.append(fresnel.fwd(wave, overwrite=True))
     far = op.propagation.fwd(wave, overwrite=True)
     check(
-        lib.tike_farplane_gradient(A.ptr(far), A.ptr(d32), A.ptr(mask), None,
-                                   A.ptr(costs), n, S, det, model,
-                                   int(want_grad), 1.0, nmeasured,
+        lib.tike_farplane_gradient(A.ptr(far), A.ptr(d32), A.ptr(cm.mask),
+                                   None, A.ptr(costs), n, S, det, cm.model,
+                                   int(want_grad), 1.0, cm.nmeasured,
                                    A.stream_ptr()),
         "multislice cgrad: cost + far-plane gradient")
     if not want_grad:
@@ -1021,20 +947,12 @@ def _multislice_chunk(op, psi, probe):
     mid + D - 1 sets of incident probes within HALF the HBM that is free right
     now, as rpie's fused multislice chunks are sized (asked once per
     minibatch: every evaluation of its line searches then splits alike)."""
-    from . import lstsq as L
-    D = psi.shape[0]
     S, pw, det = probe.shape[-3], probe.shape[-1], op.detector_shape
     if (L.CHUNK_POSITIONS_OVERRIDE
             or not (MULTISLICE_FUSED and fused_slices(pw, det, S))):
         return chunk_positions(S, det)
-    budget = 1 << 34
-    if psi.device.type == "cuda":
-        free = torch.cuda.mem_get_info(psi.device)[0]
-        held = sum(t.numel() * t.element_size() for name, t in
-                   getattr(_workspace(op), "buffers", {}).items()
-                   if name.startswith("ms_"))
-        budget = min(budget, (free + held) // 2)
-    return max(64, budget // ((D + 1) * S * det * det * 8))
+    return chunk_within_hbm(_workspace(op), psi.device, psi.shape[0] + 1, S,
+                            det)
 
 
 def _multislice_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, *,
@@ -1047,8 +965,7 @@ def _multislice_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, *,
     positions each; None: `_multislice_chunk`); a line-search probe (want_grad
     False) stops behind the cost."""
     op.diffraction._check_slices(psi)
-    dev = psi.device
-    D, (H, W) = psi.shape[0], psi.shape[-2:]
+    dev, D = psi.device, psi.shape[0]
     S, pw, det = probe.shape[-3], probe.shape[-1], op.detector_shape
     N = hi - lo
     ws = _workspace(op)
@@ -1064,17 +981,11 @@ def _multislice_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, *,
                 ws.get("ms_beams", (max(D - 1, 1), nmax, S, pw, pw),
                        torch.complex64, dev),
                 ws.get("ms_objproj", (nmax, pw, pw), torch.complex64, dev))
-    n_obj = 2 * D * H * W if want_psi else 0
     costs = ws.get("costs", (max(N, 1),), torch.float32, dev)[:N]
-    n_prb = 2 * probe.numel() if want_probe else 0
-    grads = torch.zeros(n_obj + n_prb, dtype=torch.float32, device=dev)
-    gprobe = (torch.view_as_complex(grads[n_obj:].view(*probe.shape, 2))
-              if n_prb else None)
-    if fused:  # planar accumulators of the grouped scatter
-        acc = grads[:n_obj].view(D, 2, H, W) if n_obj else None
-    else:
-        gpsi = (torch.view_as_complex(grads[:n_obj].view(D, H, W, 2))
-                if n_obj else None)
+    # (fused: the planar accumulators of the grouped scatter)
+    grads, gpsi, gprobe = _gradient_buffer(
+        psi, probe, want_psi, want_probe,
+        planar=(D, 2, *psi.shape[-2:]) if fused else None)
     for clo in range(lo, hi, chunk):
         chi = min(hi, clo + chunk)
         sc = scan[clo:chi]
@@ -1082,7 +993,7 @@ def _multislice_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, *,
         c = costs[clo - lo:chi - lo]
         if fused:
             _multislice_chunk_fused(
-                op, psi, sc, probe, d32, c, cm, want_grad, acc,
+                op, psi, sc, probe, d32, c, cm, want_grad, gpsi,
                 gprobe[0, 0] if gprobe is not None else None, bufs)
         else:
             _multislice_chunk_general(op, psi, sc, probe, d32, c, cm,
@@ -1090,62 +1001,103 @@ def _multislice_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, *,
     if comm.collective and grads.numel():
         comm.Allreduce(grads)
     # the accumulators hold MINUS the gradients
-    if fused:
-        gpsi = -torch.complex(acc[:, 0], acc[:, 1]) if n_obj else None
-    elif n_obj:
-        gpsi = -gpsi
+    if gpsi is not None:
+        gpsi = -torch.complex(gpsi[:, 0], gpsi[:, 1]) if fused else -gpsi
     return (costs.sum(dtype=torch.float64), gpsi,
             -gprobe if gprobe is not None else None)
 
 
-def _multislice_epoch(parameters, data, batches, comm, *, op, epoch, cm):
-    """One cgrad epoch on an object of several slices:
-    `opt.conjugate_gradient` with the host-side line search over ALL slices at
-    once, then over the probe, per minibatch."""
-    o = parameters.algorithm_options
-    recover_psi = parameters.object_options is not None
-    recover_probe = (parameters.probe_options is not None
-                     and epoch >= parameters.probe_options.update_start)
-    psi, probe, scan = parameters.psi, parameters.probe, parameters.scan
-    batch_cost = []
-    for batch_index, b in enumerate(batches):
-        lo = int(b[0]) if len(b) else 0
-        hi = lo + len(b)
-        comm.minibatch = batch_index
-        finish = lambda total: _finish_cost(total, comm, op, lo, hi)
-        chunk = _multislice_chunk(op, psi, probe)
+class _Minibatch:
+    """The cost of the positions [lo, hi) of this rank -- all that the epoch
+    loop and `_host_cg` know of a minibatch, whichever of the three kinds
+    (module docstring) it is.
 
-        def run_for(variable):
-            def run(x, want_grad):
-                r = _multislice_cost_and_grad(
-                    op, comm, data, x if variable == 0 else psi, scan,
-                    probe if variable == 0 else x, lo, hi,
-                    want_psi=variable == 0, want_probe=variable == 1,
-                    want_grad=want_grad, cm=cm, chunk=chunk)
-                return r[0], r[1 + variable]
-            return run
+    evaluate(psi, probe, variable, want_grad, position_terms=None) ->
+        (this rank's cost sum, a device float64 scalar; with want_grad MINUS
+        d cost / d variable -- the unnormalised adjoint, summed over the ranks
+        -- else None).  variable: 0 the object, 1 the probe, None cost only.
+        position_terms: plain minibatches only, see `_cost_and_grad`.
+    finish(total) -> the mean cost over all ranks, a host float: the one
+        read-back of an evaluation.
+    on_device: line searches may be decided on the device (`_cg_on_device`,
+        which wants `plan` and `count`): plain minibatches only.
 
-        cost = None
-        if recover_psi:
-            ev = _Evaluator(run_for(0), finish)
-            psi, cost = opt.conjugate_gradient(
-                torch, x=psi, cost_function=ev.cost, grad=ev.grad,
-                dir_multi=lambda x: x[0], num_iter=o.cg_iter,
-                step_length=o.step_length)
-        if recover_probe:
-            ev = _Evaluator(run_for(1), finish)
-            probe, cost = opt.conjugate_gradient(
-                torch, x=probe, cost_function=ev.cost, grad=ev.grad,
-                dir_multi=lambda x: x[0], num_iter=o.cg_iter,
-                step_length=o.step_length)
-        if cost is None:
-            cost = finish(_multislice_cost_and_grad(
-                op, comm, data, psi, scan, probe, lo, hi, want_psi=False,
-                want_probe=False, want_grad=False, cm=cm, chunk=chunk)[0])
-        batch_cost.append(cost)
-    o.costs.append([float(np.mean(batch_cost))])
-    parameters.psi, parameters.probe = psi, probe
-    return parameters
+    Every rank builds every minibatch and makes every collective, whatever
+    its share."""
+
+    on_device = False
+
+    def __init__(self, op, comm, data, psi, scan, probe, lo, hi, cm, fly):
+        self.where = (op, comm, data), scan, (lo, hi)
+        self.finish = lambda total: _finish_cost(total, comm, op, lo, hi, fly)
+        if psi.shape[0] > 1:  # (every evaluation splits into the same chunks)
+            self.run = _multislice_cost_and_grad
+            self.how = dict(cm=cm, chunk=_multislice_chunk(op, psi, probe))
+        elif fly > 1:
+            if lo % fly or hi % fly:
+                raise ValueError(
+                    f"minibatch [{lo}, {hi}) does not hold whole frames of "
+                    f"fly={fly} positions")
+            global_count(comm, op, lo, hi)  # (all-reduced ahead of the passes)
+            self.run, self.how = _fly_cost_and_grad, dict(cm=cm, fly=fly)
+        else:
+            self.plan = _CostPlan(op, data, psi, scan, probe, lo, hi, cm)
+            self.run = _cost_and_grad
+            self.how = dict(cm=cm, read_cost=False, plan=self.plan)
+            # line searches decided on the device: one rank, HBM-resident
+            # data, the far-plane-free sizes and 128^2
+            # (several ranks: the all-at-once search, whose cost sums are
+            # all-reduced between its cost passes and its decisions -- every
+            # rank must take the same route, so every rank must hold positions)
+            self.on_device = (DEVICE_LINE_SEARCH and hi > lo
+                              and isinstance(data, torch.Tensor)
+                              and self.plan.supports_gradients())
+            if comm.collective:
+                self.on_device = (LINEAR_LINE_SEARCH and not USE_GRAPHS
+                                  and _every_rank(comm, op, lo, hi,
+                                                  self.on_device))
+            self.count = global_count(comm, op, lo, hi)
+
+    def evaluate(self, psi, probe, variable, want_grad, position_terms=None):
+        args, scan, span = self.where
+        how = self.how if position_terms is None else dict(
+            self.how, position_terms=position_terms)
+        r = self.run(*args, psi, scan, probe, *span, want_psi=variable == 0,
+                     want_probe=variable == 1, want_grad=want_grad, **how)
+        return r[0], None if variable is None else r[1 + variable]
+
+
+def _host_cg(minibatch, psi, probe, variable, o, positions=None):
+    """`opt.conjugate_gradient` on the object (variable 0) or the probe (1)
+    of one minibatch, every line search decided on the host: (x, mean cost).
+    positions: the `_PositionTerms` of the epoch; the first gradient pass
+    takes the minibatch's sums if they are still owed.
+
+    A gradient pass forms the cost of its argument as well: it is kept ON THE
+    DEVICE and read back only if the line search asks for the cost of that
+    very array (opt.line_search does, for its starting point) -- which then
+    costs neither a forward pass nor, for the other gradient evaluations, a
+    host synchronisation."""
+    last = [None, None]  # the array of the last gradient pass, its cost sum
+
+    def run(x, want_grad):
+        return minibatch.evaluate(
+            x if variable == 0 else psi, probe if variable == 0 else x,
+            variable, want_grad,
+            positions.take() if want_grad and positions is not None else None)
+
+    def cost(x):
+        return minibatch.finish(last[1] if x is last[0] else run(x, False)[0])
+
+    def grad(x):
+        last[1], g = run(x, True)
+        last[0] = x
+        return [g]
+
+    return opt.conjugate_gradient(
+        torch, x=(psi, probe)[variable], cost_function=cost, grad=grad,
+        dir_multi=lambda x: x[0], num_iter=o.cg_iter,
+        step_length=o.step_length)
 
 
 def cgrad(parameters, data, batches, comm, *, op, epoch):
@@ -1155,29 +1107,13 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
     saw the old positions, as in lstsq_grad and rpie)."""
     o = parameters.algorithm_options
     fly = _fly_of(op, data, parameters.scan)
-    _refuse_fly(parameters, fly)
-    _refuse_multislice(parameters)
-    if parameters.eigen_probe is not None or parameters.eigen_weights is not None:
-        raise NotImplementedError("cgrad does not support eigen probes")
-    if parameters.psi.shape[0] > 1:
-        # the cost is not linear in the far plane along an object direction:
-        # the device line searches, _CostPlan's routes and graph capture are
-        # not taken
-        return _multislice_epoch(
-            parameters, data, batches, comm, op=op, epoch=epoch,
-            cm=_cost_model(parameters.exitwave_options, op.detector_shape))
-    if fly > 1:
-        # the device line searches, _CostPlan's fused routes and graph capture
-        # form the intensity per position: not taken
-        return _fly_epoch(
-            parameters, data, batches, comm, op=op, epoch=epoch, fly=fly,
-            cm=_cost_model(parameters.exitwave_options, op.detector_shape))
-    recover_psi = parameters.object_options is not None
-    recover_probe = (parameters.probe_options is not None
-                     and epoch >= parameters.probe_options.update_start)
+    _refuse(parameters, fly)
+    recover = (parameters.object_options is not None,
+               parameters.probe_options is not None
+               and epoch >= parameters.probe_options.update_start)
     psi, probe, scan = parameters.psi, parameters.probe, parameters.scan
     cm = _cost_model(parameters.exitwave_options, op.detector_shape)
-    position_options = parameters.position_options
+    position_options = parameters.position_options  # (plain minibatches only)
     positions = None
     if position_options is not None:
         if position_options.use_position_regularization and epoch > 0:
@@ -1193,103 +1129,46 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
         lo = int(b[0]) if len(b) else 0
         hi = lo + len(b)
         comm.minibatch = batch_index
-        d, s = data, scan
-        cost = None
-        finish = lambda total: _finish_cost(total, comm, op, lo, hi)
-        plan = _CostPlan(op, d, s, lo, hi, probe.shape[-3], probe.shape[-1],
-                         psi.shape[-2], psi.shape[-1], psi.device, cm)
-        # line searches decided on the device: one rank, HBM-resident data,
-        # the far-plane-free sizes and 128^2
-        # (several ranks: the all-at-once search, whose cost sums are
-        # all-reduced between its cost passes and its decisions -- every rank
-        # must take the same route, so every rank must hold positions)
-        on_device = (DEVICE_LINE_SEARCH and hi > lo
-                     and isinstance(d, torch.Tensor)
-                     and plan.supports_gradients())
-        if comm.collective:
-            on_device = (LINEAR_LINE_SEARCH and not USE_GRAPHS
-                         and _every_rank(comm, op, lo, hi, on_device))
-        count = global_count(comm, op, lo, hi)
-        done_psi = done_probe = False
+        mb = _Minibatch(op, comm, data, psi, scan, probe, lo, hi, cm, fly)
         if positions is not None:
             positions.pending = True
             # the object's first gradient pass writes the projection the sums
             # need; without one (object not recovered, no CG iteration, or a
             # CG call replayed from a graph) one extra gradient pass of the
             # minibatch, nothing accumulated: every rank decides alike
-            if not (recover_psi and o.cg_iter >= 1
-                    and not (on_device and USE_GRAPHS)):
-                _cost_and_grad(op, comm, d, psi, s, probe, lo, hi,
-                               want_psi=False, want_probe=False,
-                               want_grad=True, cm=cm, read_cost=False,
-                               plan=plan, position_terms=positions.take())
-        if recover_psi and on_device:
-            r = _cg_on_device(plan, op, comm, psi, probe, 0, o, count, d, s,
-                              lo, hi, positions=positions)
-            if r is not None:
-                psi, cost = r
-                done_psi = True
-        if recover_psi and not done_psi:
-            def run(x, want_grad):
-                r = _cost_and_grad(
-                    op, comm, d, x, s, probe, lo, hi, want_psi=True,
-                    want_probe=False, want_grad=want_grad, cm=cm,
-                    read_cost=False, plan=plan,
-                    position_terms=positions.take()
-                    if want_grad and positions is not None else None)
-                return r[0], r[1]
-            ev = _Evaluator(run, finish)
-            psi, cost = opt.conjugate_gradient(
-                torch, x=psi, cost_function=ev.cost, grad=ev.grad,
-                dir_multi=lambda x: x[0], num_iter=o.cg_iter,
-                step_length=o.step_length)
-        if recover_probe and on_device:
-            r = _cg_on_device(plan, op, comm, psi, probe, 1, o, count, d, s,
-                              lo, hi)
-            if r is not None:
-                probe, cost = r
-                done_probe = True
-        if recover_probe and not done_probe:
-            def run(x, want_grad):
-                r = _cost_and_grad(op, comm, d, psi, s, x, lo, hi,
-                                   want_psi=False, want_probe=True,
-                                   want_grad=want_grad, cm=cm,
-                                   read_cost=False, plan=plan)
-                return r[0], r[2]
-            ev = _Evaluator(run, finish)
-            probe, cost = opt.conjugate_gradient(
-                torch, x=probe, cost_function=ev.cost, grad=ev.grad,
-                dir_multi=lambda x: x[0], num_iter=o.cg_iter,
-                step_length=o.step_length)
-        if cost is None:
-            cost = _cost_and_grad(op, comm, d, psi, s, probe, lo, hi, want_psi=False,
-                                  want_probe=False, want_grad=False, cm=cm)[0]
+            if not (recover[0] and o.cg_iter >= 1
+                    and not (mb.on_device and USE_GRAPHS)):
+                mb.evaluate(psi, probe, None, True, positions.take())
+        cost = None
+        for variable in (0, 1):  # CG on the object, then on the probe
+            if not recover[variable]:
+                continue
+            owed = positions if variable == 0 else None
+            r = None
+            if mb.on_device:
+                r = _cg_on_device(mb.plan, op, comm, psi, probe, variable, o,
+                                  mb.count, data, scan, lo, hi,
+                                  positions=owed)
+            if r is None:
+                r = _host_cg(mb, psi, probe, variable, o, owed)
+            x, cost = r
+            psi, probe = (x, probe) if variable == 0 else (psi, x)
+        if cost is None:  # no variable recovered: the cost alone
+            cost = mb.finish(mb.evaluate(psi, probe, None, False)[0])
         batch_cost.append(cost)
-    flag = None
+    o.costs.append([float(np.mean(batch_cost))])  # (host floats, all of them)
     if positions is not None:
         # the minibatches above all used the old positions
         numerator = positions.numerator
-        if cm[1] == MODELS["poisson"]:
+        if cm.model == MODELS["poisson"]:
             numerator = POISSON_POSITION_STEP * numerator
         scan = _update_position(scan, position_options, numerator,
                                 positions.denominator, comm, alpha=o.alpha,
                                 epoch=epoch)
         # ... and the new ones must not reach a kernel unless every patch
         # stays inside the object
-        flag = _positions_flag(scan, psi, probe, comm)
-    if any(isinstance(c, torch.Tensor) for c in batch_cost):
-        # device-side searches leave the cost on the device: one read-back
-        # (the allowed-positions flag travels with it)
-        batch_cost = torch.stack([
-            c.to(torch.float64) if isinstance(c, torch.Tensor) else
-            torch.tensor(float(c), dtype=torch.float64, device=psi.device)
-            for c in batch_cost + ([] if flag is None else [flag])
-        ]).cpu().numpy()
-        if flag is not None:
-            batch_cost, flag = batch_cost[:-1], float(batch_cost[-1])
-    o.costs.append([float(np.mean(batch_cost))])
-    if flag is not None:
-        _raise_unless_allowed(float(flag), scan, psi, probe)
+        _raise_unless_allowed(float(_positions_flag(scan, psi, probe, comm)),
+                              scan, psi, probe)
         parameters.scan = scan
     parameters.psi, parameters.probe = psi, probe
     return parameters

@@ -31,11 +31,10 @@ from ... import random as trandom
 from ..._lib import check, lib
 from ...operators.propagation import fft_scales
 from ..position import gaussian_derivative_taps
+from ._plan import MODELS as _MODELS
 from ._plan import GradientPlan
 
 logger = logging.getLogger(__name__)
-
-_MODELS = {"gaussian": 0, "poisson": 1}
 
 
 class _Workspace:

@@ -42,7 +42,8 @@ from ... import linalg
 from ... import opt
 from ... import random as trandom
 from ..._lib import check, lib
-from ...operators.multislice import fused_slices, next_incident_probe
+from ...operators.multislice import (chunk_within_hbm, fused_forward,
+                                     fused_slices, next_incident_probe)
 from ...operators.propagation import fft_scales
 from ..position import check_allowed_positions
 from ..probe import get_varying_probe
@@ -344,16 +345,8 @@ def _gradients_multislice_fused(data, psi, scan, probe, eigen_probe,
     # Measured (c3rpie2, same box): 64 / 128 / 256 / 512 / 1000 positions per
     # chunk -> 45.2 / 47.4 / 49.5 / 51.2 / 52.4 k patterns/s: these stages
     # hand nothing over through the Infinity Cache, longer launches win.
-    # ... within HALF the HBM that is free right now (ranks that share a GPU,
-    # smaller parts, a resident dataset), at most 16 GiB, at least 64 positions
-    budget = 1 << 34
-    if dev.type == "cuda":
-        free = torch.cuda.mem_get_info(dev)[0]
-        held = sum(t.numel() * t.element_size() for name, t in
-                   getattr(ws, "buffers", {}).items() if name.startswith("ms_"))
-        budget = min(budget, (free + held) // 2)
     chunk = (L.chunk_positions(S, det) if L.CHUNK_POSITIONS_OVERRIDE else
-             max(64, budget // (2 * D * S * det * det * 8)))
+             chunk_within_hbm(ws, dev, 2 * D, S, det))
     nmax = max(1, min(chunk, B))
     far = ws.get("ms_far", (nmax, S, det, det), torch.complex64, dev)
     nback = D if step_back_in_frequency else 1
@@ -384,26 +377,9 @@ def _gradients_multislice_fused(data, psi, scan, probe, eigen_probe,
             ws.get("ms_patches", (nmax, pw, pw), torch.complex64, dev)[:n]
             if first_stored else None)
         if SLICE_STEP_FUSED:
-            # pass 1 of slice 0, then per slice behind it: column passes of
-            # the Fresnel step -> `tike_slice_step` (the step's last pass,
-            # x the slice's patch, pass 1 of the next transform)
-            check(
-                lib.tike_fwd_pass1(
-                    A.ptr(psi[0]), A.ptr(sc), A.ptr(unique), incident[0][1],
-                    None, None, None, 0, 0, A.ptr(far), A.ptr(stored),
-                    n, S, pw, det, H, W, st), "first slice, pass 1")
-            for d in range(1, D):
-                check(
-                    lib.tike_fresnel_colpass(
-                        A.ptr(far), A.ptr(prop), 0, A.ptr(beams[d - 1, :n]),
-                        n * S, det, fwd_scale * inv_scale, st),
-                    "Fresnel step: column passes")
-                check(
-                    lib.tike_slice_step(
-                        A.ptr(beams[d - 1, :n]), A.ptr(psi[d]), A.ptr(sc),
-                        A.ptr(far), n, S, det, H, W, 1.0, st),
-                    "Fresnel step: last pass + next slice, pass 1")
-                incident.append((beams[d - 1, :n], 1))
+            fused_forward(psi, sc, unique, incident[0][1], far, beams, prop,
+                          fwd_scale * inv_scale, stored=stored)
+            incident += [(beams[d - 1, :n], 1) for d in range(1, D)]
         else:
             for d in range(D - 1):
                 nxt = next_incident_probe(
