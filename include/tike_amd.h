@@ -38,7 +38,7 @@ extern "C" {
  * A binding compares tike_abi_version() of the loaded library with the
  * TIKE_ABI_VERSION it was written against before its first call
  * (tike_amd/_lib.py does; INTEGRATION.md shows the check). */
-#define TIKE_ABI_VERSION 19
+#define TIKE_ABI_VERSION 20
 
 /* sha256 (64 hex digits) of the sources the library was built from: the PMC
  * traffic files under profiles/ carry it, and bench.py withholds a traffic
@@ -1225,6 +1225,29 @@ int tike_farplane_scale(void* farplane, const float* table, long nframe, int P, 
  * W < 1 or nscan > 2^31 - 1; nscan == 0 returns 0 without a launch. */
 int tike_scan_gradient(const void* objproj, const float* scan, const void* psi, float* grad,
                        long nscan, int pw, int H, int W, void* stream);
+
+/* The same gradient summed over the D slices of a multislice object (no
+ * reference counterpart either): objproj is D planes of (nscan,pw,pw) c64,
+ * plane d = sum_s conj(beam_d[n][s]) w_d[n][s], the gradient that reaches the
+ * patches of slice d (tike_slice_step_back, tike_ifft2_pass2_products), the
+ * planes `slice_stride` ELEMENTS apart -- rows of a (D,nmax,pw,pw) workspace
+ * serve; psi (D,H,W) c64; scan (nscan,2) f32.  With the taps O00 ... O11 of
+ * tike_scan_gradient taken from slice d,
+ *   Dy_d = (1-fx)(O10 - O00) + fx (O11 - O01)
+ *   Dx_d = (1-fy)(O01 - O00) + fy (O11 - O10)
+ *   grad[n] = ( sum_d sum_px Re(Dy_d conj(objproj_d,n)),
+ *               sum_d sum_px Re(Dx_d conj(objproj_d,n)) )
+ * grad (nscan,2) f32, overwritten.  One workgroup per position walks the
+ * slices outermost; the products are float32, ONE float64 running sum per lane
+ * goes over all slices and pixels in a fixed order and is rounded to float32
+ * once; no atomics: two calls give the same bits, and D == 1 gives the bits of
+ * tike_scan_gradient.  A tap outside the object counts as zero; nothing
+ * outside the arrays is read for any position.  No allocation.  TIKE_ERR_ARG
+ * for a NULL array, D < 1, pw < 1, H < 1, W < 1, slice_stride < nscan * pw * pw
+ * or nscan > 2^31 - 1; nscan == 0 returns 0 without a launch. */
+int tike_scan_gradient_slices(const void* objproj, long slice_stride, const float* scan,
+                              const void* psi, float* grad, long nscan, int D, int pw, int H,
+                              int W, void* stream);
 
 /* ---- collectives: the per-minibatch gradient all-reduce over RCCL / xGMI,
  * one process (or thread) per GPU.  Replaces the serial peer-copy reduction of

@@ -34,12 +34,48 @@ most one chunk of far plane is ever resident:
 
 No torch arithmetic on that path: views, allocation and the final
 planar-to-complex conversion of the object gradient only.
+
+``multislice_intensity(operator, psi, probe, scan, fly=...)`` is the same for
+an object of D slices (probe window = detector): e_d = patch_n(O_d) beam_d,
+beam_0 = the probe, beam_{d+1} = Fresnel(e_d), far = F e_{D-1}.  Backward, the
+exact adjoint through every slice with no division by D:
+
+    G[n,s]       = 2 g[f(n)] far[n,s]
+    w_{D-1}      = F^H G
+    objproj_d[n] = sum_s conj(beam_d[n,s]) w_d[n,s]
+    psi.grad[d]  = scatter_n(objproj_d[n])
+    w_{d-1}      = Fresnel^H(conj(patch_n(O_d)) w_d)   F^-1 conj(H) F: the
+                                                       same for every `norm`
+    probe.grad   = sum_n conj(patch_n(O_0)) w_0
+    scan.grad[n] = sum_d sum_px Re((Dy_n,d, Dx_n,d) conj(objproj_d[n]))
+
+Per chunk of whole frames, the forward recomputed, on the route `cgrad` takes
+for the shape (`fused_slices`; its `MULTISLICE_FUSED` and
+`MULTISLICE_STEP_BACK_FUSED` are honoured):
+
+* fused (128^2, 256^2, 512^2, at most 8 modes): `fused_forward` ->
+  tike_fft2_pass2_inplace -> tike_ifft2_pass1_scaled (g applied while inverse
+  pass 1 loads; the factor 2 and the forward scale ride on the pass 2 behind
+  it) -> per slice tike_slice_step_back (512^2, or the lever off:
+  tike_ifft2_pass2_products(keep_chi) -> tike_conv_adj_probe ->
+  tike_fft2_pass1) -> tike_scatter_patches -> tike_fresnel_colpass(adjoint);
+  slice 0: tike_ifft2_pass2_products with the probe gradient;
+* general (any other probe window = detector, at most MAX_MODES modes):
+  Convolution / FresnelSpectProp / tike_fft2 slice by slice,
+  tike_farplane_scale for g, tike_lstsq_gradients for every slice's objproj;
+
+then ONE tike_scan_gradient_slices over the D objproj planes of the chunk.
+Only what `needs_input_grad` asks for is launched.
 """
+import importlib
+
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import _arrays as A
 from ._lib import check, lib
+from .operators.multislice import (Multislice, chunk_within_hbm, fused_forward,
+                                   fused_slices)
 from .operators.propagation import fft_scales
 
 MAX_MODES = 16
@@ -49,56 +85,63 @@ _SCALED_INVERSE_SIZES = (128, 256, 512)
 """Detector sizes of `tike_ifft2_crop_scaled`."""
 
 
-def _checked(operator, psi, probe, scan, fly, check_positions):
-    """Every refusal, in an order that needs no device until the last one."""
-    for name, x, dtype in (("psi", psi, torch.complex64),
+def _checked(operator, psi, probe, scan, fly, check_positions,
+             name="intensity", slices=False):
+    """Every refusal, in an order that needs no device until the last one.
+    slices: `multislice_intensity` -- any number of slices, whose shapes
+    `Multislice.check_slice_shapes` judges."""
+    depth = "D" if slices else "1"
+    for what, x, dtype in (("psi", psi, torch.complex64),
                            ("probe", probe, torch.complex64),
                            ("scan", scan, torch.float32)):
         if not isinstance(x, torch.Tensor):
             raise TypeError(
-                f"intensity: {name} must be a torch device tensor, not "
+                f"{name}: {what} must be a torch device tensor, not "
                 f"{type(x).__name__} (host arrays take part in no autograd "
                 "graph)")
         if x.dtype != dtype:
-            raise TypeError(f"intensity: {name} must be {dtype}, not {x.dtype}")
-    if psi.ndim != 3 or probe.ndim != 5 or scan.ndim != 2 or scan.shape[1] != 2:
+            raise TypeError(f"{name}: {what} must be {dtype}, not {x.dtype}")
+    if (psi.ndim != 3 or probe.ndim != 5 or scan.ndim != 2
+            or scan.shape[1] != 2 or (slices and psi.shape[0] < 1)):
         raise ValueError(
-            "intensity: psi (1, H, W), probe (1, 1, S, pw, pw) and scan "
+            f"{name}: psi ({depth}, H, W), probe (1, 1, S, pw, pw) and scan "
             f"(N, 2) expected; got {tuple(psi.shape)}, {tuple(probe.shape)}, "
             f"{tuple(scan.shape)}")
-    if psi.shape[0] > 1:
+    if psi.shape[0] > 1 and not slices:
         raise NotImplementedError(
             f"intensity with several slices (psi.shape[0] = {psi.shape[0]}): "
-            "a differentiable multislice model is not implemented")
+            "multislice_intensity is the differentiable model of a "
+            "multislice object")
     if probe.shape[0] != 1:
         raise NotImplementedError(
-            f"intensity with a probe per position (probe.shape[0] = "
+            f"{name} with a probe per position (probe.shape[0] = "
             f"{probe.shape[0]}): varying and eigen probes are not implemented")
     pw, det = operator.probe_shape, operator.detector_shape
     if probe.shape[1] != 1 or tuple(probe.shape[-2:]) != (pw, pw):
         raise ValueError(
-            f"intensity: probe must be (1, 1, S, {pw}, {pw}) for this "
+            f"{name}: probe must be (1, 1, S, {pw}, {pw}) for this "
             f"operator, not {tuple(probe.shape)}")
     if tuple(psi.shape[-2:]) != (operator.nz, operator.n):
         raise ValueError(
-            f"intensity: psi must be (1, {operator.nz}, {operator.n}) for "
+            f"{name}: psi must be ({depth}, {operator.nz}, {operator.n}) for "
             f"this operator, not {tuple(psi.shape)}")
+    Multislice.check_slice_shapes(psi.shape[0], det, pw)
     fly = int(fly)
     if fly < 1 or scan.shape[0] % fly:
         raise ValueError(
             f"{scan.shape[0]} scan positions are not a multiple of fly={fly}")
     if probe.shape[2] > MAX_MODES:
         raise ValueError(
-            f"intensity: {probe.shape[2]} probe modes; the gradient kernels "
+            f"{name}: {probe.shape[2]} probe modes; the gradient kernels "
             f"take at most {MAX_MODES}")
     if check_positions and scan.shape[0]:
         # (the fused scatter drops what falls outside the object)
         from .ptycho.position import check_allowed_positions
         check_allowed_positions(scan, psi, probe.shape)
-    for name, x in (("psi", psi), ("probe", probe), ("scan", scan)):
+    for what, x in (("psi", psi), ("probe", probe), ("scan", scan)):
         if x.device.type != "cuda":
             raise TypeError(
-                f"intensity: {name} lives on {x.device}; tike_amd runs on the "
+                f"{name}: {what} lives on {x.device}; tike_amd runs on the "
                 "GPU only and there is no CPU fallback")
     return fly
 
@@ -216,3 +259,322 @@ def intensity(operator, psi, probe, scan, *, fly=1, check_positions=True):
     """
     fly = _checked(operator, psi, probe, scan, fly, check_positions)
     return _Intensity.apply(psi, probe, scan, operator, fly)
+
+
+# ------------------------------------------------------------ several slices
+PASS1_TAKES_TABLE = True
+"""Fused route: the upstream gradient is applied by `tike_ifft2_pass1_scaled`
+while inverse pass 1 loads the far plane (its hand-off is that of
+`tike_fft2_pass1(inverse)`: the same pass-1 engine behind another load).
+False: `tike_farplane_scale` + `tike_fft2_pass1`, two launches and one more
+trip of the far plane through memory; the tests compare the two."""
+
+
+def _cgrad():
+    """cgrad's MODULE, whose levers choose the route (the package exports the
+    solver function under the module's name)."""
+    return importlib.import_module(__package__ + ".ptycho.solvers.cgrad")
+
+
+def _fused_route(op, probe):
+    """True: the two-pass kernels; as `cgrad` chooses."""
+    cgrad = _cgrad()
+    return bool(cgrad.MULTISLICE_FUSED and fused_slices(
+        probe.shape[-1], op.detector_shape, probe.shape[-3]))
+
+
+def _slices_chunk(op, psi, probe, fly, fused):
+    """Positions per chunk, whole frames.  Fused route: far + mid + D - 1 sets
+    of incident probes + the D objproj planes (D / S of a set, rounded up)
+    within half the free HBM, as `cgrad` sizes its multislice chunks."""
+    from .ptycho.solvers import lstsq
+    D, S, det = psi.shape[0], probe.shape[-3], op.detector_shape
+    if lstsq.CHUNK_POSITIONS_OVERRIDE or not fused:
+        chunk = lstsq.chunk_positions(S, det)
+    else:
+        chunk = chunk_within_hbm(lstsq._workspace(op), psi.device,
+                                 D + 1 + -(-D // S), S, det)
+    return max(1, chunk // fly) * fly
+
+
+def _fused_buffers(op, psi, probe, nmax):
+    """(far, mid, beams, objproj (D, nmax, pw, pw)) from the operator's
+    workspace -- the buffers `cgrad` uses for a multislice minibatch."""
+    from .ptycho.solvers.lstsq import _workspace
+    ws, dev, D = _workspace(op), psi.device, psi.shape[0]
+    S, pw, det = probe.shape[-3], probe.shape[-1], op.detector_shape
+    c64 = torch.complex64
+    return (ws.get("ms_far", (nmax, S, det, det), c64, dev),
+            ws.get("ms_mid", (nmax, S, det, det), c64, dev),
+            ws.get("ms_beams", (max(D - 1, 1), nmax, S, pw, pw), c64, dev),
+            ws.get("ms_objproj", (D, nmax, pw, pw), c64, dev))
+
+
+def _fused_far(op, psi, sc, probe, far, beams):
+    """The far plane of a chunk in `far[:n]`, the probes incident on the
+    slices behind the first in `beams[:, :n]`."""
+    n, S, det = sc.shape[0], probe.shape[-3], op.detector_shape
+    fwd_scale, inv_scale = fft_scales(det, op.norm)
+    prop = op.diffraction.propagation._propagator((det, det), psi.device)
+    fused_forward(psi, sc, probe, 0, far[:n], beams, prop,
+                  fwd_scale * inv_scale)
+    check(
+        lib.tike_fft2_pass2_inplace(A.ptr(far), n * S, det, 0, fwd_scale,
+                                    A.stream_ptr()),
+        "multislice_intensity: far field")
+    return far[:n]
+
+
+def _general_far(op, psi, sc, probe):
+    """(far (n, S, det, det), [the probe incident on every slice]) through
+    the general operators."""
+    conv, fresnel = op.diffraction.diffraction, op.diffraction.propagation
+    beams = [probe[0]]  # (1, S, pw, pw), then (n, S, pw, pw)
+    for d in range(psi.shape[0]):
+        wave = conv.fwd(psi=psi[d], scan=sc, probe=beams[d])
+        if d + 1 < psi.shape[0]:
+            beams.append(fresnel.fwd(wave, overwrite=True))
+    return op.propagation.fwd(wave, overwrite=True), beams
+
+
+def _fused_back(op, psi, sc, probe, table, fly, bufs, want, acc, gprobe):
+    """One chunk of the backward on the two-pass kernels: the launches of
+    cgrad's `_multislice_chunk_fused` with the upstream gradient for the cost
+    kernel and F^H for the last transform's inverse.  Leaves objproj_d in
+    bufs[3][d, :n] when the object or the positions want it."""
+    cgrad = _cgrad()
+    want_psi, want_probe, want_scan = want
+    D, (H, W) = psi.shape[0], psi.shape[-2:]
+    n, S, det = sc.shape[0], probe.shape[-3], op.detector_shape
+    far, mid, beams, objproj = bufs
+    need_proj = want_psi or want_scan
+    st = A.stream_ptr()
+    fwd_scale, inv_scale = fft_scales(det, op.norm)
+    prop = op.diffraction.propagation._propagator((det, det), psi.device)
+    far = _fused_far(op, psi, sc, probe, far, beams)
+    mid = mid[:n]
+    if PASS1_TAKES_TABLE:
+        # S * fly planes share a frame's table
+        check(
+            lib.tike_ifft2_pass1_scaled(A.ptr(far), A.ptr(table), None, None,
+                                        S * fly, A.ptr(mid), n * S, det, st),
+            "multislice_intensity backward (upstream gradient + inverse "
+            "pass 1)")
+    else:
+        check(
+            lib.tike_farplane_scale(A.ptr(far), A.ptr(table), n // fly,
+                                    S * fly, det * det, 1.0, st),
+            "multislice_intensity backward (upstream gradient)")
+        check(lib.tike_fft2_pass1(A.ptr(far), A.ptr(mid), n * S, det, 1, st),
+              "multislice_intensity backward (inverse pass 1)")
+    # the pass 2 behind it finishes F^H: the FORWARD scale, and the 2 of G
+    scale = 2.0 * fwd_scale
+    one_launch = cgrad.MULTISLICE_STEP_BACK_FUSED and det in (128, 256)
+    for d in range(D - 1, 0, -1):
+        beam = beams[d - 1, :n]
+        proj = objproj[d, :n] if need_proj else None
+        if one_launch:
+            check(
+                lib.tike_slice_step_back(A.ptr(mid), A.ptr(psi[d]), A.ptr(sc),
+                                         A.ptr(beam), A.ptr(proj), A.ptr(far),
+                                         n, S, det, H, W, scale, st),
+                "multislice_intensity backward (step back through a slice)")
+        else:
+            # (objproj is an output of this entry on every call)
+            check(
+                lib.tike_ifft2_pass2_products(
+                    A.ptr(mid), A.ptr(psi[d]), A.ptr(sc), A.ptr(beam), 1,
+                    A.ptr(objproj[d, :n]), None, 1.0, None, 1, n, S, det, H,
+                    W, scale, st),
+                "multislice_intensity backward (inverse pass 2 + object "
+                "projection)")
+            # (beam d - 1 is dead from here on: it takes conj(patch) x wave)
+            check(
+                lib.tike_conv_adj_probe(A.ptr(mid), A.ptr(sc), A.ptr(psi[d]),
+                                        A.ptr(beam), n, S, det, det, H, W, st),
+                "multislice_intensity backward (conj(patch) x wave)")
+            check(lib.tike_fft2_pass1(A.ptr(beam), A.ptr(far), n * S, det, 0,
+                                      st),
+                  "multislice_intensity backward (step back, pass 1)")
+        if want_psi:
+            check(
+                lib.tike_scatter_patches(A.ptr(proj), A.ptr(sc),
+                                         A.ptr(acc[d]), n, det, H, W, st),
+                "multislice_intensity backward (object gradient of a slice)")
+        check(
+            lib.tike_fresnel_colpass(A.ptr(far), A.ptr(prop), 1, A.ptr(mid),
+                                     n * S, det, fwd_scale, st),
+            "multislice_intensity backward (adjoint Fresnel step)")
+        scale = inv_scale
+    check(
+        lib.tike_ifft2_pass2_products(
+            A.ptr(mid), A.ptr(psi[0]), A.ptr(sc), A.ptr(probe), 0,
+            A.ptr(objproj[0, :n]), A.ptr(gprobe), 1.0, None, 0, n, S, det, H,
+            W, scale, st),
+        "multislice_intensity backward (first slice: both products)")
+    if want_psi:
+        check(
+            lib.tike_scatter_patches(A.ptr(objproj[0, :n]), A.ptr(sc),
+                                     A.ptr(acc[0]), n, det, H, W, st),
+            "multislice_intensity backward (object gradient of the first "
+            "slice)")
+
+
+def _general_back(op, psi, sc, probe, table, fly, objproj, want, acc, gprobe):
+    """One chunk of the backward through the general operators, as cgrad's
+    `_multislice_chunk_general` walks back; objproj (D, nmax, pw, pw) or
+    None."""
+    want_psi, want_probe, want_scan = want
+    D, (H, W) = psi.shape[0], psi.shape[-2:]
+    n, S, det = sc.shape[0], probe.shape[-3], op.detector_shape
+    conv, fresnel = op.diffraction.diffraction, op.diffraction.propagation
+    need_proj = want_psi or want_scan
+    st = A.stream_ptr()
+    far, beams = _general_far(op, psi, sc, probe)
+    check(
+        lib.tike_farplane_scale(A.ptr(far), A.ptr(table), n // fly, S * fly,
+                                det * det, 2.0, st),
+        "multislice_intensity backward (upstream gradient)")
+    # F^H: the unscaled inverse x the FORWARD scale, in place
+    check(
+        lib.tike_fft2(A.ptr(far), A.ptr(far), n * S, det, 1,
+                      fft_scales(det, op.norm)[0], st),
+        "multislice_intensity backward (F^H)")
+    wave = far
+    for d in range(D - 1, 0, -1):
+        if need_proj:
+            # the incident probes as the varying probe of all S modes: every
+            # mode is read from `unique_probe`, the other probe operands are
+            # placeholders that are never dereferenced for a mode below S
+            check(
+                lib.tike_lstsq_gradients(
+                    A.ptr(wave), A.ptr(sc), A.ptr(psi[d]), A.ptr(beams[d]),
+                    A.ptr(beams[d]), A.ptr(sc), 0, S, A.ptr(beams[d]), None,
+                    None, A.ptr(objproj[d, :n]), n, S, det, H, W, st),
+                "multislice_intensity backward (object projection of a "
+                "slice)")
+        if want_psi:
+            check(
+                lib.tike_scatter_patches(A.ptr(objproj[d, :n]), A.ptr(sc),
+                                         A.ptr(acc[d]), n, det, H, W, st),
+                "multislice_intensity backward (object gradient of a slice)")
+        wave = fresnel.adj(conv.adj_probe(nearplane=wave, scan=sc, psi=psi[d]),
+                           overwrite=True)
+    check(
+        lib.tike_lstsq_gradients(A.ptr(wave), A.ptr(sc), A.ptr(psi[0]),
+                                 A.ptr(probe), None, None, 0, 0, None, None,
+                                 A.ptr(gprobe),
+                                 A.ptr(objproj[0, :n]) if need_proj else None,
+                                 n, S, det, H, W, st),
+        "multislice_intensity backward (first slice: both products)")
+    if want_psi:
+        check(
+            lib.tike_scatter_patches(A.ptr(objproj[0, :n]), A.ptr(sc),
+                                     A.ptr(acc[0]), n, det, H, W, st),
+            "multislice_intensity backward (object gradient of the first "
+            "slice)")
+
+
+class _MultisliceIntensity(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, psi, probe, scan, operator, fly):
+        psi, probe, scan = (x.detach().contiguous() for x in (psi, probe, scan))
+        ctx.operator, ctx.fly = operator, fly
+        ctx.save_for_backward(psi, probe, scan)
+        A.current_device()  # (hands the library its deterministic-mode scratch)
+        op = operator
+        N, S, det = scan.shape[0], probe.shape[2], op.detector_shape
+        inten = torch.empty((N // fly, det, det), dtype=torch.float32,
+                            device=psi.device)
+        if N == 0:
+            return inten
+        fused = _fused_route(op, probe)
+        chunk = _slices_chunk(op, psi, probe, fly, fused)
+        if fused:
+            far_all, _, beams, _ = _fused_buffers(op, psi, probe,
+                                                  min(chunk, N))
+        for lo in range(0, N, chunk):
+            hi = min(N, lo + chunk)
+            sc = scan[lo:hi]
+            far = (_fused_far(op, psi, sc, probe, far_all, beams) if fused
+                   else _general_far(op, psi, sc, probe)[0])
+            # the S * fly planes of a frame are adjacent
+            check(
+                lib.tike_intensity(A.ptr(far), A.ptr(inten[lo // fly:]),
+                                   (hi - lo) // fly, S * fly, det * det,
+                                   A.stream_ptr()),
+                "multislice_intensity")
+        return inten
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        psi, probe, scan = ctx.saved_tensors
+        op, fly = ctx.operator, ctx.fly
+        want = want_psi, want_probe, want_scan = ctx.needs_input_grad[:3]
+        D, (H, W) = psi.shape[0], psi.shape[-2:]
+        N, pw = scan.shape[0], op.probe_shape
+        dev = psi.device
+        g = g.to(torch.float32).contiguous()
+        acc = (torch.zeros((D, 2, H, W), dtype=torch.float32, device=dev)
+               if want_psi else None)
+        gprobe = torch.zeros_like(probe) if want_probe else None
+        gscan = torch.empty_like(scan) if want_scan else None
+        fused = _fused_route(op, probe)
+        chunk = _slices_chunk(op, psi, probe, fly, fused)
+        nmax = min(chunk, N)
+        if fused:
+            bufs = _fused_buffers(op, psi, probe, max(nmax, 1))
+            objproj = bufs[3]
+        else:
+            objproj = (torch.empty((D, nmax, pw, pw), dtype=torch.complex64,
+                                   device=dev)
+                       if want_psi or want_scan else None)
+        for lo in range(0, N, chunk):
+            hi = min(N, lo + chunk)
+            sc, table = scan[lo:hi], g[lo // fly:hi // fly]
+            if fused:
+                _fused_back(op, psi, sc, probe, table, fly, bufs, want, acc,
+                            gprobe)
+            else:
+                _general_back(op, psi, sc, probe, table, fly, objproj, want,
+                              acc, gprobe)
+            if want_scan:
+                check(
+                    lib.tike_scan_gradient_slices(
+                        A.ptr(objproj), nmax * pw * pw, A.ptr(sc), A.ptr(psi),
+                        A.ptr(gscan[lo:hi]), hi - lo, D, pw, H, W,
+                        A.stream_ptr()),
+                    "multislice_intensity backward (scan gradient)")
+        gpsi = torch.complex(acc[:, 0], acc[:, 1]) if want_psi else None
+        return gpsi, gprobe, gscan, None, None
+
+
+def multislice_intensity(operator, psi, probe, scan, *, fly=1,
+                         check_positions=True):
+    """`intensity` for an object of D >= 1 slices: the diffraction intensities
+    (N // fly, det, det) float32 behind the last slice of psi (D, H, W)
+    complex64 -- e_d = patch_n(psi[d]) x beam_d, beam_0 = the probe,
+    beam_{d+1} = the operator's Fresnel step of e_d, far = F e_{D-1} -- summed
+    over the modes and the `fly` positions of a frame, differentiable with
+    respect to whichever of psi, probe (1, 1, S, pw, pw) complex64 and scan
+    (N, 2) float32 -- device tensors -- requires a gradient.  psi.grad is
+    (D, H, W): the exact gradient of every slice, not divided by D.  The
+    operator is an entered `tike_amd.operators.Ptycho` with probe_shape ==
+    detector_shape and its optics set (probe_wavelength, probe_FOV_lengths,
+    multislice_propagation_distance); its `norm` is honoured.  One slice goes
+    through `intensity` itself.  Once differentiable.
+
+    Raises TypeError for host arrays or other dtypes, ValueError for other
+    ranks or shapes, for several slices with probe_shape != detector_shape,
+    when N is no multiple of `fly`, for more than `MAX_MODES` modes (more than
+    8 at 128^2, 256^2 and 512^2 take the general route) and -- with
+    check_positions -- for positions that `check_allowed_positions` refuses,
+    NotImplementedError for a probe per position.
+    """
+    fly = _checked(operator, psi, probe, scan, fly, check_positions,
+                   name="multislice_intensity", slices=True)
+    if psi.shape[0] == 1:
+        return _Intensity.apply(psi, probe, scan, operator, fly)
+    return _MultisliceIntensity.apply(psi, probe, scan, operator, fly)
