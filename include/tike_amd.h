@@ -38,7 +38,7 @@ extern "C" {
  * A binding compares tike_abi_version() of the loaded library with the
  * TIKE_ABI_VERSION it was written against before its first call
  * (tike_amd/_lib.py does; INTEGRATION.md shows the check). */
-#define TIKE_ABI_VERSION 20
+#define TIKE_ABI_VERSION 21
 
 /* sha256 (64 hex digits) of the sources the library was built from: the PMC
  * traffic files under profiles/ carry it, and bench.py withholds a traffic
@@ -1248,6 +1248,47 @@ int tike_scan_gradient(const void* objproj, const float* scan, const void* psi, 
 int tike_scan_gradient_slices(const void* objproj, long slice_stride, const float* scan,
                               const void* psi, float* grad, long nscan, int D, int pw, int H,
                               int W, void* stream);
+
+/* ---- the backward of the differentiable intensity model with a varying
+ * probe (tike_amd/autograd.py; no reference counterpart: the reference updates
+ * eigen probes and their weights by a heuristic and differentiates neither).
+ * The probe at position n is that of probe.py:272-303 (get_varying_probe),
+ *   P[n][s] = w[n][0][s] probe[s] + sum_c w[n][c+1][s] eigen[c][s]    s < M
+ *   P[n][s] = w[n][0][s] probe[s]                                      s >= M
+ * with C = num_eigen, M = eigen_modes (M is taken as 0 when C is 0, and
+ * eigen_probe may then be NULL).  chi (nscan,S,pw,pw) c64 is the gradient
+ * that reaches the exit waves (tike_ifft2_crop*), scan (nscan,2) f32, psi
+ * (H,W) c64, probe (S,pw,pw) c64, eigen_probe (C,M,pw,pw) c64, eigen_weights
+ * (nscan,C+1,S) f32.  With q[n][s] = conj(patch_n(psi)) chi[n][s], the patch
+ * gathered as tike_lstsq_gradients gathers it (a pixel outside the object
+ * counts as zero; nothing outside the arrays is read for any position):
+ *   probe_grad (S,pw,pw) c64          += sum_n w[n][0][s] q[n][s]
+ *   eigen_grad (C,M,pw,pw) c64        += sum_n w[n][c+1][s] q[n][s]
+ *   weights_grad (nscan,C+1,S) f32     = sum_px Re(conj(probe[s]) q[n][s])  row 0
+ *                                      = sum_px Re(conj(eigen[c][s]) q[n][s]) row c+1,
+ *                                        s < M; exactly 0 for s >= M
+ *   objproj (nscan,pw,pw) c64          = sum_s conj(P[n][s]) chi[n][s]
+ * -- PyTorch's convention for the gradient of a real loss.  Every output may
+ * be NULL; with all four NULL nothing is launched.  chi is read ONCE for all
+ * of them.  The plane sums are float32 in registers over a chunk of positions
+ * and one float atomic pair per (pixel, plane, chunk); in deterministic mode
+ * (tike_set_deterministic) the chunks' sums are added in chunk order.  The
+ * weight sums have float32 products and float64 sums in a fixed order (lanes,
+ * waves, pixel tiles of 256 pixels ascending), rounded once: no atomics, two
+ * calls give the same bits in either mode.  The partial sums of the tiles go
+ * through `work`, caller-owned device memory of at least
+ *   8 * ceil(pw * pw / 256) * nscan * (S + C * M)   bytes,
+ * needed only when weights_grad is not NULL.  No allocation.
+ * TIKE_ERR_UNSUPPORTED for S > 16 or C * M > 16; TIKE_ERR_ARG for a NULL
+ * input, weights_grad without work, negative counts, M < 1 or M > S with
+ * C > 0, eigen_probe NULL with C > 0, or more workgroups than one launch
+ * holds; nscan == 0 returns 0 without a launch. */
+int tike_eigen_probe_gradients(const void* chi, const float* scan, const void* psi,
+                               const void* probe, const void* eigen_probe,
+                               const float* eigen_weights, int num_eigen, int eigen_modes,
+                               void* probe_grad, void* eigen_grad, float* weights_grad,
+                               void* objproj, void* work, long nscan, int S, int pw, int H,
+                               int W, void* stream);
 
 /* ---- collectives: the per-minibatch gradient all-reduce over RCCL / xGMI,
  * one process (or thread) per GPU.  Replaces the serial peer-copy reduction of

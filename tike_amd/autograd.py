@@ -35,6 +35,25 @@ most one chunk of far plane is ever resident:
 No torch arithmetic on that path: views, allocation and the final
 planar-to-complex conversion of the object gradient only.
 
+``intensity(..., eigen_probe=E, eigen_weights=w)`` is the same with the
+varying probe of the reference's `get_varying_probe` (probe.py:272-303), E
+(1, C, M, pw, pw), w (N, C + 1, S), weights per POSITION (any `fly`):
+
+    P[n,s] = w[n,0,s] probe[s] + sum_c w[n,c+1,s] E[c,s]    s < M
+    P[n,s] = w[n,0,s] probe[s]                               s >= M
+
+Backward, with chi as above (far from P) and q[n,s] = conj(patch_n) chi[n,s]:
+
+    probe.grad[s]      = sum_n w[n,0,s]   q[n,s]
+    E.grad[c,s]        = sum_n w[n,c+1,s] q[n,s]                   s < M
+    w.grad[n,0,s]      = sum_px Re(conj(probe[s]) q[n,s])
+    w.grad[n,c+1,s]    = sum_px Re(conj(E[c,s])   q[n,s])          s < M; 0 else
+    objproj[n]         = sum_s conj(P[n,s]) chi[n,s]   -> psi.grad, scan.grad
+
+all five from ONE pass over chi, `tike_eigen_probe_gradients` in the place of
+`tike_lstsq_gradients`; the other launches are unchanged, and without
+eigen_weights nothing changes at all.
+
 ``multislice_intensity(operator, psi, probe, scan, fly=...)`` is the same for
 an object of D slices (probe window = detector): e_d = patch_n(O_d) beam_d,
 beam_0 = the probe, beam_{d+1} = Fresnel(e_d), far = F e_{D-1}.  Backward, the
@@ -81,19 +100,33 @@ from .operators.propagation import fft_scales
 MAX_MODES = 16
 """Probe modes `tike_lstsq_gradients` takes (TK_MAX_MODES)."""
 
+MAX_EIGEN_PLANES = 16
+"""Eigen planes C * M (eigen probes x the modes that own them)
+`tike_eigen_probe_gradients` takes."""
+
 _SCALED_INVERSE_SIZES = (128, 256, 512)
 """Detector sizes of `tike_ifft2_crop_scaled`."""
 
 
 def _checked(operator, psi, probe, scan, fly, check_positions,
-             name="intensity", slices=False):
+             name="intensity", slices=False, eigen_probe=None,
+             eigen_weights=None):
     """Every refusal, in an order that needs no device until the last one.
     slices: `multislice_intensity` -- any number of slices, whose shapes
-    `Multislice.check_slice_shapes` judges."""
+    `Multislice.check_slice_shapes` judges.  eigen_probe, eigen_weights: the
+    varying probe of `intensity`."""
     depth = "D" if slices else "1"
-    for what, x, dtype in (("psi", psi, torch.complex64),
-                           ("probe", probe, torch.complex64),
-                           ("scan", scan, torch.float32)):
+    if eigen_probe is not None and eigen_weights is None:
+        raise ValueError(
+            f"{name}: eigen_probe without eigen_weights (the weights say how "
+            "much of every eigen probe a position sees)")
+    given = [("psi", psi, torch.complex64), ("probe", probe, torch.complex64),
+             ("scan", scan, torch.float32)]
+    if eigen_probe is not None:
+        given.append(("eigen_probe", eigen_probe, torch.complex64))
+    if eigen_weights is not None:
+        given.append(("eigen_weights", eigen_weights, torch.float32))
+    for what, x, dtype in given:
         if not isinstance(x, torch.Tensor):
             raise TypeError(
                 f"{name}: {what} must be a torch device tensor, not "
@@ -115,7 +148,9 @@ def _checked(operator, psi, probe, scan, fly, check_positions,
     if probe.shape[0] != 1:
         raise NotImplementedError(
             f"{name} with a probe per position (probe.shape[0] = "
-            f"{probe.shape[0]}): varying and eigen probes are not implemented")
+            f"{probe.shape[0]}): a probe tensor per position is not "
+            "implemented; intensity(..., eigen_probe=, eigen_weights=) is the "
+            "varying probe of shared probe + weighted eigen probes")
     pw, det = operator.probe_shape, operator.detector_shape
     if probe.shape[1] != 1 or tuple(probe.shape[-2:]) != (pw, pw):
         raise ValueError(
@@ -134,11 +169,38 @@ def _checked(operator, psi, probe, scan, fly, check_positions,
         raise ValueError(
             f"{name}: {probe.shape[2]} probe modes; the gradient kernels "
             f"take at most {MAX_MODES}")
+    if eigen_weights is not None:
+        N, S = scan.shape[0], probe.shape[2]
+        if eigen_weights.ndim != 3 or (eigen_probe is not None
+                                       and eigen_probe.ndim != 5):
+            raise ValueError(
+                f"{name}: eigen_weights (N, C + 1, S) and eigen_probe "
+                f"(1, C, M, pw, pw) expected; got "
+                f"{tuple(eigen_weights.shape)}"
+                + ("" if eigen_probe is None else
+                   f", {tuple(eigen_probe.shape)}"))
+        C, M = (0, 0) if eigen_probe is None else eigen_probe.shape[1:3]
+        if eigen_probe is not None and (
+                eigen_probe.shape[0] != 1 or C < 1 or not 1 <= M <= S
+                or tuple(eigen_probe.shape[-2:]) != (pw, pw)):
+            raise ValueError(
+                f"{name}: eigen_probe must be (1, C, M, {pw}, {pw}) with "
+                f"C >= 1 and 1 <= M <= S = {S} for this probe, not "
+                f"{tuple(eigen_probe.shape)}")
+        if tuple(eigen_weights.shape) != (N, C + 1, S):
+            raise ValueError(
+                f"{name}: eigen_weights must be (N, C + 1, S) = ({N}, "
+                f"{C + 1}, {S}) for these positions, eigen probes and modes, "
+                f"not {tuple(eigen_weights.shape)}")
+        if C * M > MAX_EIGEN_PLANES:
+            raise ValueError(
+                f"{name}: {C} eigen probes on {M} modes are {C * M} planes; "
+                f"the gradient kernel takes at most {MAX_EIGEN_PLANES}")
     if check_positions and scan.shape[0]:
         # (the fused scatter drops what falls outside the object)
         from .ptycho.position import check_allowed_positions
         check_allowed_positions(scan, psi, probe.shape)
-    for what, x in (("psi", psi), ("probe", probe), ("scan", scan)):
+    for what, x, _ in given:
         if x.device.type != "cuda":
             raise TypeError(
                 f"{name}: {what} lives on {x.device}; tike_amd runs on the "
@@ -240,25 +302,157 @@ class _Intensity(torch.autograd.Function):
         return gpsi, gprobe, gscan, None, None
 
 
-def intensity(operator, psi, probe, scan, *, fly=1, check_positions=True):
+class _EigenIntensity(torch.autograd.Function):
+    """`_Intensity` with the varying probe of eigen_probe (or None: C = 0) and
+    eigen_weights; the backward swaps tike_lstsq_gradients for
+    tike_eigen_probe_gradients."""
+
+    @staticmethod
+    def forward(ctx, psi, probe, scan, eigen_probe, eigen_weights, operator,
+                fly):
+        from .ptycho.ptycho import _intensity_chunks
+        psi, probe, scan, eigen_weights = (
+            x.detach().contiguous()
+            for x in (psi, probe, scan, eigen_weights))
+        if eigen_probe is not None:
+            eigen_probe = eigen_probe.detach().contiguous()
+        ctx.operator, ctx.fly = operator, fly
+        ctx.eigen = eigen_probe is not None
+        ctx.save_for_backward(psi, probe, scan, eigen_weights,
+                              *((eigen_probe,) if ctx.eigen else ()))
+        A.current_device()  # (hands the library its deterministic-mode scratch)
+        det = operator.detector_shape
+        if scan.shape[0] == 0:
+            return torch.empty((0, det, det), dtype=torch.float32,
+                               device=psi.device)
+        frames = [inten for _, _, inten in _intensity_chunks(
+            operator, psi, scan, probe, eigen_probe, eigen_weights, fly=fly)]
+        return frames[0] if len(frames) == 1 else torch.cat(frames)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from .ptycho.solvers.lstsq import _workspace, chunk_positions
+        psi, probe, scan, weights = ctx.saved_tensors[:4]
+        eigen = ctx.saved_tensors[4] if ctx.eigen else None
+        op, fly = ctx.operator, ctx.fly
+        (want_psi, want_probe, want_scan, want_eigen,
+         want_weights) = ctx.needs_input_grad[:5]
+        want_eigen = want_eigen and ctx.eigen
+        N, S = scan.shape[0], probe.shape[2]
+        C, M = eigen.shape[1:3] if ctx.eigen else (0, 0)
+        pw, det = op.probe_shape, op.detector_shape
+        H, W = psi.shape[-2:]
+        dev = psi.device
+        g = g.to(torch.float32).contiguous()
+        st = A.stream_ptr()
+        # F^H = the unscaled inverse x the forward scale; the 2 of G goes along
+        scale = 2.0 * fft_scales(det, op.norm)[0]
+        scaled_inverse = det in _SCALED_INVERSE_SIZES
+        acc = (torch.zeros((2, H, W), dtype=torch.float32, device=dev)
+               if want_psi else None)
+        gprobe = torch.zeros_like(probe) if want_probe else None
+        geigen = torch.zeros_like(eigen) if want_eigen else None
+        gweights = torch.empty_like(weights) if want_weights else None
+        gscan = torch.empty_like(scan) if want_scan else None
+        chunk = max(1, chunk_positions(S, det) // fly) * fly  # whole frames
+        rows = min(chunk, N)
+        far_all = torch.empty((rows, 1, S, det, det), dtype=torch.complex64,
+                              device=dev)
+        # (the scaled inverse must not work in place; the plain one may)
+        mid_all = torch.empty_like(far_all) if scaled_inverse else far_all
+        chi_all = mid_all if pw == det else torch.empty(
+            (rows, 1, S, pw, pw), dtype=torch.complex64, device=dev)
+        need_proj = want_psi or want_scan
+        objproj_all = (torch.empty((rows, pw, pw), dtype=torch.complex64,
+                                   device=dev) if need_proj else None)
+        # the pixel tiles' partial weight sums (include/tike_amd.h): float64
+        work = (_workspace(op).get(
+            "eigen_gradients_work",
+            (-(-pw * pw // 256), max(rows, 1), S + C * M), torch.float64, dev)
+                if want_weights else None)
+        for lo in range(0, N, chunk):
+            hi = min(N, lo + chunk)
+            n = hi - lo
+            sc, w = scan[lo:hi], weights[lo:hi]
+            far, mid, chi = far_all[:n], mid_all[:n], chi_all[:n]
+            table = g[lo // fly:hi // fly]
+            op.fwd_device(probe, sc, psi, eigen, w, out=far)
+            if scaled_inverse:
+                # S * fly planes share a frame's table
+                check(
+                    lib.tike_ifft2_crop_scaled(A.ptr(far), A.ptr(table),
+                                               S * fly, A.ptr(mid), A.ptr(chi),
+                                               n * S, det, pw, scale, st),
+                    "intensity backward (scaled ifft2 + crop)")
+            else:
+                check(
+                    lib.tike_farplane_scale(A.ptr(far), A.ptr(table), n // fly,
+                                            S * fly, det * det, 2.0, st),
+                    "intensity backward (upstream gradient)")
+                check(
+                    lib.tike_ifft2_crop(A.ptr(far), A.ptr(mid), A.ptr(chi),
+                                        n * S, det, pw, 0.5 * scale, st),
+                    "intensity backward (ifft2 + crop)")
+            objproj = objproj_all[:n] if need_proj else None
+            check(
+                lib.tike_eigen_probe_gradients(
+                    A.ptr(chi), A.ptr(sc), A.ptr(psi), A.ptr(probe),
+                    A.ptr(eigen), A.ptr(w), C, M, A.ptr(gprobe),
+                    A.ptr(geigen),
+                    A.ptr(gweights[lo:hi]) if want_weights else None,
+                    A.ptr(objproj), A.ptr(work), n, S, pw, H, W, st),
+                "intensity backward (probe, eigen probe and weight gradients "
+                "+ object projection)")
+            if want_psi:
+                check(
+                    lib.tike_scatter_patches(A.ptr(objproj), A.ptr(sc),
+                                             A.ptr(acc), n, pw, H, W, st),
+                    "intensity backward (object gradient)")
+            if want_scan:
+                check(
+                    lib.tike_scan_gradient(A.ptr(objproj), A.ptr(sc),
+                                           A.ptr(psi), A.ptr(gscan[lo:hi]), n,
+                                           pw, H, W, st),
+                    "intensity backward (scan gradient)")
+        gpsi = torch.complex(acc[0], acc[1])[None] if want_psi else None
+        return gpsi, gprobe, gscan, geigen, gweights, None, None
+
+
+def intensity(operator, psi, probe, scan, *, eigen_probe=None,
+              eigen_weights=None, fly=1, check_positions=True):
     """Diffraction intensities (N // fly, det, det) float32 of an entered
     `tike_amd.operators.Ptycho`, differentiable with respect to whichever of
-    psi (1, H, W) complex64, probe (1, 1, S, pw, pw) complex64 and scan (N, 2)
-    float32 -- device tensors -- requires a gradient.  Frame f is the sum over
-    the positions f * fly ... f * fly + fly - 1 and over the modes: the values
-    of ``operator._compute_intensity(..., fly=fly)``; the operator's `norm` is
-    honoured.  Once differentiable.
+    psi (1, H, W) complex64, probe (1, 1, S, pw, pw) complex64, scan (N, 2)
+    float32, eigen_probe (1, C, M, pw, pw) complex64 and eigen_weights
+    (N, C + 1, S) float32 -- device tensors -- requires a gradient.  Frame f
+    is the sum over the positions f * fly ... f * fly + fly - 1 and over the
+    modes: the values of ``operator._compute_intensity(..., fly=fly)``; the
+    operator's `norm` is honoured.  Once differentiable.
 
-    Raises NotImplementedError for several slices or a probe per position
-    (there are no eigen probes either), TypeError for host arrays or other
-    dtypes, ValueError when N is no multiple of `fly`, for more than
-    `MAX_MODES` modes and -- with check_positions, the default -- for positions
-    that `check_allowed_positions` refuses: the object gradient's scatter
-    drops what falls outside the object.  check_positions costs a read-back of
-    the positions per call.
+    With eigen_weights the probe varies from position to position (not from
+    frame to frame: any `fly`), as `get_varying_probe` has it: position n sees
+    w[n, 0, s] probe[s] + sum_c w[n, c + 1, s] eigen_probe[c, s] in the first
+    M <= S modes and w[n, 0, s] probe[s] in the others.  eigen_probe=None with
+    eigen_weights (N, 1, S) is C = 0: an intensity scale per position and
+    mode.  Without eigen_weights the call launches what it always launched.
+
+    Raises NotImplementedError for several slices or a probe TENSOR per
+    position, TypeError for host arrays or other dtypes, ValueError when N is
+    no multiple of `fly`, for more than `MAX_MODES` modes, for eigen_probe
+    without eigen_weights, for eigen shapes that do not fit probe and scan,
+    for more than `MAX_EIGEN_PLANES` eigen planes C * M and -- with
+    check_positions, the default -- for positions that
+    `check_allowed_positions` refuses: the object gradient's scatter drops
+    what falls outside the object.  check_positions costs a read-back of the
+    positions per call.
     """
-    fly = _checked(operator, psi, probe, scan, fly, check_positions)
-    return _Intensity.apply(psi, probe, scan, operator, fly)
+    fly = _checked(operator, psi, probe, scan, fly, check_positions,
+                   eigen_probe=eigen_probe, eigen_weights=eigen_weights)
+    if eigen_weights is None:
+        return _Intensity.apply(psi, probe, scan, operator, fly)
+    return _EigenIntensity.apply(psi, probe, scan, eigen_probe, eigen_weights,
+                                 operator, fly)
 
 
 # ------------------------------------------------------------ several slices
