@@ -38,7 +38,7 @@ extern "C" {
  * A binding compares tike_abi_version() of the loaded library with the
  * TIKE_ABI_VERSION it was written against before its first call
  * (tike_amd/_lib.py does; INTEGRATION.md shows the check). */
-#define TIKE_ABI_VERSION 21
+#define TIKE_ABI_VERSION 22
 
 /* sha256 (64 hex digits) of the sources the library was built from: the PMC
  * traffic files under profiles/ carry it, and bench.py withholds a traffic
@@ -1289,6 +1289,48 @@ int tike_eigen_probe_gradients(const void* chi, const float* scan, const void* p
                                void* probe_grad, void* eigen_grad, float* weights_grad,
                                void* objproj, void* work, long nscan, int S, int pw, int H,
                                int W, void* stream);
+
+/* ---- the forward-mode derivative (J v) of the differentiable intensity model
+ * (tike_amd/autograd.py: intensity_jvp; no reference counterpart): the tangent
+ * of the exit waves of tike_conv_fwd for tangents dpsi (H,W) c64 of the
+ * object, dscan (nscan,2) f32 of the positions and dprobe (S,pw,pw) c64 of the
+ * shared probe.  With the taps O00 ... O11, the fractions and Dy, Dx of
+ * tike_scan_gradient (the integer part of a position held fixed; a tap
+ * outside the object counts as zero):
+ *   dpatch_n      = patch_n(dpsi) + dscan[n][0] Dy_n(psi) + dscan[n][1] Dx_n(psi)
+ *   nearplane[n][s] = pad( dpatch_n probe[s] + patch_n(psi) dprobe[s] )
+ * nearplane (nscan,S,det,det) c64, overwritten: the centred pw window and the
+ * zero padding around it in the layout of tike_conv_fwd; the kernel writes
+ * the zeros itself (exactly 0.0; no memset is needed).  Any of dpsi, dscan,
+ * dprobe may be NULL: a zero tangent; with all three NULL the plane is zeros.
+ * A position's taps of psi (and of dpsi) are loaded once and serve the patch,
+ * Dy, Dx and every mode.  Products are float32; every output element has one
+ * owner, no atomics: two calls give the same bits.  Nothing outside the
+ * arrays is read for any position.  No allocation.  TIKE_ERR_ARG for a NULL
+ * psi, scan, probe or nearplane, S < 1, pw < 1, det < pw, H < 1, W < 1,
+ * nscan > 2^31 - 1 or a detector of more items than one launch holds;
+ * TIKE_ERR_UNSUPPORTED for S > 16; nscan == 0 returns 0 without a launch. */
+int tike_conv_fwd_tangent(const void* psi, const void* dpsi, const float* scan,
+                          const float* dscan, const void* probe, const void* dprobe,
+                          void* nearplane, long nscan, int S, int pw, int det, int H, int W,
+                          void* stream);
+
+/* The tangent of the intensity from a far plane and its tangent (tike_fft2 of
+ * the plane above, with the forward scale):
+ *   dintensity[f][p] = 2 sum_{j<P} Re( conj(farplane[f][j][p]) dfarplane[f][j][p] )
+ *   intensity[f][p]  = sum_{j<P} |farplane[f][j][p]|^2        (unless NULL)
+ * farplane, dfarplane (nframe,P,npix) c64, P = fly * S: the positions and
+ * modes that expose frame f; intensity, dintensity (nframe,npix) f32,
+ * overwritten.  The intensity has the bits of tike_intensity (and of
+ * tike_fly_farplane_gradient): planes ascending, a float32 running sum; the
+ * tangent is a float32 running sum of the P products, doubled.  Both far
+ * planes are read once with 16-byte accesses, the last npix % 4 pixels of a
+ * frame one per lane; any P; no atomics: two calls give the same bits.  No
+ * allocation.  TIKE_ERR_ARG for a NULL farplane, dfarplane or dintensity,
+ * P < 1, npix < 1 or more workgroups than one launch holds; nframe == 0
+ * returns 0 without a launch. */
+int tike_intensity_tangent(const void* farplane, const void* dfarplane, float* intensity,
+                           float* dintensity, long nframe, int P, long npix, void* stream);
 
 /* ---- collectives: the per-minibatch gradient all-reduce over RCCL / xGMI,
  * one process (or thread) per GPU.  Replaces the serial peer-copy reduction of

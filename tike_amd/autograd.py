@@ -85,6 +85,32 @@ for the shape (`fused_slices`; its `MULTISLICE_FUSED` and
 
 then ONE tike_scan_gradient_slices over the D objproj planes of the chunk.
 Only what `needs_input_grad` asks for is launched.
+
+Forward mode.  ``intensity_jvp(operator, psi, probe, scan, d_psi=, d_probe=,
+d_scan=, fly=...)`` returns (I, dI = J v) for tangents d_psi (1, H, W), d_probe
+(1, 1, S, pw, pw) and d_scan (N, 2) -- one slice, the shared probe, any `fly`,
+the operator's `norm`; Dy, Dx as above (`tike_scan_gradient`: the integer part
+of the position held fixed, a tap outside the object zero):
+
+    dpatch_n   = patch_n(d_psi) + d_scan[n,0] Dy_n(psi) + d_scan[n,1] Dx_n(psi)
+    dwave[n,s] = dpatch_n probe[s] + patch_n(psi) d_probe[s]
+    dfar[n,s]  = F pad(dwave[n,s])                F with its forward scale
+    dI[f]      = sum_{n in frame f} sum_s 2 Re(conj(far[n,s]) dfar[n,s])
+
+Per chunk of whole frames -- half of `chunk_positions`: the far plane and its
+tangent are both resident --
+
+    tike_ptycho_fwd -> tike_conv_fwd_tangent -> tike_fft2 (in place, forward
+    scale) -> tike_intensity_tangent (dI, and I with the bits of
+    tike_intensity)
+
+and with no tangent at all only the primal launches.  `intensity` on
+``torch.autograd.forward_ad`` dual tensors (any subset of psi, probe, scan)
+returns a dual whose tangent is this dI: `_Intensity.jvp` runs the same chunk
+loop.  The eigen-probe form and `multislice_intensity` have no forward-mode
+rule yet: under `forward_ad` they keep torch's own refusal ("you must
+implement the jvp function").  ``gauss_newton_product`` composes the two
+modes: J^T (weight * J v) by `intensity_jvp` and then the backward above.
 """
 import importlib
 
@@ -216,6 +242,7 @@ class _Intensity(torch.autograd.Function):
         psi, probe, scan = (x.detach().contiguous() for x in (psi, probe, scan))
         ctx.operator, ctx.fly = operator, fly
         ctx.save_for_backward(psi, probe, scan)
+        ctx.save_for_forward(psi, probe, scan)
         A.current_device()  # (hands the library its deterministic-mode scratch)
         det = operator.detector_shape
         if scan.shape[0] == 0:
@@ -225,6 +252,21 @@ class _Intensity(torch.autograd.Function):
         frames = [inten for _, _, inten in _intensity_chunks(
             operator, psi, scan, probe, fly=fly)]
         return frames[0] if len(frames) == 1 else torch.cat(frames)
+
+    @staticmethod
+    def jvp(ctx, d_psi, d_probe, d_scan, _operator, _fly):
+        """The tangent of the intensity under `torch.autograd.forward_ad`.
+        torch hands an input that is no dual tensor a tangent of zeros, not
+        None (None only when materialising is off), and `forward` cannot see
+        which inputs are dual.  Its terms add exact zeros -- the bits of a
+        None tangent -- but the gather then reads all three tangents: with
+        scan alone dual, `tike_conv_fwd_tangent` takes about a quarter longer
+        than under `intensity_jvp(d_scan=...)` (profiles/autograd_jvp.md)."""
+        psi, probe, scan = ctx.saved_tensors
+        tangents = [None if t is None else t.detach().contiguous()
+                    for t in (d_psi, d_probe, d_scan)]
+        return _jvp_chunks(ctx.operator, psi, probe, scan, *tangents, ctx.fly,
+                           primal=False)[1]
 
     @staticmethod
     @once_differentiable
@@ -428,7 +470,15 @@ def intensity(operator, psi, probe, scan, *, eigen_probe=None,
     (N, C + 1, S) float32 -- device tensors -- requires a gradient.  Frame f
     is the sum over the positions f * fly ... f * fly + fly - 1 and over the
     modes: the values of ``operator._compute_intensity(..., fly=fly)``; the
-    operator's `norm` is honoured.  Once differentiable.
+    operator's `norm` is honoured.  Once differentiable.  Without
+    eigen_weights it also has a forward-mode rule: on
+    `torch.autograd.forward_ad` dual tensors (any of psi, probe, scan) the
+    result is a dual with the tangent of `intensity_jvp` (torch gives the
+    inputs that are not dual a tangent of zeros, so all three tangents are
+    gathered: where only some inputs vary, `intensity_jvp` with the others
+    left None is the faster call).  The eigen-probe
+    form below and `multislice_intensity` have none: under `forward_ad` they
+    raise torch's "you must implement the jvp function".
 
     With eigen_weights the probe varies from position to position (not from
     frame to frame: any `fly`), as `get_varying_probe` has it: position n sees
@@ -453,6 +503,199 @@ def intensity(operator, psi, probe, scan, *, eigen_probe=None,
         return _Intensity.apply(psi, probe, scan, operator, fly)
     return _EigenIntensity.apply(psi, probe, scan, eigen_probe, eigen_weights,
                                  operator, fly)
+
+
+# -------------------------------------------------------------- forward mode
+def _jvp_chunks(op, psi, probe, scan, d_psi, d_probe, d_scan, fly, primal=True):
+    """(I or None, dI): the chunk loop of `intensity_jvp` and `_Intensity.jvp`
+    on contiguous device tensors; at least one tangent is not None."""
+    from .ptycho.solvers.lstsq import chunk_positions
+    N, S = scan.shape[0], probe.shape[2]
+    pw, det = op.probe_shape, op.detector_shape
+    H, W = psi.shape[-2:]
+    dev = psi.device
+    A.current_device()  # (hands the library its deterministic-mode scratch)
+    st = A.stream_ptr()
+    inten = (torch.empty((N // fly, det, det), dtype=torch.float32, device=dev)
+             if primal else None)
+    tangent = torch.empty((N // fly, det, det), dtype=torch.float32,
+                          device=dev)
+    if N == 0:
+        return inten, tangent
+    # the far plane and its tangent are both resident; whole frames
+    chunk = max(1, chunk_positions(S, det) // 2 // fly) * fly
+    rows = min(chunk, N)
+    far_all = torch.empty((rows, 1, S, det, det), dtype=torch.complex64,
+                          device=dev)
+    dfar_all = torch.empty_like(far_all)
+    fwd_scale = fft_scales(det, op.norm)[0]
+    for lo in range(0, N, chunk):
+        hi = min(N, lo + chunk)
+        n = hi - lo
+        sc = scan[lo:hi]
+        far, dfar = far_all[:n], dfar_all[:n]
+        op.fwd_device(probe, sc, psi, out=far)
+        check(
+            lib.tike_conv_fwd_tangent(
+                A.ptr(psi), A.ptr(d_psi), A.ptr(sc),
+                None if d_scan is None else A.ptr(d_scan[lo:hi]),
+                A.ptr(probe), A.ptr(d_probe), A.ptr(dfar), n, S, pw, det, H,
+                W, st), "intensity_jvp (tangent exit waves)")
+        check(lib.tike_fft2(A.ptr(dfar), A.ptr(dfar), n * S, det, 0,
+                            fwd_scale, st),
+              "intensity_jvp (tangent far plane)")
+        # the S * fly planes of a frame are adjacent
+        check(
+            lib.tike_intensity_tangent(
+                A.ptr(far), A.ptr(dfar),
+                A.ptr(inten[lo // fly:]) if primal else None,
+                A.ptr(tangent[lo // fly:]), n // fly, S * fly, det * det, st),
+            "intensity_jvp (tangent intensity)")
+    return inten, tangent
+
+
+def _checked_tangents(name, psi, probe, scan, d_psi, d_probe, d_scan):
+    """A tangent matches its primal in type, dtype, shape and device; the
+    tangents detached and contiguous (None stays None)."""
+    out = []
+    for what, x, t in (("psi", psi, d_psi), ("probe", probe, d_probe),
+                       ("scan", scan, d_scan)):
+        if t is None:
+            out.append(None)
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(
+                f"{name}: d_{what} must be a torch device tensor, not "
+                f"{type(t).__name__}")
+        if t.dtype != x.dtype:
+            raise TypeError(
+                f"{name}: d_{what} must be {x.dtype} as {what} is, not "
+                f"{t.dtype}")
+        if t.shape != x.shape:
+            raise ValueError(
+                f"{name}: d_{what} must have the shape of {what}, "
+                f"{tuple(x.shape)}, not {tuple(t.shape)}")
+        if t.device != x.device:
+            raise ValueError(
+                f"{name}: d_{what} lives on {t.device}, {what} on {x.device}")
+        out.append(t.detach().contiguous())
+    return out
+
+
+def _checked_jvp(name, operator, psi, probe, scan, d_psi, d_probe, d_scan,
+                 fly, check_positions):
+    """Every refusal of the forward-mode entries that needs no device, the
+    tangents' among them, before `_checked` asks for device tensors."""
+    tangents = None
+    if all(isinstance(x, torch.Tensor) for x in (psi, probe, scan)):
+        # (host arrays: `_checked` below names them)
+        tangents = _checked_tangents(name, psi, probe, scan, d_psi, d_probe,
+                                     d_scan)
+    fly = _checked(operator, psi, probe, scan, fly, check_positions, name=name)
+    return fly, tangents
+
+
+def intensity_jvp(operator, psi, probe, scan, *, d_psi=None, d_probe=None,
+                  d_scan=None, fly=1, check_positions=True):
+    """(I, dI): the intensities of `intensity(operator, psi, probe, scan,
+    fly=fly)` -- the same bits -- and their directional derivative J v along
+    the tangents d_psi (1, H, W) complex64, d_probe (1, 1, S, pw, pw)
+    complex64 and d_scan (N, 2) float32, each None (zero) or a device tensor
+    of its primal's shape, dtype and device.  Both (N // fly, det, det)
+    float32, outside any autograd graph.  The derivative with respect to the
+    positions is that of `scan.grad`: the integer part of a position is held
+    fixed.  One slice and the shared probe only: eigen probes are no parameter
+    of this function, and `multislice_intensity` has no forward mode yet.
+    With no tangent dI is zeros and only the primal launches.
+
+    Raises what `intensity` raises (NotImplementedError for several slices or
+    a probe per position, TypeError, ValueError), and TypeError / ValueError
+    for a tangent that does not match its primal, before any launch.
+    """
+    fly, (d_psi, d_probe, d_scan) = _checked_jvp(
+        "intensity_jvp", operator, psi, probe, scan, d_psi, d_probe, d_scan,
+        fly, check_positions)
+    psi, probe, scan = (x.detach().contiguous() for x in (psi, probe, scan))
+    if d_psi is None and d_probe is None and d_scan is None:
+        with torch.no_grad():
+            inten = _Intensity.apply(psi, probe, scan, operator, fly)
+        return inten, torch.zeros_like(inten)
+    return _jvp_chunks(operator, psi, probe, scan, d_psi, d_probe, d_scan, fly)
+
+
+_WRT = ("psi", "probe", "scan")
+
+
+def _frames(scan, fly):
+    """N // fly, or None where `_checked` is about to refuse scan or fly."""
+    try:
+        fly = int(fly)
+    except (TypeError, ValueError):
+        return None
+    if (not isinstance(scan, torch.Tensor) or scan.ndim != 2 or fly < 1
+            or scan.shape[0] % fly):
+        return None
+    return scan.shape[0] // fly
+
+
+def gauss_newton_product(operator, psi, probe, scan, *, d_psi=None,
+                         d_probe=None, d_scan=None, weight=None, fly=1,
+                         wrt=_WRT, check_positions=True):
+    """J^T (weight * J v): the Gauss-Newton (weight=None) or Fisher (weight =
+    1 / I for Poisson counts) matrix of the intensity model applied to the
+    tangents v = (d_psi, d_probe, d_scan) of `intensity_jvp`.  Returns a tuple
+    with one tensor per name in `wrt` (any of "psi", "probe", "scan", in that
+    order of `wrt`), each in the `.grad` convention of `intensity` (a complex
+    input's part is d/dRe + i d/dIm).  weight: (N // fly, det, det) float32
+    device tensor or None.
+
+    Composed of `intensity_jvp` and the backward of `intensity` with
+    weight * dI for the upstream gradient -- one forward more than a fused
+    chain would take; only what `wrt` names is launched in the backward.
+
+    Raises what `intensity_jvp` raises, ValueError for names in `wrt` other
+    than the three (or none, or one twice), TypeError / ValueError for a
+    weight of another type, dtype, shape or device.
+    """
+    name = "gauss_newton_product"
+    wrt = tuple(wrt)
+    if not wrt or len(set(wrt)) != len(wrt) or any(w not in _WRT for w in wrt):
+        raise ValueError(
+            f"{name}: wrt must name some of {_WRT}, each once; got {wrt}")
+    if weight is not None:
+        if not isinstance(weight, torch.Tensor):
+            raise TypeError(
+                f"{name}: weight must be a torch device tensor, not "
+                f"{type(weight).__name__}")
+        if weight.dtype != torch.float32:
+            raise TypeError(
+                f"{name}: weight must be torch.float32, not {weight.dtype}")
+        frames = _frames(scan, fly)
+        det = operator.detector_shape
+        if frames is not None and tuple(weight.shape) != (frames, det, det):
+            raise ValueError(
+                f"{name}: weight must be (N // fly, det, det) = ({frames}, "
+                f"{det}, {det}), not {tuple(weight.shape)}")
+        if isinstance(psi, torch.Tensor) and weight.device != psi.device:
+            raise ValueError(
+                f"{name}: weight lives on {weight.device}, psi on "
+                f"{psi.device}")
+    fly, (d_psi, d_probe, d_scan) = _checked_jvp(
+        name, operator, psi, probe, scan, d_psi, d_probe, d_scan, fly,
+        check_positions)
+    leaves = {k: x.detach().contiguous().requires_grad_(k in wrt)
+              for k, x in zip(_WRT, (psi, probe, scan))}
+    if d_psi is None and d_probe is None and d_scan is None:
+        return tuple(torch.zeros_like(leaves[k]) for k in wrt)
+    tangent = _jvp_chunks(operator, *(leaves[k].detach() for k in _WRT), d_psi,
+                          d_probe, d_scan, fly, primal=False)[1]
+    if weight is not None:
+        tangent = tangent * weight.detach()
+    with torch.enable_grad():
+        inten = _Intensity.apply(leaves["psi"], leaves["probe"],
+                                 leaves["scan"], operator, fly)
+        return torch.autograd.grad(inten, [leaves[k] for k in wrt],
+                                   grad_outputs=tangent)
 
 
 # ------------------------------------------------------------ several slices

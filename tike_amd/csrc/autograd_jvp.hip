@@ -1,0 +1,266 @@
+// The kernels of the FORWARD-mode derivative of the differentiable intensity
+// model (tike_amd/autograd.py: intensity_jvp, _Intensity.jvp): the tangent of
+// the exit waves, and the tangent of the intensity from a far plane and its
+// tangent.  Between the two, the tangent far plane comes from tike_fft2.  No
+// reference counterpart: the reference has no derivative of its forward model
+// in any direction but its hand-written adjoints.
+//
+//   tike_conv_fwd_tangent   dwave[n][s] = pad( dpatch_n probe[s] + patch_n(psi) dprobe[s] )
+//                           dpatch_n = patch_n(dpsi) + dscan[n][0] Dy_n(psi) + dscan[n][1] Dx_n(psi)
+//   tike_intensity_tangent  dI[f][p] = 2 sum_j Re( conj(far[f][j][p]) dfar[f][j][p] )
+//                           I[f][p]  = sum_j |far[f][j][p]|^2             (optional)
+//
+// Byte models.  tike_conv_fwd_tangent, per position: S * det^2 * 8 bytes
+// written once (the window and the zeros around it); (pw + 1)^2 * 8 bytes of
+// object read, twice that with dpsi (mostly served from cache: the footprints
+// of neighbouring positions overlap), S * pw^2 * 8 bytes of probe, twice that
+// with dprobe (from cache: every position reads the same planes), 8 bytes of
+// scan and 8 of dscan.  tike_intensity_tangent, per frame of P planes of npix
+// pixels: 2 * P * npix * 8 bytes of far plane and tangent read once, npix * 4
+// bytes of dI written, npix * 4 more with I.
+#include "../../include/tike_amd.h"
+#include "common.h"
+
+namespace {
+
+constexpr int JV_MAX_MODES = 16;  // TK_MAX_MODES of the gradient kernels
+constexpr int JV_COLS = 63;       // detector columns of a wave: lane 63 is the halo column
+constexpr int JV_ROWS = 8;        // detector rows of a strip
+
+__device__ __forceinline__ cf jv_lane_up(cf v) {  // lane i receives lane i + 1
+  return mk(__shfl_down(v.x, 1, 64), __shfl_down(v.y, 1, 64));
+}
+
+// The bilinear patch pixel from its four taps, in the order of tk_gather.
+__device__ __forceinline__ cf jv_bilinear(cf o00, cf o01, cf o10, cf o11, const TkCorner& c) {
+  cf r = mk(o00.x * c.w00, o00.y * c.w00);
+  r.x += o01.x * c.w01;
+  r.y += o01.y * c.w01;
+  r.x += o10.x * c.w10;
+  r.y += o10.y * c.w10;
+  r.x += o11.x * c.w11;
+  r.y += o11.y * c.w11;
+  return r;
+}
+
+// grid (position, group of four items): the (det, det) plane of a position is
+// cut into items of JV_ROWS rows x JV_COLS columns, one per wave, with the
+// strip / halo-lane scheme of scan_gradient_kernel (autograd.hip) laid over
+// the DETECTOR plane: a lane owns one column of its item and walks down the
+// strip, JV_ROWS + 1 object rows of psi (and of dpsi when given), each loaded
+// once -- they serve the patch, Dy, Dx and every mode -- and the tap to the
+// right comes from the next lane by wave shuffle (lane 63 only feeds lane 62
+// and owns no output).  With the taps O00, O01, O10, O11 and the weights of
+// tk_corner,
+//   patch = w00 O00 + w01 O01 + w10 O10 + w11 O11
+//   Dy = (1 - fx)(O10 - O00) + fx (O11 - O01)      d patch / d scan[n][0]
+//   Dx = (1 - fy)(O01 - O00) + fy (O11 - O10)      d patch / d scan[n][1]
+// as tike_scan_gradient has them (the integer part of the position held
+// fixed).  A NULL tangent is a zero tangent: its loads are skipped (uniform)
+// and its terms are computed on zeros.  Every load that is made is
+// unconditional (clamped address, value selected): a tap outside the object
+// counts as zero, a pixel outside the centred pw window is written as exactly
+// 0.0, and nothing outside the arrays is touched, whatever the positions.  An
+// item that lies in the padding altogether only writes its zeros.  Products
+// are float32; every output element has one owner: no atomics.  All offsets
+// are `long`.
+__global__ __launch_bounds__(256) void conv_fwd_tangent_kernel(
+    const cf* __restrict__ psi, const cf* __restrict__ dpsi, const float* __restrict__ scan,
+    const float* __restrict__ dscan, const cf* __restrict__ probe, const cf* __restrict__ dprobe,
+    cf* __restrict__ nearplane, int S, int pw, int det, int H, int W) {
+  const long n = blockIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int nseg = (det + JV_COLS - 1) / JV_COLS;
+  const int nstrip = (det + JV_ROWS - 1) / JV_ROWS;
+  const int item = (int)blockIdx.y * 4 + wave;  // uniform in a wave
+  if (item >= nseg * nstrip) return;
+  const int pad = (det - pw) / 2;
+  const int dx0 = (item % nseg) * JV_COLS;
+  const int dy0 = (item / nseg) * JV_ROWS;
+  const int dx = dx0 + lane;  // detector column; lane 63: the right tap of lane 62
+  const int px = dx - pad, px0 = dx0 - pad, py0 = dy0 - pad;
+  const bool owner = lane < JV_COLS && dx < det;
+  const long plane = (long)det * det;
+  cf* __restrict__ dst = nearplane + n * S * plane + (long)dx;
+  if (py0 + JV_ROWS <= 0 || py0 >= pw || px0 + JV_COLS <= 0 || px0 >= pw) {
+    // padding only (uniform in a wave)
+    for (int s = 0; s < S; ++s)
+      for (int j = 0; j < JV_ROWS; ++j)
+        if (owner && dy0 + j < det) dst[s * plane + (long)(dy0 + j) * det] = mk(0.f, 0.f);
+    return;
+  }
+  const TkCorner c = tk_corner(scan, n);
+  const float py_ = scan[2 * n], px_ = scan[2 * n + 1];
+  const float fy = py_ - floorf(py_), fx = px_ - floorf(px_);
+  const float dsy = dscan != nullptr ? dscan[2 * n] : 0.f;
+  const float dsx = dscan != nullptr ? dscan[2 * n + 1] : 0.f;
+  const long X = (long)c.sx + px;
+  const bool okx = X >= 0 && X < W;
+  const long Xc = X < 0 ? 0 : (X < W ? X : W - 1);
+  cf o[JV_ROWS + 1], d[JV_ROWS + 1];
+#pragma unroll
+  for (int j = 0; j <= JV_ROWS; ++j) {
+    const long Y = (long)c.sy + py0 + j;
+    const bool ok = okx && Y >= 0 && Y < H;
+    const long Yc = Y < 0 ? 0 : (Y < H ? Y : H - 1);
+    const cf v = psi[Yc * W + Xc];
+    o[j] = ok ? v : mk(0.f, 0.f);
+    d[j] = mk(0.f, 0.f);
+    if (dpsi != nullptr) {  // uniform
+      const cf t = dpsi[Yc * W + Xc];
+      d[j] = ok ? t : mk(0.f, 0.f);
+    }
+  }
+  const bool colin = px >= 0 && px < pw;
+  const int pxc = px < 0 ? 0 : (px < pw ? px : pw - 1);
+  cf pat[JV_ROWS], dpat[JV_ROWS];
+  cf right = jv_lane_up(o[0]), dright = jv_lane_up(d[0]);
+#pragma unroll
+  for (int j = 0; j < JV_ROWS; ++j) {
+    const cf o00 = o[j], o01 = right, o10 = o[j + 1];
+    const cf o11 = jv_lane_up(o10);
+    right = o11;
+    const cf d00 = d[j], d01 = dright, d10 = d[j + 1];
+    const cf d11 = jv_lane_up(d10);
+    dright = d11;
+    const float dyr = (1.0f - fx) * (o10.x - o00.x) + fx * (o11.x - o01.x);
+    const float dyi = (1.0f - fx) * (o10.y - o00.y) + fx * (o11.y - o01.y);
+    const float dxr = (1.0f - fy) * (o01.x - o00.x) + fy * (o11.x - o10.x);
+    const float dxi = (1.0f - fy) * (o01.y - o00.y) + fy * (o11.y - o10.y);
+    pat[j] = jv_bilinear(o00, o01, o10, o11, c);
+    cf t = jv_bilinear(d00, d01, d10, d11, c);
+    t.x += dsy * dyr;
+    t.y += dsy * dyi;
+    t.x += dsx * dxr;
+    t.y += dsx * dxi;
+    dpat[j] = t;
+  }
+  const long pp = (long)pw * pw;
+  for (int s = 0; s < S; ++s) {
+#pragma unroll
+    for (int j = 0; j < JV_ROWS; ++j) {
+      const int py = py0 + j;
+      const bool in = colin && py >= 0 && py < pw;
+      const int pyc = py < 0 ? 0 : (py < pw ? py : pw - 1);
+      const long at = s * pp + (long)pyc * pw + pxc;
+      cf v = dpat[j] * probe[at];
+      if (dprobe != nullptr) v = v + pat[j] * dprobe[at];  // uniform
+      if (owner && dy0 + j < det)
+        dst[s * plane + (long)(dy0 + j) * det] = in ? v : mk(0.f, 0.f);
+    }
+  }
+}
+
+// 16-byte accesses whose ADDRESS is only as aligned as an element (a plane
+// starts at a multiple of npix elements): see autograd.hip.
+typedef float jv_f4 __attribute__((ext_vector_type(4), aligned(8)));  // two cf
+typedef float jv_t4 __attribute__((ext_vector_type(4), aligned(4)));  // four sums
+
+constexpr int JV_PX = 4;  // pixels of a lane: two 16-byte accesses per plane and far plane
+
+// The layout of farplane_scale_kernel: a lane owns JV_PX consecutive pixels of
+// one frame and walks the P planes, both far planes read once; the last
+// npix % JV_PX pixels of a frame are taken one per lane by the lanes behind
+// the last vector.  `bpf` workgroups serve a frame.  The intensity is summed
+// as tike_intensity and tike_fly_farplane_gradient sum it (planes ascending,
+// a float32 running sum of re^2 + im^2, each product and each sum rounded:
+// those kernels compile to packed multiplies and adds).  The same bits must
+// not hang on what the compiler chooses to fuse here, so contraction is off
+// in this kernel: no fused multiply-add in either sum.
+__global__ __launch_bounds__(256) void intensity_tangent_kernel(
+    const cf* __restrict__ farplane, const cf* __restrict__ dfarplane,
+    float* __restrict__ intensity, float* __restrict__ dintensity, int P, long npix, long bpf) {
+#pragma clang fp contract(off)
+  const long f = (long)blockIdx.x / bpf;
+  const long v = ((long)blockIdx.x % bpf) * blockDim.x + threadIdx.x;
+  const cf* __restrict__ F = farplane + f * P * npix;
+  const cf* __restrict__ D = dfarplane + f * P * npix;
+  const long nvec = npix / JV_PX;
+  if (v < nvec) {
+    const long p = v * JV_PX;
+    float I[JV_PX] = {0.f, 0.f, 0.f, 0.f};
+    float T[JV_PX] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int j = 0; j < P; ++j) {
+      const cf* at = F + j * npix + p;
+      const cf* dt = D + j * npix + p;
+      const jv_f4 a = *reinterpret_cast<const jv_f4*>(at);
+      const jv_f4 b = *reinterpret_cast<const jv_f4*>(at + 2);
+      const jv_f4 da = *reinterpret_cast<const jv_f4*>(dt);
+      const jv_f4 db = *reinterpret_cast<const jv_f4*>(dt + 2);
+      I[0] += a.x * a.x + a.y * a.y;
+      I[1] += a.z * a.z + a.w * a.w;
+      I[2] += b.x * b.x + b.y * b.y;
+      I[3] += b.z * b.z + b.w * b.w;
+      T[0] += a.x * da.x + a.y * da.y;
+      T[1] += a.z * da.z + a.w * da.w;
+      T[2] += b.x * db.x + b.y * db.y;
+      T[3] += b.z * db.z + b.w * db.w;
+    }
+    jv_t4 t;
+#pragma unroll
+    for (int k = 0; k < JV_PX; ++k) t[k] = 2.0f * T[k];
+    *reinterpret_cast<jv_t4*>(dintensity + f * npix + p) = t;
+    if (intensity != nullptr) {
+      jv_t4 o;
+#pragma unroll
+      for (int k = 0; k < JV_PX; ++k) o[k] = I[k];
+      *reinterpret_cast<jv_t4*>(intensity + f * npix + p) = o;
+    }
+    return;
+  }
+  // scalar tail: fewer than JV_PX pixels, one per lane
+  const long p = nvec * JV_PX + (v - nvec);
+  if (p >= npix) return;
+  float I = 0.f, T = 0.f;
+  for (int j = 0; j < P; ++j) {
+    const cf a = F[j * npix + p], da = D[j * npix + p];
+    I += a.x * a.x + a.y * a.y;  // (written here: the pragma does not reach into norm2)
+    T += a.x * da.x + a.y * da.y;
+  }
+  dintensity[f * npix + p] = 2.0f * T;
+  if (intensity != nullptr) intensity[f * npix + p] = I;
+}
+
+}  // namespace
+
+extern "C" int tike_conv_fwd_tangent(const void* psi, const void* dpsi, const float* scan,
+                                     const float* dscan, const void* probe, const void* dprobe,
+                                     void* nearplane, long nscan, int S, int pw, int det, int H,
+                                     int W, void* stream_) {
+  TK_ENTER();
+  hipStream_t stream = (hipStream_t)stream_;
+  TK_CHECK_ARG(psi && scan && probe && nearplane);
+  TK_CHECK_ARG(nscan >= 0 && S >= 1 && pw >= 1 && det >= pw && H >= 1 && W >= 1);
+  if (S > JV_MAX_MODES) return TK_ERR_UNSUPPORTED;
+  if (nscan == 0) return TK_OK;
+  TK_CHECK_ARG(nscan <= 0x7fffffffL);  // one grid column per position: grid.x
+  const long items = (long)((det + JV_COLS - 1) / JV_COLS) * ((det + JV_ROWS - 1) / JV_ROWS);
+  const long groups = (items + 3) / 4;  // one item per wave
+  TK_CHECK_ARG(groups <= (long)tike_max_grid_dim_y());
+  hipLaunchKernelGGL(conv_fwd_tangent_kernel, dim3((unsigned)nscan, (unsigned)groups), dim3(256),
+                     0, stream, (const cf*)psi, (const cf*)dpsi, scan, dscan, (const cf*)probe,
+                     (const cf*)dprobe, (cf*)nearplane, S, pw, det, H, W);
+  TK_LAUNCH_CHECK();
+  return TK_OK;
+}
+
+extern "C" int tike_intensity_tangent(const void* farplane, const void* dfarplane,
+                                      float* intensity, float* dintensity, long nframe, int P,
+                                      long npix, void* stream_) {
+  TK_ENTER();
+  hipStream_t stream = (hipStream_t)stream_;
+  TK_CHECK_ARG(farplane && dfarplane && dintensity);
+  TK_CHECK_ARG(nframe >= 0 && P >= 1 && npix >= 1);
+  if (nframe == 0) return TK_OK;
+  // lanes of a frame: one per vector of JV_PX pixels, one per pixel of the tail
+  const long lanes = npix / JV_PX + npix % JV_PX;
+  const long bpf = (lanes + 255) / 256;
+  TK_CHECK_ARG(bpf <= 0x7fffffffL / nframe);  // the workgroups of all frames: grid.x
+  hipLaunchKernelGGL(intensity_tangent_kernel, dim3((unsigned)(nframe * bpf)), dim3(256), 0,
+                     stream, (const cf*)farplane, (const cf*)dfarplane, intensity, dintensity, P,
+                     npix, bpf);
+  TK_LAUNCH_CHECK();
+  return TK_OK;
+}
