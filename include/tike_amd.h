@@ -38,7 +38,7 @@ extern "C" {
  * A binding compares tike_abi_version() of the loaded library with the
  * TIKE_ABI_VERSION it was written against before its first call
  * (tike_amd/_lib.py does; INTEGRATION.md shows the check). */
-#define TIKE_ABI_VERSION 22
+#define TIKE_ABI_VERSION 23
 
 /* sha256 (64 hex digits) of the sources the library was built from: the PMC
  * traffic files under profiles/ carry it, and bench.py withholds a traffic
@@ -1315,8 +1315,38 @@ int tike_conv_fwd_tangent(const void* psi, const void* dpsi, const float* scan,
                           void* nearplane, long nscan, int S, int pw, int det, int H, int W,
                           void* stream);
 
+/* The same for ONE slice of a multislice object (tike_amd/autograd.py:
+ * multislice_intensity_jvp; no reference counterpart), probe window =
+ * detector, so the (pw,pw) planes carry no padding, with the beam incident on
+ * the slice and its tangent in the place of the probe and its tangent:
+ *   dpatch_n    = patch_n(dpsi) + dscan[n][0] Dy_n(psi) + dscan[n][1] Dx_n(psi)
+ *   dwave[n][s] = dpatch_n beam[n|0][s] + patch_n(psi) dbeam[n|0][s]
+ * psi, dpsi (H,W) c64: the slice and its tangent; beam (nscan,S,pw,pw) c64
+ * with beam_per_scan != 0, else (S,pw,pw) shared by every position; dbeam
+ * likewise with dbeam_per_scan; dwave (nscan,S,pw,pw) c64, overwritten.  Any
+ * of dpsi, dscan, dbeam may be NULL: a zero tangent whose loads are skipped;
+ * with all three NULL the plane is written as exactly 0.0.  dwave may be the
+ * very buffer of a per-position dbeam (the same address, not a shifted
+ * overlap): every element is read by its one owner before that owner writes
+ * it; dwave must not overlap beam.  Taps, weights, Dy, Dx as
+ * tike_scan_gradient has them (the integer part of a position held fixed; a
+ * tap outside the object counts as zero); float32 products; one owner per
+ * output element, no atomics: two calls give the same bits.  Nothing outside
+ * the arrays is touched, whatever the positions.  Any pw.  No allocation.
+ * Per position S pw^2 8 bytes are written, as many read of a per-position beam
+ * and again of a per-position dbeam, (pw + 1)^2 8 bytes of object taps (twice
+ * that with dpsi; mostly from cache), 8 bytes of scan and 8 of dscan.
+ * TIKE_ERR_ARG for a NULL psi, scan, beam or dwave, S < 1, pw < 1, H < 1,
+ * W < 1, nscan < 0, nscan > 2^31 - 1 or a plane of more items than one launch
+ * holds; TIKE_ERR_UNSUPPORTED for S > 16; nscan == 0 returns 0 without a
+ * launch. */
+int tike_slice_wave_tangent(const void* psi, const void* dpsi, const float* scan,
+                            const float* dscan, const void* beam, int beam_per_scan,
+                            const void* dbeam, int dbeam_per_scan, void* dwave, long nscan,
+                            int S, int pw, int H, int W, void* stream);
+
 /* The tangent of the intensity from a far plane and its tangent (tike_fft2 of
- * the plane above, with the forward scale):
+ * a plane above, with the forward scale):
  *   dintensity[f][p] = 2 sum_{j<P} Re( conj(farplane[f][j][p]) dfarplane[f][j][p] )
  *   intensity[f][p]  = sum_{j<P} |farplane[f][j][p]|^2        (unless NULL)
  * farplane, dfarplane (nframe,P,npix) c64, P = fly * S: the positions and

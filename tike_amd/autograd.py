@@ -108,9 +108,43 @@ and with no tangent at all only the primal launches.  `intensity` on
 ``torch.autograd.forward_ad`` dual tensors (any subset of psi, probe, scan)
 returns a dual whose tangent is this dI: `_Intensity.jvp` runs the same chunk
 loop.  The eigen-probe form and `multislice_intensity` have no forward-mode
-rule yet: under `forward_ad` they keep torch's own refusal ("you must
-implement the jvp function").  ``gauss_newton_product`` composes the two
-modes: J^T (weight * J v) by `intensity_jvp` and then the backward above.
+rule: under `forward_ad` they keep torch's own refusal ("you must implement
+the jvp function").  ``gauss_newton_product`` composes the two modes:
+J^T (weight * J v) by `intensity_jvp` and then the backward above.
+
+Forward mode, several slices.  ``multislice_intensity_jvp(operator, psi, probe,
+scan, d_psi=, d_probe=, d_scan=, fly=...)`` returns (I, dI = J v) of
+`multislice_intensity` for tangents d_psi (D, H, W), d_probe (1, 1, S, pw, pw)
+and d_scan (N, 2); the Fresnel step is linear, so the tangent of a beam is the
+Fresnel step of the tangent of the exit wave in front of it:
+
+    beam_0 = probe                      dbeam_0 = d_probe
+    dpatch_{n,d} = patch_n(d_psi[d]) + d_scan[n,0] Dy_n(psi[d])
+                                     + d_scan[n,1] Dx_n(psi[d])
+    e_d  = patch_n(psi[d]) beam_d
+    de_d = dpatch_{n,d} beam_d + patch_n(psi[d]) dbeam_d
+    beam_{d+1} = Fresnel(e_d)           dbeam_{d+1} = Fresnel(de_d)
+    far = F e_{D-1}    dfar = F de_{D-1}
+    dI[f] = sum_{n in frame f} sum_s 2 Re(conj(far) dfar)
+
+Per chunk of whole frames -- the far plane, the D - 1 sets of incident beams
+and ONE tangent set are resident, one set more than the forward holds --
+
+    the primal as `multislice_intensity` runs it (`_fused_far` or
+    `_general_far`: I has its bits; both leave the beam incident on every
+    slice) -> per slice tike_slice_wave_tangent, de_d written over dbeam_d in
+    place (slice 0: the shared probe and d_probe), and between two slices the
+    Fresnel step of the tangent (fused route: tike_fft2_pass1 ->
+    tike_fresnel_colpass -> tike_fft2_pass2_inplace with the scale of
+    `_fused_far`, measured faster; general route: tike_fresnel_spect_prop in
+    place) -> tike_fft2 (in place, forward scale) -> tike_intensity_tangent
+
+with no torch arithmetic; no tangent at all: only the primal launches.  One
+slice goes through the chunk loop of `intensity_jvp`.  There is still no
+forward-mode RULE for `_MultisliceIntensity`: dual tensors stay refused, the
+function is the interface.  ``multislice_gauss_newton_product`` is
+`gauss_newton_product` for this model: the JVP without the primal intensity,
+then the backward of `multislice_intensity` with weight * dI upstream.
 """
 import importlib
 
@@ -478,7 +512,8 @@ def intensity(operator, psi, probe, scan, *, eigen_probe=None,
     gathered: where only some inputs vary, `intensity_jvp` with the others
     left None is the faster call).  The eigen-probe
     form below and `multislice_intensity` have none: under `forward_ad` they
-    raise torch's "you must implement the jvp function".
+    raise torch's "you must implement the jvp function" (the forward mode of
+    several slices is the function `multislice_intensity_jvp`).
 
     With eigen_weights the probe varies from position to position (not from
     frame to frame: any `fly`), as `get_varying_probe` has it: position n sees
@@ -583,7 +618,7 @@ def _checked_tangents(name, psi, probe, scan, d_psi, d_probe, d_scan):
 
 
 def _checked_jvp(name, operator, psi, probe, scan, d_psi, d_probe, d_scan,
-                 fly, check_positions):
+                 fly, check_positions, slices=False):
     """Every refusal of the forward-mode entries that needs no device, the
     tangents' among them, before `_checked` asks for device tensors."""
     tangents = None
@@ -591,7 +626,8 @@ def _checked_jvp(name, operator, psi, probe, scan, d_psi, d_probe, d_scan,
         # (host arrays: `_checked` below names them)
         tangents = _checked_tangents(name, psi, probe, scan, d_psi, d_probe,
                                      d_scan)
-    fly = _checked(operator, psi, probe, scan, fly, check_positions, name=name)
+    fly = _checked(operator, psi, probe, scan, fly, check_positions, name=name,
+                   slices=slices)
     return fly, tangents
 
 
@@ -605,7 +641,7 @@ def intensity_jvp(operator, psi, probe, scan, *, d_psi=None, d_probe=None,
     float32, outside any autograd graph.  The derivative with respect to the
     positions is that of `scan.grad`: the integer part of a position is held
     fixed.  One slice and the shared probe only: eigen probes are no parameter
-    of this function, and `multislice_intensity` has no forward mode yet.
+    of this function, and several slices are `multislice_intensity_jvp`'s.
     With no tangent dI is zeros and only the primal launches.
 
     Raises what `intensity` raises (NotImplementedError for several slices or
@@ -658,6 +694,28 @@ def gauss_newton_product(operator, psi, probe, scan, *, d_psi=None,
     weight of another type, dtype, shape or device.
     """
     name = "gauss_newton_product"
+    wrt = _checked_product(name, operator, psi, scan, weight, fly, wrt)
+    fly, (d_psi, d_probe, d_scan) = _checked_jvp(
+        name, operator, psi, probe, scan, d_psi, d_probe, d_scan, fly,
+        check_positions)
+    leaves = {k: x.detach().contiguous().requires_grad_(k in wrt)
+              for k, x in zip(_WRT, (psi, probe, scan))}
+    if d_psi is None and d_probe is None and d_scan is None:
+        return tuple(torch.zeros_like(leaves[k]) for k in wrt)
+    tangent = _jvp_chunks(operator, *(leaves[k].detach() for k in _WRT), d_psi,
+                          d_probe, d_scan, fly, primal=False)[1]
+    if weight is not None:
+        tangent = tangent * weight.detach()
+    with torch.enable_grad():
+        inten = _Intensity.apply(leaves["psi"], leaves["probe"],
+                                 leaves["scan"], operator, fly)
+        return torch.autograd.grad(inten, [leaves[k] for k in wrt],
+                                   grad_outputs=tangent)
+
+
+def _checked_product(name, operator, psi, scan, weight, fly, wrt):
+    """The `wrt` and `weight` refusals of the Gauss-Newton products; wrt as a
+    tuple."""
     wrt = tuple(wrt)
     if not wrt or len(set(wrt)) != len(wrt) or any(w not in _WRT for w in wrt):
         raise ValueError(
@@ -680,22 +738,7 @@ def gauss_newton_product(operator, psi, probe, scan, *, d_psi=None,
             raise ValueError(
                 f"{name}: weight lives on {weight.device}, psi on "
                 f"{psi.device}")
-    fly, (d_psi, d_probe, d_scan) = _checked_jvp(
-        name, operator, psi, probe, scan, d_psi, d_probe, d_scan, fly,
-        check_positions)
-    leaves = {k: x.detach().contiguous().requires_grad_(k in wrt)
-              for k, x in zip(_WRT, (psi, probe, scan))}
-    if d_psi is None and d_probe is None and d_scan is None:
-        return tuple(torch.zeros_like(leaves[k]) for k in wrt)
-    tangent = _jvp_chunks(operator, *(leaves[k].detach() for k in _WRT), d_psi,
-                          d_probe, d_scan, fly, primal=False)[1]
-    if weight is not None:
-        tangent = tangent * weight.detach()
-    with torch.enable_grad():
-        inten = _Intensity.apply(leaves["psi"], leaves["probe"],
-                                 leaves["scan"], operator, fly)
-        return torch.autograd.grad(inten, [leaves[k] for k in wrt],
-                                   grad_outputs=tangent)
+    return wrt
 
 
 # ------------------------------------------------------------ several slices
@@ -720,17 +763,18 @@ def _fused_route(op, probe):
         probe.shape[-1], op.detector_shape, probe.shape[-3]))
 
 
-def _slices_chunk(op, psi, probe, fly, fused):
+def _slices_chunk(op, psi, probe, fly, fused, extra=0):
     """Positions per chunk, whole frames.  Fused route: far + mid + D - 1 sets
     of incident probes + the D objproj planes (D / S of a set, rounded up)
-    within half the free HBM, as `cgrad` sizes its multislice chunks."""
+    + `extra` sets (the forward mode's tangent) within half the free HBM, as
+    `cgrad` sizes its multislice chunks."""
     from .ptycho.solvers import lstsq
     D, S, det = psi.shape[0], probe.shape[-3], op.detector_shape
     if lstsq.CHUNK_POSITIONS_OVERRIDE or not fused:
         chunk = lstsq.chunk_positions(S, det)
     else:
         chunk = chunk_within_hbm(lstsq._workspace(op), psi.device,
-                                 D + 1 + -(-D // S), S, det)
+                                 D + 1 + -(-D // S) + extra, S, det)
     return max(1, chunk // fly) * fly
 
 
@@ -1015,3 +1059,193 @@ def multislice_intensity(operator, psi, probe, scan, *, fly=1,
     if psi.shape[0] == 1:
         return _Intensity.apply(psi, probe, scan, operator, fly)
     return _MultisliceIntensity.apply(psi, probe, scan, operator, fly)
+
+
+# --------------------------------------------- forward mode, several slices
+TANGENT_FRESNEL_TWO_PASS = True
+"""Fused route: the Fresnel step of the tangent between two slices by
+`tike_fft2_pass1` -> `tike_fresnel_colpass` -> `tike_fft2_pass2_inplace` (the
+scale of `_fused_far`, the `ms_mid` workspace for the hand-off) instead of
+`tike_fresnel_spect_prop` in place: 0.68 - 0.77 of its time at 256^2 and 128^2
+(profiles/autograd_multislice_jvp.md).  The general route has the one launch
+only; the tests compare the two."""
+
+FIRST_SLICE_BY_CONV_TANGENT = False
+"""Slice 0 (shared probe, shared d_probe) by `tike_conv_fwd_tangent` at
+det == pw instead of `tike_slice_wave_tangent`: the two are timed against each
+other in profiles/autograd_multislice_jvp.md; the tests compare them."""
+
+
+def _multislice_jvp_chunks(op, psi, probe, scan, d_psi, d_probe, d_scan, fly,
+                           primal=True):
+    """(I or None, dI): the chunk loop of `multislice_intensity_jvp` for
+    D > 1 slices on contiguous device tensors; at least one tangent is not
+    None."""
+    from .ptycho.solvers.lstsq import _workspace
+    D, (H, W) = psi.shape[0], psi.shape[-2:]
+    N, S, det = scan.shape[0], probe.shape[2], op.detector_shape
+    dev = psi.device
+    A.current_device()  # (hands the library its deterministic-mode scratch)
+    st = A.stream_ptr()
+    inten = (torch.empty((N // fly, det, det), dtype=torch.float32, device=dev)
+             if primal else None)
+    tangent = torch.empty((N // fly, det, det), dtype=torch.float32,
+                          device=dev)
+    if N == 0:
+        return inten, tangent
+    fused = _fused_route(op, probe)
+    # one set more than the forward: the tangent (the general route keeps the
+    # forward's chunk, which bounds a launch, not the memory)
+    chunk = _slices_chunk(op, psi, probe, fly, fused, extra=1)
+    nmax = min(chunk, N)
+    fresnel = op.diffraction.propagation
+    fwd_scale, inv_scale = fft_scales(det, op.norm)
+    if fused:
+        far_all, mid, beams, _ = _fused_buffers(op, psi, probe, nmax)
+        dwave_all = _workspace(op).get("ms_tangent", (nmax, S, det, det),
+                                       torch.complex64, dev)
+        prop = fresnel._propagator((det, det), dev)
+    else:
+        dwave_all = torch.empty((nmax, S, det, det), dtype=torch.complex64,
+                                device=dev)
+    for lo in range(0, N, chunk):
+        hi = min(N, lo + chunk)
+        n = hi - lo
+        sc = scan[lo:hi]
+        dsc = None if d_scan is None else d_scan[lo:hi]
+        if fused:
+            far = _fused_far(op, psi, sc, probe, far_all, beams)
+        else:
+            far, incident = _general_far(op, psi, sc, probe)
+        dwave = dwave_all[:n]
+        for d in range(D):
+            dslice = None if d_psi is None else d_psi[d]
+            if d == 0 and FIRST_SLICE_BY_CONV_TANGENT:
+                check(
+                    lib.tike_conv_fwd_tangent(
+                        A.ptr(psi[0]), A.ptr(dslice), A.ptr(sc), A.ptr(dsc),
+                        A.ptr(probe), A.ptr(d_probe), A.ptr(dwave), n, S, det,
+                        det, H, W, st),
+                    "multislice_intensity_jvp (tangent exit waves of the "
+                    "first slice)")
+                continue
+            if d == 0:
+                beam, per_scan = probe, 0
+                dbeam, dper_scan = d_probe, 0
+            else:
+                if fused and TANGENT_FRESNEL_TWO_PASS:
+                    check(lib.tike_fft2_pass1(A.ptr(dwave), A.ptr(mid), n * S,
+                                              det, 0, st),
+                          "multislice_intensity_jvp (Fresnel step of the "
+                          "tangent: pass 1)")
+                    check(
+                        lib.tike_fresnel_colpass(A.ptr(mid), A.ptr(prop), 0,
+                                                 A.ptr(dwave), n * S, det,
+                                                 fwd_scale * inv_scale, st),
+                        "multislice_intensity_jvp (Fresnel step of the "
+                        "tangent: column passes)")
+                    check(lib.tike_fft2_pass2_inplace(A.ptr(dwave), n * S, det,
+                                                      1, 1.0, st),
+                          "multislice_intensity_jvp (Fresnel step of the "
+                          "tangent: pass 2)")
+                else:
+                    dwave = fresnel.fwd(dwave, overwrite=True)
+                beam = beams[d - 1, :n] if fused else incident[d]
+                per_scan, dbeam, dper_scan = 1, dwave, 1
+            # (de_d goes over dbeam_d where that is per position)
+            check(
+                lib.tike_slice_wave_tangent(
+                    A.ptr(psi[d]), A.ptr(dslice), A.ptr(sc), A.ptr(dsc),
+                    A.ptr(beam), per_scan, A.ptr(dbeam), dper_scan,
+                    A.ptr(dwave), n, S, det, H, W, st),
+                "multislice_intensity_jvp (tangent exit waves of a slice)")
+        check(lib.tike_fft2(A.ptr(dwave), A.ptr(dwave), n * S, det, 0,
+                            fwd_scale, st),
+              "multislice_intensity_jvp (tangent far plane)")
+        # the S * fly planes of a frame are adjacent
+        check(
+            lib.tike_intensity_tangent(
+                A.ptr(far), A.ptr(dwave),
+                A.ptr(inten[lo // fly:]) if primal else None,
+                A.ptr(tangent[lo // fly:]), n // fly, S * fly, det * det, st),
+            "multislice_intensity_jvp (tangent intensity)")
+    return inten, tangent
+
+
+def multislice_intensity_jvp(operator, psi, probe, scan, *, d_psi=None,
+                             d_probe=None, d_scan=None, fly=1,
+                             check_positions=True):
+    """(I, dI): the intensities of `multislice_intensity(operator, psi, probe,
+    scan, fly=fly)` -- the same bits -- and their directional derivative J v
+    along the tangents d_psi (D, H, W) complex64, d_probe (1, 1, S, pw, pw)
+    complex64 and d_scan (N, 2) float32, each None (zero) or a device tensor
+    of its primal's shape, dtype and device.  Both (N // fly, det, det)
+    float32, outside any autograd graph.  The operator is what
+    `multislice_intensity` wants: entered, probe window = detector, its optics
+    set.  The derivative with respect to the positions is that of `scan.grad`:
+    the integer part of a position is held fixed and a tap outside the object
+    counts as zero.  With no tangent dI is zeros and only the primal launches;
+    one slice returns the bits of `intensity_jvp`.  This function is the
+    forward mode of the model: `multislice_intensity` itself has no rule for
+    `torch.autograd.forward_ad` dual tensors and keeps torch's refusal there.
+
+    Raises what `multislice_intensity` raises (TypeError, ValueError,
+    NotImplementedError for a probe per position), and TypeError / ValueError
+    for a tangent that does not match its primal -- a (1, H, W) tangent of a
+    (D, H, W) object among them --, before any launch.
+    """
+    name = "multislice_intensity_jvp"
+    fly, (d_psi, d_probe, d_scan) = _checked_jvp(
+        name, operator, psi, probe, scan, d_psi, d_probe, d_scan, fly,
+        check_positions, slices=True)
+    psi, probe, scan = (x.detach().contiguous() for x in (psi, probe, scan))
+    single = psi.shape[0] == 1
+    if d_psi is None and d_probe is None and d_scan is None:
+        with torch.no_grad():
+            inten = (_Intensity if single else _MultisliceIntensity).apply(
+                psi, probe, scan, operator, fly)
+        return inten, torch.zeros_like(inten)
+    return (_jvp_chunks if single else _multislice_jvp_chunks)(
+        operator, psi, probe, scan, d_psi, d_probe, d_scan, fly)
+
+
+def multislice_gauss_newton_product(operator, psi, probe, scan, *, d_psi=None,
+                                    d_probe=None, d_scan=None, weight=None,
+                                    fly=1, wrt=_WRT, check_positions=True):
+    """`gauss_newton_product` for `multislice_intensity`: J^T (weight * J v)
+    for the tangents v = (d_psi (D, H, W), d_probe, d_scan) of
+    `multislice_intensity_jvp`, one tensor per name in `wrt` (any of "psi",
+    "probe", "scan", in that order of `wrt`) in the `.grad` convention of
+    `multislice_intensity`: the object part is (D, H, W), every slice's exact
+    part, not divided by D.  weight: (N // fly, det, det) float32 device tensor
+    or None.
+
+    Composed of the JVP with the primal intensity not written and the backward
+    of `multislice_intensity` with weight * dI for the upstream gradient; only
+    what `wrt` names is launched in the backward.  No dual tensors: see
+    `multislice_intensity_jvp`.
+
+    Raises what `multislice_intensity_jvp` raises, ValueError for names in
+    `wrt` other than the three (or none, or one twice), TypeError / ValueError
+    for a weight of another type, dtype, shape or device.
+    """
+    name = "multislice_gauss_newton_product"
+    wrt = _checked_product(name, operator, psi, scan, weight, fly, wrt)
+    fly, (d_psi, d_probe, d_scan) = _checked_jvp(
+        name, operator, psi, probe, scan, d_psi, d_probe, d_scan, fly,
+        check_positions, slices=True)
+    leaves = {k: x.detach().contiguous().requires_grad_(k in wrt)
+              for k, x in zip(_WRT, (psi, probe, scan))}
+    if d_psi is None and d_probe is None and d_scan is None:
+        return tuple(torch.zeros_like(leaves[k]) for k in wrt)
+    single = psi.shape[0] == 1
+    tangent = (_jvp_chunks if single else _multislice_jvp_chunks)(
+        operator, *(leaves[k].detach() for k in _WRT), d_psi, d_probe, d_scan,
+        fly, primal=False)[1]
+    if weight is not None:
+        tangent = tangent * weight.detach()
+    with torch.enable_grad():
+        inten = (_Intensity if single else _MultisliceIntensity).apply(
+            leaves["psi"], leaves["probe"], leaves["scan"], operator, fly)
+        return torch.autograd.grad(inten, [leaves[k] for k in wrt],
+                                   grad_outputs=tangent)

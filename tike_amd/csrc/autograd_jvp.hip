@@ -1,12 +1,16 @@
 // The kernels of the FORWARD-mode derivative of the differentiable intensity
 // model (tike_amd/autograd.py: intensity_jvp, _Intensity.jvp): the tangent of
 // the exit waves, and the tangent of the intensity from a far plane and its
-// tangent.  Between the two, the tangent far plane comes from tike_fft2.  No
-// reference counterpart: the reference has no derivative of its forward model
-// in any direction but its hand-written adjoints.
+// tangent.  Between the two, the tangent far plane comes from tike_fft2.  The
+// multislice model (multislice_intensity_jvp) walks its tangent through the
+// slices with tike_slice_wave_tangent, the Fresnel step between two slices
+// being linear.  No reference counterpart: the reference has no derivative of
+// its forward model in any direction but its hand-written adjoints.
 //
 //   tike_conv_fwd_tangent   dwave[n][s] = pad( dpatch_n probe[s] + patch_n(psi) dprobe[s] )
 //                           dpatch_n = patch_n(dpsi) + dscan[n][0] Dy_n(psi) + dscan[n][1] Dx_n(psi)
+//   tike_slice_wave_tangent dwave[n][s] = dpatch_n beam[n|0][s] + patch_n(psi) dbeam[n|0][s]
+//                           (one slice, probe window = detector: no padding; dwave may be dbeam)
 //   tike_intensity_tangent  dI[f][p] = 2 sum_j Re( conj(far[f][j][p]) dfar[f][j][p] )
 //                           I[f][p]  = sum_j |far[f][j][p]|^2             (optional)
 //
@@ -15,9 +19,14 @@
 // object read, twice that with dpsi (mostly served from cache: the footprints
 // of neighbouring positions overlap), S * pw^2 * 8 bytes of probe, twice that
 // with dprobe (from cache: every position reads the same planes), 8 bytes of
-// scan and 8 of dscan.  tike_intensity_tangent, per frame of P planes of npix
-// pixels: 2 * P * npix * 8 bytes of far plane and tangent read once, npix * 4
-// bytes of dI written, npix * 4 more with I.
+// scan and 8 of dscan.  tike_slice_wave_tangent, per position: S * pw^2 * 8
+// bytes written once; S * pw^2 * 8 bytes of beam read once when it is per
+// position, and as many of dbeam (a shared beam or dbeam comes from cache, as
+// the probe above); (pw + 1)^2 * 8 bytes of object taps, twice that with dpsi
+// (mostly from cache); 8 bytes of scan and 8 of dscan.
+// tike_intensity_tangent, per frame of P planes of npix pixels:
+// 2 * P * npix * 8 bytes of far plane and tangent read once, npix * 4 bytes of
+// dI written, npix * 4 more with I.
 #include "../../include/tike_amd.h"
 #include "common.h"
 
@@ -152,6 +161,145 @@ __global__ __launch_bounds__(256) void conv_fwd_tangent_kernel(
   }
 }
 
+constexpr int SW_COLS = 64;  // columns of an item: every lane owns one
+constexpr int SW_ROWS = 8;   // rows of a strip
+
+// The tap to the right of a lane's own: from the next lane by wave shuffle,
+// in lane 63 from the halo column, whose row j lane j holds.
+__device__ __forceinline__ cf sw_right(cf own, cf halo, int j, int lane) {
+  const cf next = jv_lane_up(own);
+  const cf edge = mk(__shfl(halo.x, j, 64), __shfl(halo.y, j, 64));
+  return lane == SW_COLS - 1 ? edge : next;
+}
+
+// grid (position, group of four items): conv_fwd_tangent_kernel for ONE slice
+// of a multislice object, whose (pw, pw) plane has no padding (probe window =
+// detector), with a beam and a tangent beam that may differ from position to
+// position (stride 0: shared).  The plane is cut into items of SW_ROWS rows x
+// SW_COLS columns, one per wave; all 64 lanes own a column, so a row segment
+// of an item is 512 contiguous bytes that start on a multiple of 512 bytes
+// within the row.  A lane loads the SW_ROWS + 1 object rows of its column once
+// (they serve the patch, Dy, Dx and every mode); the tap to the right comes
+// from the next lane by wave shuffle, and lane 63 takes it from the halo
+// column, the column behind the item, which ONE more load per lane fetches
+// (lane j its row j, j <= SW_ROWS; the other lanes repeat the last row).  The
+// formulas, the float32 products, the unconditional clamped loads with a
+// selected value and the zero tap outside the object are those of
+// conv_fwd_tangent_kernel.  A NULL tangent is a zero tangent whose loads are
+// skipped (uniform); with all three NULL the plane is written as exactly 0.0
+// and nothing is loaded.
+//
+// dwave may be dbeam itself (stride S * pw * pw): the SW_ROWS elements of a
+// mode that a lane owns are loaded into registers before the first of them is
+// stored, a lane that owns no element stores nothing, and what a clamped
+// address makes it load is never used -- so every element is read by its one
+// owner before that owner writes it.  Hence neither is `__restrict__`.  Every
+// output element has one owner: no atomics.  All offsets are `long`.
+__global__ __launch_bounds__(256) void slice_wave_tangent_kernel(
+    const cf* __restrict__ psi, const cf* __restrict__ dpsi, const float* __restrict__ scan,
+    const float* __restrict__ dscan, const cf* __restrict__ beam, long beam_stride,
+    const cf* dbeam, long dbeam_stride, cf* dwave, int S, int pw, int H, int W) {
+  const long n = blockIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int nseg = (pw + SW_COLS - 1) / SW_COLS;
+  const int nstrip = (pw + SW_ROWS - 1) / SW_ROWS;
+  const int item = (int)blockIdx.y * 4 + wave;  // uniform in a wave
+  if (item >= nseg * nstrip) return;
+  const int px0 = (item % nseg) * SW_COLS;
+  const int py0 = (item / nseg) * SW_ROWS;
+  const int px = px0 + lane;
+  const bool owner = px < pw;
+  const int pxc = owner ? px : pw - 1;
+  const long pp = (long)pw * pw;
+  cf* dst = dwave + n * S * pp + px;
+  if (dpsi == nullptr && dscan == nullptr && dbeam == nullptr) {
+    // no tangent (uniform): zeros, and no load
+    for (int s = 0; s < S; ++s)
+      for (int j = 0; j < SW_ROWS; ++j)
+        if (owner && py0 + j < pw) dst[s * pp + (long)(py0 + j) * pw] = mk(0.f, 0.f);
+    return;
+  }
+  const TkCorner c = tk_corner(scan, n);
+  const float py_ = scan[2 * n], px_ = scan[2 * n + 1];
+  const float fy = py_ - floorf(py_), fx = px_ - floorf(px_);
+  const float dsy = dscan != nullptr ? dscan[2 * n] : 0.f;
+  const float dsx = dscan != nullptr ? dscan[2 * n + 1] : 0.f;
+  const long X = (long)c.sx + px;
+  const bool okx = X >= 0 && X < W;
+  const long Xc = X < 0 ? 0 : (X < W ? X : W - 1);
+  cf o[SW_ROWS + 1], d[SW_ROWS + 1];
+#pragma unroll
+  for (int j = 0; j <= SW_ROWS; ++j) {
+    const long Y = (long)c.sy + py0 + j;
+    const bool ok = okx && Y >= 0 && Y < H;
+    const long Yc = Y < 0 ? 0 : (Y < H ? Y : H - 1);
+    const cf v = psi[Yc * W + Xc];
+    o[j] = ok ? v : mk(0.f, 0.f);
+    d[j] = mk(0.f, 0.f);
+    if (dpsi != nullptr) {  // uniform
+      const cf t = dpsi[Yc * W + Xc];
+      d[j] = ok ? t : mk(0.f, 0.f);
+    }
+  }
+  // the halo column: row min(lane, SW_ROWS) of the column behind the item
+  cf ho, hd = mk(0.f, 0.f);
+  {
+    const long XH = (long)c.sx + px0 + SW_COLS;
+    const long Y = (long)c.sy + py0 + (lane < SW_ROWS ? lane : SW_ROWS);
+    const bool ok = XH >= 0 && XH < W && Y >= 0 && Y < H;
+    const long XHc = XH < 0 ? 0 : (XH < W ? XH : W - 1);
+    const long Yc = Y < 0 ? 0 : (Y < H ? Y : H - 1);
+    const cf v = psi[Yc * W + XHc];
+    ho = ok ? v : mk(0.f, 0.f);
+    if (dpsi != nullptr) {  // uniform
+      const cf t = dpsi[Yc * W + XHc];
+      hd = ok ? t : mk(0.f, 0.f);
+    }
+  }
+  cf pat[SW_ROWS], dpat[SW_ROWS];
+  cf right = sw_right(o[0], ho, 0, lane);
+#pragma unroll
+  for (int j = 0; j < SW_ROWS; ++j) {
+    const cf o00 = o[j], o01 = right, o10 = o[j + 1];
+    const cf o11 = sw_right(o10, ho, j + 1, lane);
+    right = o11;
+    const float dyr = (1.0f - fx) * (o10.x - o00.x) + fx * (o11.x - o01.x);
+    const float dyi = (1.0f - fx) * (o10.y - o00.y) + fx * (o11.y - o01.y);
+    const float dxr = (1.0f - fy) * (o01.x - o00.x) + fy * (o11.x - o10.x);
+    const float dxi = (1.0f - fy) * (o01.y - o00.y) + fy * (o11.y - o10.y);
+    pat[j] = jv_bilinear(o00, o01, o10, o11, c);
+    cf t = mk(0.f, 0.f);
+    if (dpsi != nullptr)  // uniform
+      t = jv_bilinear(d[j], sw_right(d[j], hd, j, lane), d[j + 1],
+                      sw_right(d[j + 1], hd, j + 1, lane), c);
+    t.x += dsy * dyr;
+    t.y += dsy * dyi;
+    t.x += dsx * dxr;
+    t.y += dsx * dxi;
+    dpat[j] = t;
+  }
+  const cf* __restrict__ bsrc = beam + n * beam_stride;
+  const cf* dbsrc = dbeam != nullptr ? dbeam + n * dbeam_stride : nullptr;
+  for (int s = 0; s < S; ++s) {
+    cf b[SW_ROWS], t[SW_ROWS];
+#pragma unroll
+    for (int j = 0; j < SW_ROWS; ++j) {
+      const int py = py0 + j;
+      const long at = s * pp + (long)(py < pw ? py : pw - 1) * pw + pxc;
+      b[j] = bsrc[at];
+      t[j] = mk(0.f, 0.f);
+      if (dbsrc != nullptr) t[j] = dbsrc[at];  // uniform
+    }
+#pragma unroll
+    for (int j = 0; j < SW_ROWS; ++j) {
+      cf v = dpat[j] * b[j];
+      if (dbsrc != nullptr) v = v + pat[j] * t[j];  // uniform
+      if (owner && py0 + j < pw) dst[s * pp + (long)(py0 + j) * pw] = v;
+    }
+  }
+}
+
 // 16-byte accesses whose ADDRESS is only as aligned as an element (a plane
 // starts at a multiple of npix elements): see autograd.hip.
 typedef float jv_f4 __attribute__((ext_vector_type(4), aligned(8)));  // two cf
@@ -242,6 +390,29 @@ extern "C" int tike_conv_fwd_tangent(const void* psi, const void* dpsi, const fl
   hipLaunchKernelGGL(conv_fwd_tangent_kernel, dim3((unsigned)nscan, (unsigned)groups), dim3(256),
                      0, stream, (const cf*)psi, (const cf*)dpsi, scan, dscan, (const cf*)probe,
                      (const cf*)dprobe, (cf*)nearplane, S, pw, det, H, W);
+  TK_LAUNCH_CHECK();
+  return TK_OK;
+}
+
+extern "C" int tike_slice_wave_tangent(const void* psi, const void* dpsi, const float* scan,
+                                       const float* dscan, const void* beam, int beam_per_scan,
+                                       const void* dbeam, int dbeam_per_scan, void* dwave,
+                                       long nscan, int S, int pw, int H, int W, void* stream_) {
+  TK_ENTER();
+  hipStream_t stream = (hipStream_t)stream_;
+  TK_CHECK_ARG(psi && scan && beam && dwave);
+  TK_CHECK_ARG(nscan >= 0 && S >= 1 && pw >= 1 && H >= 1 && W >= 1);
+  if (S > JV_MAX_MODES) return TK_ERR_UNSUPPORTED;
+  if (nscan == 0) return TK_OK;
+  TK_CHECK_ARG(nscan <= 0x7fffffffL);  // one grid column per position: grid.x
+  const long items = (long)((pw + SW_COLS - 1) / SW_COLS) * ((pw + SW_ROWS - 1) / SW_ROWS);
+  const long groups = (items + 3) / 4;  // one item per wave
+  TK_CHECK_ARG(groups <= (long)tike_max_grid_dim_y());
+  const long set = (long)S * pw * pw;
+  hipLaunchKernelGGL(slice_wave_tangent_kernel, dim3((unsigned)nscan, (unsigned)groups),
+                     dim3(256), 0, stream, (const cf*)psi, (const cf*)dpsi, scan, dscan,
+                     (const cf*)beam, beam_per_scan ? set : 0L, (const cf*)dbeam,
+                     dbeam_per_scan ? set : 0L, (cf*)dwave, S, pw, H, W);
   TK_LAUNCH_CHECK();
   return TK_OK;
 }
