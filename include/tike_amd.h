@@ -38,7 +38,7 @@ extern "C" {
  * A binding compares tike_abi_version() of the loaded library with the
  * TIKE_ABI_VERSION it was written against before its first call
  * (tike_amd/_lib.py does; INTEGRATION.md shows the check). */
-#define TIKE_ABI_VERSION 23
+#define TIKE_ABI_VERSION 24
 
 /* sha256 (64 hex digits) of the sources the library was built from: the PMC
  * traffic files under profiles/ carry it, and bench.py withholds a traffic
@@ -1344,6 +1344,48 @@ int tike_slice_wave_tangent(const void* psi, const void* dpsi, const float* scan
                             const float* dscan, const void* beam, int beam_per_scan,
                             const void* dbeam, int dbeam_per_scan, void* dwave, long nscan,
                             int S, int pw, int H, int W, void* stream);
+
+/* The same for the VARYING probe of tike_eigen_probe_gradients above
+ * (tike_amd/autograd.py: eigen_intensity_jvp; no reference counterpart), with
+ * C = num_eigen, M = eigen_modes (M is taken as 0 when C is 0, and eigen_probe
+ * may then be NULL; deigen_probe is then ignored):
+ *   P[n][s]  = w[n][0][s] probe[s] + sum_c w[n][c+1][s] E[c][s]          s < M; else the first term
+ *   dP[n][s] = w[n][0][s] dprobe[s] + dw[n][0][s] probe[s]
+ *            + sum_c ( w[n][c+1][s] dE[c][s] + dw[n][c+1][s] E[c][s] )   the sum only for s < M
+ *   dpatch_n = patch_n(dpsi) + dscan[n][0] Dy_n(psi) + dscan[n][1] Dx_n(psi)
+ *   nearplane[n][s] = pad( dpatch_n P[n][s] + patch_n(psi) dP[n][s] )
+ * psi, dpsi (H,W) c64; scan, dscan (nscan,2) f32; probe, dprobe (S,pw,pw) c64;
+ * eigen_probe, deigen_probe (C,M,pw,pw) c64; eigen_weights, deigen_weights
+ * (nscan,C+1,S) f32 (the full shape: rows c + 1 contribute nothing for s >= M,
+ * whatever they hold, and are not read there); nearplane (nscan,S,det,det)
+ * c64, overwritten: the centred pw window and the zero padding around it in
+ * the layout of tike_conv_fwd (pw == det: no padding; an odd det - pw as
+ * tike_conv_fwd has it); the kernel writes the zeros itself (exactly 0.0; no
+ * memset is needed).  Any of dpsi, dscan, dprobe, deigen_probe,
+ * deigen_weights may be NULL: a zero tangent whose loads are skipped; with
+ * all five NULL the plane is written as zeros and nothing is loaded.  P and
+ * dP are built in registers and never stored.  Taps, fractions, Dy, Dx as
+ * tike_scan_gradient has them (the integer part of a position held fixed; a
+ * tap outside the object counts as zero); every load is made on a clamped
+ * address and its value selected: nothing outside the arrays is touched,
+ * whatever the positions.  Products are float32; every output element has one
+ * owner, no atomics: two calls give the same bits, in either determinism mode.
+ * No allocation.  Per position S det^2 8 bytes are written; read are
+ * (pw + 1)^2 8 bytes of object taps (twice that with dpsi; mostly from cache),
+ * the (S + C M) pw^2 8 bytes of the probe planes (twice that with their
+ * tangents; from cache: shared by every position), 2 (C + 1) S floats of
+ * weights and their tangent, 8 bytes of scan and 8 of dscan.  TIKE_ERR_ARG for
+ * a NULL psi, scan, probe, eigen_weights or nearplane, eigen_probe NULL with
+ * C > 0, M < 1 or M > S with C > 0, S < 1, pw < 1, det < pw, H < 1, W < 1,
+ * nscan < 0, C < 0, M < 0, nscan > 2^31 - 1 or a detector of more items than
+ * one launch holds; TIKE_ERR_UNSUPPORTED for S > 16 or C * M > 16;
+ * nscan == 0 returns 0 without a launch. */
+int tike_eigen_wave_tangent(const void* psi, const void* dpsi, const float* scan,
+                            const float* dscan, const void* probe, const void* dprobe,
+                            const void* eigen_probe, const void* deigen_probe,
+                            const float* eigen_weights, const float* deigen_weights,
+                            int num_eigen, int eigen_modes, void* nearplane, long nscan, int S,
+                            int pw, int det, int H, int W, void* stream);
 
 /* The tangent of the intensity from a far plane and its tangent (tike_fft2 of
  * a plane above, with the forward scale):

@@ -108,9 +108,11 @@ and with no tangent at all only the primal launches.  `intensity` on
 ``torch.autograd.forward_ad`` dual tensors (any subset of psi, probe, scan)
 returns a dual whose tangent is this dI: `_Intensity.jvp` runs the same chunk
 loop.  The eigen-probe form and `multislice_intensity` have no forward-mode
-rule: under `forward_ad` they keep torch's own refusal ("you must implement
-the jvp function").  ``gauss_newton_product`` composes the two modes:
-J^T (weight * J v) by `intensity_jvp` and then the backward above.
+RULE: under `forward_ad` they keep torch's own refusal ("you must implement
+the jvp function"); their forward mode is a function each,
+`eigen_intensity_jvp` and `multislice_intensity_jvp` below.
+``gauss_newton_product`` composes the two modes: J^T (weight * J v) by
+`intensity_jvp` and then the backward above.
 
 Forward mode, several slices.  ``multislice_intensity_jvp(operator, psi, probe,
 scan, d_psi=, d_probe=, d_scan=, fly=...)`` returns (I, dI = J v) of
@@ -145,6 +147,35 @@ forward-mode RULE for `_MultisliceIntensity`: dual tensors stay refused, the
 function is the interface.  ``multislice_gauss_newton_product`` is
 `gauss_newton_product` for this model: the JVP without the primal intensity,
 then the backward of `multislice_intensity` with weight * dI upstream.
+
+Forward mode, eigen probes.  ``eigen_intensity_jvp(operator, psi, probe, scan,
+eigen_probe=, eigen_weights=, d_psi=, d_probe=, d_scan=, d_eigen_probe=,
+d_eigen_weights=, fly=...)`` returns (I, dI = J v) of `intensity(...,
+eigen_probe=, eigen_weights=)` for tangents of all five inputs (d_eigen_probe
+(1, C, M, pw, pw), d_eigen_weights (N, C + 1, S); eigen_probe=None is C = 0):
+the varying probe is linear in the planes and in the weights, so with P as
+above
+
+    dP[n,s]    = w[n,0,s] d_probe[s] + d_w[n,0,s] probe[s]
+               + sum_c (w[n,c+1,s] d_E[c,s] + d_w[n,c+1,s] E[c,s])    s < M
+                 (the first two terms alone for s >= M)
+    dpatch_n   = patch_n(d_psi) + d_scan[n,0] Dy_n(psi) + d_scan[n,1] Dx_n(psi)
+    dwave[n,s] = dpatch_n P[n,s] + patch_n(psi) dP[n,s]
+    dfar[n,s]  = F pad(dwave[n,s])
+    dI[f]      = sum_{n in frame f} sum_s 2 Re(conj(far[n,s]) dfar[n,s])
+
+Per chunk of whole frames -- half of `chunk_positions`, as above --
+
+    tike_ptycho_fwd (with the eigen probes: I has the bits of `intensity`) ->
+    tike_eigen_wave_tangent (P and dP built in registers, never stored;
+    d_scan and d_eigen_weights sliced to the chunk) -> tike_fft2 (in place,
+    forward scale) -> tike_intensity_tangent
+
+with no torch arithmetic; no tangent at all: only the primal launches.  There
+is no forward-mode rule for `_EigenIntensity` either: the function is the
+interface.  ``eigen_gauss_newton_product`` is `gauss_newton_product` for this
+model over the five inputs: the JVP without the primal intensity, then the
+backward of the eigen form with weight * dI upstream.
 """
 import importlib
 
@@ -512,8 +543,8 @@ def intensity(operator, psi, probe, scan, *, eigen_probe=None,
     gathered: where only some inputs vary, `intensity_jvp` with the others
     left None is the faster call).  The eigen-probe
     form below and `multislice_intensity` have none: under `forward_ad` they
-    raise torch's "you must implement the jvp function" (the forward mode of
-    several slices is the function `multislice_intensity_jvp`).
+    raise torch's "you must implement the jvp function" (their forward mode
+    is a function each: `eigen_intensity_jvp`, `multislice_intensity_jvp`).
 
     With eigen_weights the probe varies from position to position (not from
     frame to frame: any `fly`), as `get_varying_probe` has it: position n sees
@@ -589,12 +620,15 @@ def _jvp_chunks(op, psi, probe, scan, d_psi, d_probe, d_scan, fly, primal=True):
     return inten, tangent
 
 
-def _checked_tangents(name, psi, probe, scan, d_psi, d_probe, d_scan):
+def _checked_tangents(name, psi, probe, scan, d_psi, d_probe, d_scan,
+                      more=()):
     """A tangent matches its primal in type, dtype, shape and device; the
-    tangents detached and contiguous (None stays None)."""
+    tangents detached and contiguous (None stays None).  more: further
+    (what, primal, tangent) behind the three -- the eigen probes and their
+    weights."""
     out = []
     for what, x, t in (("psi", psi, d_psi), ("probe", probe, d_probe),
-                       ("scan", scan, d_scan)):
+                       ("scan", scan, d_scan)) + tuple(more):
         if t is None:
             out.append(None)
             continue
@@ -713,13 +747,14 @@ def gauss_newton_product(operator, psi, probe, scan, *, d_psi=None,
                                    grad_outputs=tangent)
 
 
-def _checked_product(name, operator, psi, scan, weight, fly, wrt):
+def _checked_product(name, operator, psi, scan, weight, fly, wrt, names=_WRT):
     """The `wrt` and `weight` refusals of the Gauss-Newton products; wrt as a
-    tuple."""
+    tuple.  names: what `wrt` may name."""
     wrt = tuple(wrt)
-    if not wrt or len(set(wrt)) != len(wrt) or any(w not in _WRT for w in wrt):
+    if not wrt or len(set(wrt)) != len(wrt) or any(w not in names
+                                                   for w in wrt):
         raise ValueError(
-            f"{name}: wrt must name some of {_WRT}, each once; got {wrt}")
+            f"{name}: wrt must name some of {names}, each once; got {wrt}")
     if weight is not None:
         if not isinstance(weight, torch.Tensor):
             raise TypeError(
@@ -1247,5 +1282,184 @@ def multislice_gauss_newton_product(operator, psi, probe, scan, *, d_psi=None,
     with torch.enable_grad():
         inten = (_Intensity if single else _MultisliceIntensity).apply(
             leaves["psi"], leaves["probe"], leaves["scan"], operator, fly)
+        return torch.autograd.grad(inten, [leaves[k] for k in wrt],
+                                   grad_outputs=tangent)
+
+
+# ------------------------------------------------ forward mode, eigen probes
+def _eigen_jvp_chunks(op, psi, probe, scan, eigen, weights, d_psi, d_probe,
+                      d_scan, d_eigen, d_weights, fly, primal=True):
+    """(I or None, dI): the chunk loop of `eigen_intensity_jvp` on contiguous
+    device tensors (eigen, d_eigen: None for C = 0); at least one tangent is
+    not None."""
+    from .ptycho.solvers.lstsq import chunk_positions
+    N, S = scan.shape[0], probe.shape[2]
+    C, M = (0, 0) if eigen is None else eigen.shape[1:3]
+    pw, det = op.probe_shape, op.detector_shape
+    H, W = psi.shape[-2:]
+    dev = psi.device
+    A.current_device()  # (hands the library its deterministic-mode scratch)
+    st = A.stream_ptr()
+    inten = (torch.empty((N // fly, det, det), dtype=torch.float32, device=dev)
+             if primal else None)
+    tangent = torch.empty((N // fly, det, det), dtype=torch.float32,
+                          device=dev)
+    if N == 0:
+        return inten, tangent
+    # the far plane and its tangent are both resident; whole frames
+    chunk = max(1, chunk_positions(S, det) // 2 // fly) * fly
+    rows = min(chunk, N)
+    far_all = torch.empty((rows, 1, S, det, det), dtype=torch.complex64,
+                          device=dev)
+    dfar_all = torch.empty_like(far_all)
+    fwd_scale = fft_scales(det, op.norm)[0]
+    for lo in range(0, N, chunk):
+        hi = min(N, lo + chunk)
+        n = hi - lo
+        sc, w = scan[lo:hi], weights[lo:hi]
+        far, dfar = far_all[:n], dfar_all[:n]
+        op.fwd_device(probe, sc, psi, eigen, w, out=far)
+        check(
+            lib.tike_eigen_wave_tangent(
+                A.ptr(psi), A.ptr(d_psi), A.ptr(sc),
+                None if d_scan is None else A.ptr(d_scan[lo:hi]),
+                A.ptr(probe), A.ptr(d_probe), A.ptr(eigen), A.ptr(d_eigen),
+                A.ptr(w),
+                None if d_weights is None else A.ptr(d_weights[lo:hi]), C, M,
+                A.ptr(dfar), n, S, pw, det, H, W, st),
+            "eigen_intensity_jvp (tangent exit waves)")
+        check(lib.tike_fft2(A.ptr(dfar), A.ptr(dfar), n * S, det, 0,
+                            fwd_scale, st),
+              "eigen_intensity_jvp (tangent far plane)")
+        # the S * fly planes of a frame are adjacent
+        check(
+            lib.tike_intensity_tangent(
+                A.ptr(far), A.ptr(dfar),
+                A.ptr(inten[lo // fly:]) if primal else None,
+                A.ptr(tangent[lo // fly:]), n // fly, S * fly, det * det, st),
+            "eigen_intensity_jvp (tangent intensity)")
+    return inten, tangent
+
+
+def _checked_eigen_jvp(name, operator, psi, probe, scan, eigen_probe,
+                       eigen_weights, d_psi, d_probe, d_scan, d_eigen_probe,
+                       d_eigen_weights, fly, check_positions):
+    """`_checked_jvp` for the eigen form: (fly, the five tangents)."""
+    if d_eigen_probe is not None and eigen_probe is None:
+        raise ValueError(
+            f"{name}: d_eigen_probe without eigen_probe (there is no eigen "
+            "probe it could be the tangent of)")
+    tangents = None
+    if all(isinstance(x, torch.Tensor)
+           for x in (psi, probe, scan, eigen_weights)) and isinstance(
+               eigen_probe, (torch.Tensor, type(None))):
+        # (host arrays: `_checked` below names them)
+        more = [("eigen_weights", eigen_weights, d_eigen_weights)]
+        if eigen_probe is not None:
+            more.insert(0, ("eigen_probe", eigen_probe, d_eigen_probe))
+        tangents = _checked_tangents(name, psi, probe, scan, d_psi, d_probe,
+                                     d_scan, more)
+        if eigen_probe is None:
+            tangents.insert(3, None)
+    if eigen_weights is None:
+        raise TypeError(
+            f"{name}: eigen_weights is required (without them `intensity_jvp` "
+            "is the forward mode of the model)")
+    fly = _checked(operator, psi, probe, scan, fly, check_positions, name=name,
+                   eigen_probe=eigen_probe, eigen_weights=eigen_weights)
+    return fly, tangents
+
+
+def eigen_intensity_jvp(operator, psi, probe, scan, *, eigen_probe=None,
+                        eigen_weights, d_psi=None, d_probe=None, d_scan=None,
+                        d_eigen_probe=None, d_eigen_weights=None, fly=1,
+                        check_positions=True):
+    """(I, dI): the intensities of `intensity(operator, psi, probe, scan,
+    eigen_probe=eigen_probe, eigen_weights=eigen_weights, fly=fly)` -- the
+    same bits -- and their directional derivative J v along the tangents
+    d_psi (1, H, W) complex64, d_probe (1, 1, S, pw, pw) complex64, d_scan
+    (N, 2) float32, d_eigen_probe (1, C, M, pw, pw) complex64 and
+    d_eigen_weights (N, C + 1, S) float32, each None (zero) or a device tensor
+    of its primal's shape, dtype and device.  Both (N // fly, det, det)
+    float32, outside any autograd graph.  eigen_weights is required;
+    eigen_probe=None with eigen_weights (N, 1, S) is C = 0.  Rows c + 1 of the
+    weights and of their tangent count for nothing in the modes s >= M.  The
+    derivative with respect to the positions is that of `scan.grad`: the
+    integer part of a position is held fixed.  With no tangent dI is zeros and
+    only the primal launches.  This function is the forward mode of the eigen
+    form: `intensity(..., eigen_weights=)` itself has no rule for
+    `torch.autograd.forward_ad` dual tensors and keeps torch's refusal there.
+
+    Raises what `intensity` raises for the eigen form (NotImplementedError,
+    TypeError, ValueError), TypeError without eigen_weights, ValueError for
+    d_eigen_probe without eigen_probe, and TypeError / ValueError for a
+    tangent that does not match its primal, before any launch.
+    """
+    fly, (d_psi, d_probe, d_scan, d_eigen, d_weights) = _checked_eigen_jvp(
+        "eigen_intensity_jvp", operator, psi, probe, scan, eigen_probe,
+        eigen_weights, d_psi, d_probe, d_scan, d_eigen_probe, d_eigen_weights,
+        fly, check_positions)
+    psi, probe, scan, weights = (x.detach().contiguous()
+                                 for x in (psi, probe, scan, eigen_weights))
+    eigen = None if eigen_probe is None else eigen_probe.detach().contiguous()
+    if all(t is None for t in (d_psi, d_probe, d_scan, d_eigen, d_weights)):
+        with torch.no_grad():
+            inten = _EigenIntensity.apply(psi, probe, scan, eigen, weights,
+                                          operator, fly)
+        return inten, torch.zeros_like(inten)
+    return _eigen_jvp_chunks(operator, psi, probe, scan, eigen, weights, d_psi,
+                             d_probe, d_scan, d_eigen, d_weights, fly)
+
+
+_EIGEN_WRT = ("psi", "probe", "scan", "eigen_probe", "eigen_weights")
+
+
+def eigen_gauss_newton_product(operator, psi, probe, scan, *, eigen_probe=None,
+                               eigen_weights, d_psi=None, d_probe=None,
+                               d_scan=None, d_eigen_probe=None,
+                               d_eigen_weights=None, weight=None, fly=1,
+                               wrt=_EIGEN_WRT, check_positions=True):
+    """`gauss_newton_product` for the eigen form of `intensity`:
+    J^T (weight * J v) for the tangents v of `eigen_intensity_jvp`, one tensor
+    per name in `wrt` (any of "psi", "probe", "scan", "eigen_probe",
+    "eigen_weights", in that order of `wrt`) in the `.grad` convention of
+    `intensity` (a complex input's part is d/dRe + i d/dIm; the weights' part
+    is exactly 0 in rows c + 1 of the modes s >= M).  weight: (N // fly, det,
+    det) float32 device tensor or None.
+
+    Composed of the JVP with the primal intensity not written and the backward
+    of `intensity(..., eigen_probe=, eigen_weights=)` with weight * dI for the
+    upstream gradient; only what `wrt` names is launched in the backward.  No
+    dual tensors: see `eigen_intensity_jvp`.
+
+    Raises what `eigen_intensity_jvp` raises, ValueError for names in `wrt`
+    other than the five (or none, or one twice) or for "eigen_probe" in `wrt`
+    with eigen_probe=None, TypeError / ValueError for a weight of another
+    type, dtype, shape or device.
+    """
+    name = "eigen_gauss_newton_product"
+    wrt = _checked_product(name, operator, psi, scan, weight, fly, wrt,
+                           names=_EIGEN_WRT)
+    if "eigen_probe" in wrt and eigen_probe is None:
+        raise ValueError(
+            f'{name}: "eigen_probe" in wrt with eigen_probe=None (there is no '
+            "eigen probe to differentiate with respect to)")
+    fly, tangents = _checked_eigen_jvp(
+        name, operator, psi, probe, scan, eigen_probe, eigen_weights, d_psi,
+        d_probe, d_scan, d_eigen_probe, d_eigen_weights, fly, check_positions)
+    leaves = {k: None if x is None else
+              x.detach().contiguous().requires_grad_(k in wrt)
+              for k, x in zip(_EIGEN_WRT, (psi, probe, scan, eigen_probe,
+                                           eigen_weights))}
+    if all(t is None for t in tangents):
+        return tuple(torch.zeros_like(leaves[k]) for k in wrt)
+    tangent = _eigen_jvp_chunks(
+        operator, *(None if leaves[k] is None else leaves[k].detach()
+                    for k in _EIGEN_WRT), *tangents, fly, primal=False)[1]
+    if weight is not None:
+        tangent = tangent * weight.detach()
+    with torch.enable_grad():
+        inten = _EigenIntensity.apply(*(leaves[k] for k in _EIGEN_WRT),
+                                      operator, fly)
         return torch.autograd.grad(inten, [leaves[k] for k in wrt],
                                    grad_outputs=tangent)
