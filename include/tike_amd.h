@@ -38,7 +38,7 @@ extern "C" {
  * A binding compares tike_abi_version() of the loaded library with the
  * TIKE_ABI_VERSION it was written against before its first call
  * (tike_amd/_lib.py does; INTEGRATION.md shows the check). */
-#define TIKE_ABI_VERSION 24
+#define TIKE_ABI_VERSION 25
 
 /* sha256 (64 hex digits) of the sources the library was built from: the PMC
  * traffic files under profiles/ carry it, and bench.py withholds a traffic
@@ -1403,6 +1403,70 @@ int tike_eigen_wave_tangent(const void* psi, const void* dpsi, const float* scan
  * returns 0 without a launch. */
 int tike_intensity_tangent(const void* farplane, const void* dfarplane, float* intensity,
                            float* dintensity, long nframe, int P, long npix, void* stream);
+
+/* The noise-model cost of a far plane and the table its backward takes (no
+ * reference counterpart; tike_amd.autograd.cost).  With
+ *   I[f][p] = sum_{j<P} |farplane[f][j][p]|^2
+ * (the bits of tike_intensity: planes ascending, a float32 running sum), d the
+ * counts and, per pixel, the cost term and gradient factor of
+ * tike_fly_farplane_gradient --
+ *   gaussian (model 0): (sqrt(I) - sqrt(d))^2,  l' = 1 - sqrt(d) / (sqrt(I) + 1e-9)
+ *   poisson  (model 1): I - d log(I + 1e-9),    l' = 1 - d / (I + 1e-9)
+ * -- from ONE read of the far plane:
+ *   costs[f]    = sum_{p measured} term(I, d) / num_measured        (unless NULL)
+ *   table[f][p] = upstream[f] l'(I, d) / num_measured   p measured  (unless NULL)
+ *               = 0 exactly                              p unmeasured
+ * farplane (nframe,P,npix) c64, P = fly * S: the positions and modes that
+ * expose frame f; it is not written.  data (nframe,npix) f32, or u16 with
+ * data_u16; measured (npix) u8 or NULL (every pixel measured); upstream
+ * (nframe) f32 or NULL (ones); costs (nframe) f32 and table (nframe,npix) f32,
+ * overwritten.  A count at an unmeasured pixel may be NaN: it is selected
+ * away, never multiplied.  costs carries the bits of
+ * tike_fly_farplane_gradient's costs on the same far plane: the same per-pixel
+ * terms, the same float64 sum in the same fixed order (lane, wave shuffles,
+ * the four waves).  The table is float32: upstream[f] / num_measured rounded
+ * once, times l'.  It is what tike_ifft2_crop_scaled, tike_ifft2_pass1_scaled
+ * and tike_farplane_scale take as the upstream gradient.  One workgroup per
+ * frame; 16-byte far-plane accesses with the counts and the mask requested
+ * alongside, the last npix % 4 pixels of a frame one per lane; any P; no
+ * atomics: two calls give the same bits.  No allocation.  Per frame
+ * P npix 8 bytes of far plane, npix 4 (or 2) of counts and npix of mask are
+ * read, npix 4 written.  TIKE_ERR_ARG for a NULL farplane or data, P < 1,
+ * npix < 1, num_measured < 1, a model other than 0 or 1, nframe < 0 or
+ * nframe > 2^31 - 1 (one workgroup per frame); nframe == 0 returns 0 without a
+ * launch. */
+int tike_cost_factor(const void* farplane, const void* data, int data_u16,
+                     const unsigned char* measured, const float* upstream, float* costs,
+                     float* table, long nframe, int P, long npix, int model,
+                     long num_measured, void* stream);
+
+/* The same from ONE read of a far plane and its tangent (no reference
+ * counterpart; tike_amd.autograd.cost_jvp and cost_gauss_newton_product).
+ * With I as above and
+ *   dI[f][p] = 2 sum_{j<P} Re( conj(farplane[f][j][p]) dfarplane[f][j][p] )
+ * (the bits of tike_intensity_tangent: a float32 running sum, doubled):
+ *   costs[f]    as tike_cost_factor writes it, the same bits      (unless NULL)
+ *   dcosts[f]   = sum_{p measured} l'(I, d) dI / num_measured      (unless NULL)
+ *                 the directional derivative of costs[f]: products and sum in
+ *                 float64, the fixed order of costs
+ *   table[f][p] = upstream[f] c / (num_measured (I + floor)) dI    p measured
+ *               = 0 exactly                                        p unmeasured
+ * c = 1/2 (gaussian: the Gauss-Newton curvature of the amplitude residual,
+ * 2 (d sqrt(I) / dI)^2 = 1 / (2 I)) or 1 (poisson: the Fisher information
+ * 1 / I).  floor = 0 with I = 0 on a measured pixel gives what float32 gives
+ * (inf x 0).  Shapes, the mask, upstream and the NaN rule as above; data may
+ * be NULL when costs and dcosts both are.  Neither far plane is written.  The
+ * table is float32: upstream[f] c / num_measured rounded once, divided by
+ * I + floor, times dI.  The layout of tike_cost_factor; no atomics: two calls
+ * give the same bits.  No allocation.  TIKE_ERR_ARG for a NULL farplane or
+ * dfarplane, data NULL with costs or dcosts, P < 1, npix < 1,
+ * num_measured < 1, a model other than 0 or 1, a negative or non-finite
+ * floor, nframe < 0 or nframe > 2^31 - 1; nframe == 0 returns 0 without a
+ * launch. */
+int tike_cost_curvature(const void* farplane, const void* dfarplane, const void* data,
+                        int data_u16, const unsigned char* measured, const float* upstream,
+                        float* costs, float* dcosts, float* table, long nframe, int P,
+                        long npix, int model, float floor, long num_measured, void* stream);
 
 /* ---- collectives: the per-minibatch gradient all-reduce over RCCL / xGMI,
  * one process (or thread) per GPU.  Replaces the serial peer-copy reduction of

@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("TIKE_AMD_LIB") or os.path.join(
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "tike_amd.h")
 
 # the header version this binding's prototypes were written against
-ABI_VERSION = 24
+ABI_VERSION = 25
 ERR_ARG = 1000001
 ERR_UNSUPPORTED = 1000002
 ERR_COMM = 2000000
@@ -205,6 +205,9 @@ _PROTOTYPES = {
     "tike_intensity_tangent": [_p, _p, _p, _p, _l, _i, _l, _p],
     "tike_eigen_wave_tangent": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i,
                                 _p, _l, _i, _i, _i, _i, _i, _p],
+    "tike_cost_factor": [_p, _p, _i, _p, _p, _p, _p, _l, _i, _l, _i, _l, _p],
+    "tike_cost_curvature": [_p, _p, _p, _i, _p, _p, _p, _p, _p, _l, _i, _l, _i,
+                            _f, _l, _p],
     "tike_comm_unique_id": [_p],
     "tike_comm_create": [_p, _i, _i, ctypes.POINTER(_p)],
     "tike_comm_destroy": [_p],

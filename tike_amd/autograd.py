@@ -176,6 +176,36 @@ is no forward-mode rule for `_EigenIntensity` either: the function is the
 interface.  ``eigen_gauss_newton_product`` is `gauss_newton_product` for this
 model over the five inputs: the JVP without the primal intensity, then the
 backward of the eigen form with weight * dI upstream.
+
+The noise-model cost.  ``cost(operator, data, psi, probe, scan, model=,
+measured_pixels=, eigen_probe=, eigen_weights=, fly=...)`` returns the
+per-frame costs of `Ptycho.cost`'s two noise models on the measured pixels,
+differentiable with respect to every input of the form it dispatches to
+(several slices, eigen probes, or plain):
+
+    gaussian: cost_f = mean_p (sqrt(I) - sqrt(d))^2,  l' = 1 - sqrt(d) / (sqrt(I) + 1e-9)
+    poisson:  cost_f = mean_p I - d log(I + 1e-9),    l' = 1 - d / (I + 1e-9)
+
+Forward, per chunk of whole frames: the form's forward -> tike_cost_factor
+(costs).  Backward, per chunk: the forward again -> tike_cost_factor (the
+chunk's table upstream_f l' / num_measured, 0 under the mask) -> the form's
+backward chain from the point where it reads the table (`_Back.run`,
+`_fused_back`, `_general_back`: shared with the three backwards above, which
+hand them ``g[lo // fly:hi // fly]``).  ``cost_jvp`` runs the form's
+forward-mode chunk loop with tike_cost_curvature in the place of
+tike_intensity_tangent: (costs, dcosts = sum_p l' dI / num_measured).
+``cost_gauss_newton_product`` is J^T diag(upstream_f c / (num_measured
+(I + floor))) J v, c = 1/2 (gaussian) or 1 (poisson): for one slice ONE chunk
+loop with the far plane resident --
+
+    the forward-mode launches of the form -> tike_cost_curvature (the chunk's
+    table) -> `_Back.run` on the SAME far plane (the scaled inverse writes
+    into the tangent's far plane)
+
+-- and for several slices the forward-mode chunks (the table over all frames)
+followed by the backward of `multislice_intensity`.  No tensor of
+N // fly * det * det elements exists in `cost`, `cost_jvp` or the one-slice
+product.
 """
 import importlib
 
@@ -299,6 +329,161 @@ def _checked(operator, psi, probe, scan, fly, check_positions,
     return fly
 
 
+class _Back:
+    """The backward chain of the one-slice forms behind the far plane, shared
+    by `_Intensity.backward`, `_EigenIntensity.backward`, the backward of
+    `cost` and the resident `cost_gauss_newton_product`: the buffers of a
+    chunk of at most `rows` positions, the accumulated gradients, and per
+    chunk the launches from the point where the upstream table is read.
+    weights (with eigen or None: C = 0) selects the eigen form, which swaps
+    tike_lstsq_gradients for tike_eigen_probe_gradients.  want: (psi, probe,
+    scan, eigen_probe, eigen_weights).  resident: the caller brings the far
+    plane and a second buffer of its size to `run`; none is allocated here."""
+
+    def __init__(self, op, fly, psi, probe, scan, want, rows, eigen=None,
+                 weights=None, resident=False):
+        from .ptycho.solvers.lstsq import _workspace
+        (self.want_psi, self.want_probe, self.want_scan, want_eigen,
+         want_weights) = want
+        self.op, self.fly = op, fly
+        self.psi, self.probe, self.scan = psi, probe, scan
+        self.eigen, self.weights = eigen, weights
+        self.want_eigen = bool(want_eigen) and eigen is not None
+        self.want_weights = bool(want_weights) and weights is not None
+        S = probe.shape[2]
+        C, M = eigen.shape[1:3] if eigen is not None else (0, 0)
+        pw, det = op.probe_shape, op.detector_shape
+        H, W = psi.shape[-2:]
+        dev = psi.device
+        # F^H = the unscaled inverse x the forward scale; the 2 of G goes along
+        self.scale = 2.0 * fft_scales(det, op.norm)[0]
+        self.scaled_inverse = det in _SCALED_INVERSE_SIZES
+        self.acc = (torch.zeros((2, H, W), dtype=torch.float32, device=dev)
+                    if self.want_psi else None)
+        self.gprobe = torch.zeros_like(probe) if self.want_probe else None
+        self.geigen = torch.zeros_like(eigen) if self.want_eigen else None
+        self.gweights = (torch.empty_like(weights) if self.want_weights
+                         else None)
+        self.gscan = torch.empty_like(scan) if self.want_scan else None
+        self.far_all = None if resident else torch.empty(
+            (rows, 1, S, det, det), dtype=torch.complex64, device=dev)
+        # (the scaled inverse must not work in place; the plain one may: None)
+        self.mid_all = (torch.empty((rows, 1, S, det, det),
+                                    dtype=torch.complex64, device=dev)
+                        if self.scaled_inverse and not resident else None)
+        self.chi_all = None if pw == det else torch.empty(
+            (rows, 1, S, pw, pw), dtype=torch.complex64, device=dev)
+        self.need_proj = self.want_psi or self.want_scan
+        self.objproj_all = (torch.empty((rows, pw, pw), dtype=torch.complex64,
+                                        device=dev)
+                            if self.need_proj else None)
+        # the pixel tiles' partial weight sums (include/tike_amd.h): float64
+        self.work = (_workspace(op).get(
+            "eigen_gradients_work",
+            (-(-pw * pw // 256), max(rows, 1), S + C * M), torch.float64, dev)
+                     if self.want_weights else None)
+
+    def forward(self, lo, hi):
+        """The far plane of the positions lo ... hi - 1 in the chunk's own
+        buffer."""
+        far = self.far_all[:hi - lo]
+        w = None if self.weights is None else self.weights[lo:hi]
+        if w is None:
+            self.op.fwd_device(self.probe, self.scan[lo:hi], self.psi, out=far)
+        else:
+            self.op.fwd_device(self.probe, self.scan[lo:hi], self.psi,
+                               self.eigen, w, out=far)
+        return far
+
+    def run(self, lo, hi, far, table, spare=None):
+        """The chain behind `far` (n, 1, S, det, det), which it may overwrite,
+        with table (n // fly, det, det) = dL/dI of the chunk's frames.  spare:
+        a buffer of far's shape for the scaled inverse to write to (resident
+        callers)."""
+        op, fly, st = self.op, self.fly, A.stream_ptr()
+        psi, probe = self.psi, self.probe
+        n, S = hi - lo, probe.shape[2]
+        pw, det = op.probe_shape, op.detector_shape
+        H, W = psi.shape[-2:]
+        sc = self.scan[lo:hi]
+        if self.scaled_inverse:
+            mid = spare if self.mid_all is None else self.mid_all[:n]
+        else:
+            mid = far
+        chi = mid if self.chi_all is None else self.chi_all[:n]
+        if self.scaled_inverse:
+            # S * fly planes share a frame's table
+            check(
+                lib.tike_ifft2_crop_scaled(A.ptr(far), A.ptr(table), S * fly,
+                                           A.ptr(mid), A.ptr(chi), n * S, det,
+                                           pw, self.scale, st),
+                "intensity backward (scaled ifft2 + crop)")
+        else:
+            check(
+                lib.tike_farplane_scale(A.ptr(far), A.ptr(table), n // fly,
+                                        S * fly, det * det, 2.0, st),
+                "intensity backward (upstream gradient)")
+            check(
+                lib.tike_ifft2_crop(A.ptr(far), A.ptr(mid), A.ptr(chi), n * S,
+                                    det, pw, 0.5 * self.scale, st),
+                "intensity backward (ifft2 + crop)")
+        objproj = self.objproj_all[:n] if self.need_proj else None
+        if self.weights is None:
+            check(
+                lib.tike_lstsq_gradients(A.ptr(chi), A.ptr(sc), A.ptr(psi),
+                                         A.ptr(probe), None, None, 0, 0, None,
+                                         None, A.ptr(self.gprobe),
+                                         A.ptr(objproj), n, S, pw, H, W, st),
+                "intensity backward (probe gradient + object projection)")
+        else:
+            eigen = self.eigen
+            C, M = eigen.shape[1:3] if eigen is not None else (0, 0)
+            check(
+                lib.tike_eigen_probe_gradients(
+                    A.ptr(chi), A.ptr(sc), A.ptr(psi), A.ptr(probe),
+                    A.ptr(eigen), A.ptr(self.weights[lo:hi]), C, M,
+                    A.ptr(self.gprobe), A.ptr(self.geigen),
+                    A.ptr(self.gweights[lo:hi]) if self.want_weights else None,
+                    A.ptr(objproj), A.ptr(self.work), n, S, pw, H, W, st),
+                "intensity backward (probe, eigen probe and weight gradients "
+                "+ object projection)")
+        if self.want_psi:
+            check(
+                lib.tike_scatter_patches(A.ptr(objproj), A.ptr(sc),
+                                         A.ptr(self.acc), n, pw, H, W, st),
+                "intensity backward (object gradient)")
+        if self.want_scan:
+            check(
+                lib.tike_scan_gradient(A.ptr(objproj), A.ptr(sc), A.ptr(psi),
+                                       A.ptr(self.gscan[lo:hi]), n, pw, H, W,
+                                       st),
+                "intensity backward (scan gradient)")
+
+    def result(self):
+        """(psi, probe, scan, eigen_probe, eigen_weights) gradients, None
+        where not wanted."""
+        gpsi = (torch.complex(self.acc[0], self.acc[1])[None]
+                if self.want_psi else None)
+        return gpsi, self.gprobe, self.gscan, self.geigen, self.gweights
+
+
+def _backward_chunks(op, fly, psi, probe, scan, want, table_of, eigen=None,
+                     weights=None):
+    """The backward of the one-slice forms: per chunk of whole frames the
+    recomputed forward, the upstream table of the chunk -- table_of(lo, hi,
+    far), frames lo // fly ... hi // fly - 1 -- and the chain of `_Back`."""
+    from .ptycho.solvers.lstsq import chunk_positions
+    N, S = scan.shape[0], probe.shape[2]
+    chunk = max(1, chunk_positions(S, op.detector_shape) // fly) * fly
+    back = _Back(op, fly, psi, probe, scan, want, min(chunk, N), eigen,
+                 weights)
+    for lo in range(0, N, chunk):
+        hi = min(N, lo + chunk)
+        far = back.forward(lo, hi)
+        back.run(lo, hi, far, table_of(lo, hi, far))
+    return back.result()
+
+
 class _Intensity(torch.autograd.Function):
 
     @staticmethod
@@ -336,77 +521,14 @@ class _Intensity(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        from .ptycho.solvers.lstsq import chunk_positions
         psi, probe, scan = ctx.saved_tensors
-        op, fly = ctx.operator, ctx.fly
-        want_psi, want_probe, want_scan = ctx.needs_input_grad[:3]
-        N, S = scan.shape[0], probe.shape[2]
-        pw, det = op.probe_shape, op.detector_shape
-        H, W = psi.shape[-2:]
-        dev = psi.device
+        fly = ctx.fly
         g = g.to(torch.float32).contiguous()
-        st = A.stream_ptr()
-        # F^H = the unscaled inverse x the forward scale; the 2 of G goes along
-        scale = 2.0 * fft_scales(det, op.norm)[0]
-        scaled_inverse = det in _SCALED_INVERSE_SIZES
-        acc = (torch.zeros((2, H, W), dtype=torch.float32, device=dev)
-               if want_psi else None)
-        gprobe = (torch.zeros_like(probe) if want_probe else None)
-        gscan = (torch.empty_like(scan) if want_scan else None)
-        chunk = max(1, chunk_positions(S, det) // fly) * fly  # whole frames
-        rows = min(chunk, N)
-        far_all = torch.empty((rows, 1, S, det, det), dtype=torch.complex64,
-                              device=dev)
-        # (the scaled inverse must not work in place; the plain one may)
-        mid_all = torch.empty_like(far_all) if scaled_inverse else far_all
-        chi_all = mid_all if pw == det else torch.empty(
-            (rows, 1, S, pw, pw), dtype=torch.complex64, device=dev)
-        need_proj = want_psi or want_scan
-        objproj_all = (torch.empty((rows, pw, pw), dtype=torch.complex64,
-                                   device=dev) if need_proj else None)
-        for lo in range(0, N, chunk):
-            hi = min(N, lo + chunk)
-            n = hi - lo
-            sc = scan[lo:hi]
-            far, mid, chi = far_all[:n], mid_all[:n], chi_all[:n]
-            table = g[lo // fly:hi // fly]
-            op.fwd_device(probe, sc, psi, out=far)
-            if scaled_inverse:
-                # S * fly planes share a frame's table
-                check(
-                    lib.tike_ifft2_crop_scaled(A.ptr(far), A.ptr(table),
-                                               S * fly, A.ptr(mid), A.ptr(chi),
-                                               n * S, det, pw, scale, st),
-                    "intensity backward (scaled ifft2 + crop)")
-            else:
-                check(
-                    lib.tike_farplane_scale(A.ptr(far), A.ptr(table), n // fly,
-                                            S * fly, det * det, 2.0, st),
-                    "intensity backward (upstream gradient)")
-                check(
-                    lib.tike_ifft2_crop(A.ptr(far), A.ptr(mid), A.ptr(chi),
-                                        n * S, det, pw, 0.5 * scale, st),
-                    "intensity backward (ifft2 + crop)")
-            objproj = objproj_all[:n] if need_proj else None
-            check(
-                lib.tike_lstsq_gradients(A.ptr(chi), A.ptr(sc), A.ptr(psi),
-                                         A.ptr(probe), None, None, 0, 0, None,
-                                         None, A.ptr(gprobe), A.ptr(objproj),
-                                         n, S, pw, H, W, st),
-                "intensity backward (probe gradient + object projection)")
-            if want_psi:
-                check(
-                    lib.tike_scatter_patches(A.ptr(objproj), A.ptr(sc),
-                                             A.ptr(acc), n, pw, H, W, st),
-                    "intensity backward (object gradient)")
-            if want_scan:
-                check(
-                    lib.tike_scan_gradient(A.ptr(objproj), A.ptr(sc),
-                                           A.ptr(psi), A.ptr(gscan[lo:hi]), n,
-                                           pw, H, W, st),
-                    "intensity backward (scan gradient)")
-        gpsi = torch.complex(acc[0], acc[1])[None] if want_psi else None
-        return gpsi, gprobe, gscan, None, None
+        want = tuple(ctx.needs_input_grad[:3]) + (False, False)
+        grads = _backward_chunks(
+            ctx.operator, fly, psi, probe, scan, want,
+            lambda lo, hi, far: g[lo // fly:hi // fly])
+        return grads[0], grads[1], grads[2], None, None
 
 
 class _EigenIntensity(torch.autograd.Function):
@@ -439,91 +561,15 @@ class _EigenIntensity(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        from .ptycho.solvers.lstsq import _workspace, chunk_positions
         psi, probe, scan, weights = ctx.saved_tensors[:4]
         eigen = ctx.saved_tensors[4] if ctx.eigen else None
-        op, fly = ctx.operator, ctx.fly
-        (want_psi, want_probe, want_scan, want_eigen,
-         want_weights) = ctx.needs_input_grad[:5]
-        want_eigen = want_eigen and ctx.eigen
-        N, S = scan.shape[0], probe.shape[2]
-        C, M = eigen.shape[1:3] if ctx.eigen else (0, 0)
-        pw, det = op.probe_shape, op.detector_shape
-        H, W = psi.shape[-2:]
-        dev = psi.device
+        fly = ctx.fly
         g = g.to(torch.float32).contiguous()
-        st = A.stream_ptr()
-        # F^H = the unscaled inverse x the forward scale; the 2 of G goes along
-        scale = 2.0 * fft_scales(det, op.norm)[0]
-        scaled_inverse = det in _SCALED_INVERSE_SIZES
-        acc = (torch.zeros((2, H, W), dtype=torch.float32, device=dev)
-               if want_psi else None)
-        gprobe = torch.zeros_like(probe) if want_probe else None
-        geigen = torch.zeros_like(eigen) if want_eigen else None
-        gweights = torch.empty_like(weights) if want_weights else None
-        gscan = torch.empty_like(scan) if want_scan else None
-        chunk = max(1, chunk_positions(S, det) // fly) * fly  # whole frames
-        rows = min(chunk, N)
-        far_all = torch.empty((rows, 1, S, det, det), dtype=torch.complex64,
-                              device=dev)
-        # (the scaled inverse must not work in place; the plain one may)
-        mid_all = torch.empty_like(far_all) if scaled_inverse else far_all
-        chi_all = mid_all if pw == det else torch.empty(
-            (rows, 1, S, pw, pw), dtype=torch.complex64, device=dev)
-        need_proj = want_psi or want_scan
-        objproj_all = (torch.empty((rows, pw, pw), dtype=torch.complex64,
-                                   device=dev) if need_proj else None)
-        # the pixel tiles' partial weight sums (include/tike_amd.h): float64
-        work = (_workspace(op).get(
-            "eigen_gradients_work",
-            (-(-pw * pw // 256), max(rows, 1), S + C * M), torch.float64, dev)
-                if want_weights else None)
-        for lo in range(0, N, chunk):
-            hi = min(N, lo + chunk)
-            n = hi - lo
-            sc, w = scan[lo:hi], weights[lo:hi]
-            far, mid, chi = far_all[:n], mid_all[:n], chi_all[:n]
-            table = g[lo // fly:hi // fly]
-            op.fwd_device(probe, sc, psi, eigen, w, out=far)
-            if scaled_inverse:
-                # S * fly planes share a frame's table
-                check(
-                    lib.tike_ifft2_crop_scaled(A.ptr(far), A.ptr(table),
-                                               S * fly, A.ptr(mid), A.ptr(chi),
-                                               n * S, det, pw, scale, st),
-                    "intensity backward (scaled ifft2 + crop)")
-            else:
-                check(
-                    lib.tike_farplane_scale(A.ptr(far), A.ptr(table), n // fly,
-                                            S * fly, det * det, 2.0, st),
-                    "intensity backward (upstream gradient)")
-                check(
-                    lib.tike_ifft2_crop(A.ptr(far), A.ptr(mid), A.ptr(chi),
-                                        n * S, det, pw, 0.5 * scale, st),
-                    "intensity backward (ifft2 + crop)")
-            objproj = objproj_all[:n] if need_proj else None
-            check(
-                lib.tike_eigen_probe_gradients(
-                    A.ptr(chi), A.ptr(sc), A.ptr(psi), A.ptr(probe),
-                    A.ptr(eigen), A.ptr(w), C, M, A.ptr(gprobe),
-                    A.ptr(geigen),
-                    A.ptr(gweights[lo:hi]) if want_weights else None,
-                    A.ptr(objproj), A.ptr(work), n, S, pw, H, W, st),
-                "intensity backward (probe, eigen probe and weight gradients "
-                "+ object projection)")
-            if want_psi:
-                check(
-                    lib.tike_scatter_patches(A.ptr(objproj), A.ptr(sc),
-                                             A.ptr(acc), n, pw, H, W, st),
-                    "intensity backward (object gradient)")
-            if want_scan:
-                check(
-                    lib.tike_scan_gradient(A.ptr(objproj), A.ptr(sc),
-                                           A.ptr(psi), A.ptr(gscan[lo:hi]), n,
-                                           pw, H, W, st),
-                    "intensity backward (scan gradient)")
-        gpsi = torch.complex(acc[0], acc[1])[None] if want_psi else None
-        return gpsi, gprobe, gscan, geigen, gweights, None, None
+        grads = _backward_chunks(
+            ctx.operator, fly, psi, probe, scan,
+            tuple(ctx.needs_input_grad[:5]),
+            lambda lo, hi, far: g[lo // fly:hi // fly], eigen, weights)
+        return grads + (None, None)
 
 
 def intensity(operator, psi, probe, scan, *, eigen_probe=None,
@@ -572,9 +618,45 @@ def intensity(operator, psi, probe, scan, *, eigen_probe=None,
 
 
 # -------------------------------------------------------------- forward mode
-def _jvp_chunks(op, psi, probe, scan, d_psi, d_probe, d_scan, fly, primal=True):
+def _tangent_sink(inten, tangent, fly, what):
+    """What the forward-mode chunk loops do with a chunk's far plane and its
+    tangent unless told otherwise: tike_intensity_tangent into the frames'
+    rows of `tangent` (and of `inten` unless None)."""
+
+    def sink(lo, hi, far, dfar):
+        # the S * fly planes of a frame are adjacent
+        P = far.shape[-3] * fly
+        check(
+            lib.tike_intensity_tangent(
+                A.ptr(far), A.ptr(dfar),
+                None if inten is None else A.ptr(inten[lo // fly:]),
+                A.ptr(tangent[lo // fly:]), (hi - lo) // fly, P,
+                far.shape[-1] * far.shape[-2], A.stream_ptr()),
+            f"{what} (tangent intensity)")
+
+    return sink
+
+
+def _jvp_outputs(op, psi, scan, fly, primal, sink):
+    """(I or None, dI) to fill, or (None, None) where a sink takes the far
+    planes."""
+    if sink is not None:
+        return None, None
+    det, frames = op.detector_shape, scan.shape[0] // fly
+    return (torch.empty((frames, det, det), dtype=torch.float32,
+                        device=psi.device) if primal else None,
+            torch.empty((frames, det, det), dtype=torch.float32,
+                        device=psi.device))
+
+
+def _jvp_chunks(op, psi, probe, scan, d_psi, d_probe, d_scan, fly, primal=True,
+                sink=None):
     """(I or None, dI): the chunk loop of `intensity_jvp` and `_Intensity.jvp`
-    on contiguous device tensors; at least one tangent is not None."""
+    on contiguous device tensors; at least one tangent is not None.  sink(lo,
+    hi, far, dfar): called per chunk in the place of tike_intensity_tangent
+    (`cost_jvp`, `cost_gauss_newton_product`; both far planes are its to
+    overwrite); then (None, None) is returned and no frame-sized tensor
+    exists."""
     from .ptycho.solvers.lstsq import chunk_positions
     N, S = scan.shape[0], probe.shape[2]
     pw, det = op.probe_shape, op.detector_shape
@@ -582,12 +664,11 @@ def _jvp_chunks(op, psi, probe, scan, d_psi, d_probe, d_scan, fly, primal=True):
     dev = psi.device
     A.current_device()  # (hands the library its deterministic-mode scratch)
     st = A.stream_ptr()
-    inten = (torch.empty((N // fly, det, det), dtype=torch.float32, device=dev)
-             if primal else None)
-    tangent = torch.empty((N // fly, det, det), dtype=torch.float32,
-                          device=dev)
+    inten, tangent = _jvp_outputs(op, psi, scan, fly, primal, sink)
     if N == 0:
         return inten, tangent
+    if sink is None:
+        sink = _tangent_sink(inten, tangent, fly, "intensity_jvp")
     # the far plane and its tangent are both resident; whole frames
     chunk = max(1, chunk_positions(S, det) // 2 // fly) * fly
     rows = min(chunk, N)
@@ -610,13 +691,7 @@ def _jvp_chunks(op, psi, probe, scan, d_psi, d_probe, d_scan, fly, primal=True):
         check(lib.tike_fft2(A.ptr(dfar), A.ptr(dfar), n * S, det, 0,
                             fwd_scale, st),
               "intensity_jvp (tangent far plane)")
-        # the S * fly planes of a frame are adjacent
-        check(
-            lib.tike_intensity_tangent(
-                A.ptr(far), A.ptr(dfar),
-                A.ptr(inten[lo // fly:]) if primal else None,
-                A.ptr(tangent[lo // fly:]), n // fly, S * fly, det * det, st),
-            "intensity_jvp (tangent intensity)")
+        sink(lo, hi, far, dfar)
     return inten, tangent
 
 
@@ -853,7 +928,8 @@ def _general_far(op, psi, sc, probe):
     return op.propagation.fwd(wave, overwrite=True), beams
 
 
-def _fused_back(op, psi, sc, probe, table, fly, bufs, want, acc, gprobe):
+def _fused_back(op, psi, sc, probe, table_of, fly, bufs, want, acc,
+                gprobe):
     """One chunk of the backward on the two-pass kernels: the launches of
     cgrad's `_multislice_chunk_fused` with the upstream gradient for the cost
     kernel and F^H for the last transform's inverse.  Leaves objproj_d in
@@ -868,6 +944,7 @@ def _fused_back(op, psi, sc, probe, table, fly, bufs, want, acc, gprobe):
     fwd_scale, inv_scale = fft_scales(det, op.norm)
     prop = op.diffraction.propagation._propagator((det, det), psi.device)
     far = _fused_far(op, psi, sc, probe, far, beams)
+    table = table_of(far)
     mid = mid[:n]
     if PASS1_TAKES_TABLE:
         # S * fly planes share a frame's table
@@ -936,10 +1013,11 @@ def _fused_back(op, psi, sc, probe, table, fly, bufs, want, acc, gprobe):
             "slice)")
 
 
-def _general_back(op, psi, sc, probe, table, fly, objproj, want, acc, gprobe):
+def _general_back(op, psi, sc, probe, table_of, fly, objproj, want, acc,
+                  gprobe):
     """One chunk of the backward through the general operators, as cgrad's
-    `_multislice_chunk_general` walks back; objproj (D, nmax, pw, pw) or
-    None."""
+    `_multislice_chunk_general` walks back; table_of(far) is the upstream
+    table of the chunk's frames; objproj (D, nmax, pw, pw) or None."""
     want_psi, want_probe, want_scan = want
     D, (H, W) = psi.shape[0], psi.shape[-2:]
     n, S, det = sc.shape[0], probe.shape[-3], op.detector_shape
@@ -947,6 +1025,7 @@ def _general_back(op, psi, sc, probe, table, fly, objproj, want, acc, gprobe):
     need_proj = want_psi or want_scan
     st = A.stream_ptr()
     far, beams = _general_far(op, psi, sc, probe)
+    table = table_of(far)
     check(
         lib.tike_farplane_scale(A.ptr(far), A.ptr(table), n // fly, S * fly,
                                 det * det, 2.0, st),
@@ -1027,44 +1106,56 @@ class _MultisliceIntensity(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g):
         psi, probe, scan = ctx.saved_tensors
-        op, fly = ctx.operator, ctx.fly
-        want = want_psi, want_probe, want_scan = ctx.needs_input_grad[:3]
-        D, (H, W) = psi.shape[0], psi.shape[-2:]
-        N, pw = scan.shape[0], op.probe_shape
-        dev = psi.device
+        fly = ctx.fly
         g = g.to(torch.float32).contiguous()
-        acc = (torch.zeros((D, 2, H, W), dtype=torch.float32, device=dev)
-               if want_psi else None)
-        gprobe = torch.zeros_like(probe) if want_probe else None
-        gscan = torch.empty_like(scan) if want_scan else None
-        fused = _fused_route(op, probe)
-        chunk = _slices_chunk(op, psi, probe, fly, fused)
-        nmax = min(chunk, N)
+        grads = _multislice_backward_chunks(
+            ctx.operator, fly, psi, probe, scan,
+            tuple(ctx.needs_input_grad[:3]),
+            lambda lo, hi, far: g[lo // fly:hi // fly])
+        return grads + (None, None)
+
+
+def _multislice_backward_chunks(op, fly, psi, probe, scan, want, table_of):
+    """The backward of `multislice_intensity`, shared with the backward of
+    `cost`: per chunk of whole frames `_fused_back` or `_general_back` with
+    the upstream table table_of(lo, hi, far) of the chunk's frames, then the
+    scan gradient over the D objproj planes.  (psi, probe, scan) gradients."""
+    want_psi, want_probe, want_scan = want
+    D, (H, W) = psi.shape[0], psi.shape[-2:]
+    N, pw = scan.shape[0], op.probe_shape
+    dev = psi.device
+    acc = (torch.zeros((D, 2, H, W), dtype=torch.float32, device=dev)
+           if want_psi else None)
+    gprobe = torch.zeros_like(probe) if want_probe else None
+    gscan = torch.empty_like(scan) if want_scan else None
+    fused = _fused_route(op, probe)
+    chunk = _slices_chunk(op, psi, probe, fly, fused)
+    nmax = min(chunk, N)
+    if fused:
+        bufs = _fused_buffers(op, psi, probe, max(nmax, 1))
+        objproj = bufs[3]
+    else:
+        objproj = (torch.empty((D, nmax, pw, pw), dtype=torch.complex64,
+                               device=dev)
+                   if want_psi or want_scan else None)
+    for lo in range(0, N, chunk):
+        hi = min(N, lo + chunk)
+        sc = scan[lo:hi]
+        of = lambda far, lo=lo, hi=hi: table_of(lo, hi, far)
         if fused:
-            bufs = _fused_buffers(op, psi, probe, max(nmax, 1))
-            objproj = bufs[3]
+            _fused_back(op, psi, sc, probe, of, fly, bufs, want, acc, gprobe)
         else:
-            objproj = (torch.empty((D, nmax, pw, pw), dtype=torch.complex64,
-                                   device=dev)
-                       if want_psi or want_scan else None)
-        for lo in range(0, N, chunk):
-            hi = min(N, lo + chunk)
-            sc, table = scan[lo:hi], g[lo // fly:hi // fly]
-            if fused:
-                _fused_back(op, psi, sc, probe, table, fly, bufs, want, acc,
-                            gprobe)
-            else:
-                _general_back(op, psi, sc, probe, table, fly, objproj, want,
-                              acc, gprobe)
-            if want_scan:
-                check(
-                    lib.tike_scan_gradient_slices(
-                        A.ptr(objproj), nmax * pw * pw, A.ptr(sc), A.ptr(psi),
-                        A.ptr(gscan[lo:hi]), hi - lo, D, pw, H, W,
-                        A.stream_ptr()),
-                    "multislice_intensity backward (scan gradient)")
-        gpsi = torch.complex(acc[:, 0], acc[:, 1]) if want_psi else None
-        return gpsi, gprobe, gscan, None, None
+            _general_back(op, psi, sc, probe, of, fly, objproj, want, acc,
+                          gprobe)
+        if want_scan:
+            check(
+                lib.tike_scan_gradient_slices(
+                    A.ptr(objproj), nmax * pw * pw, A.ptr(sc), A.ptr(psi),
+                    A.ptr(gscan[lo:hi]), hi - lo, D, pw, H, W,
+                    A.stream_ptr()),
+                "multislice_intensity backward (scan gradient)")
+    gpsi = torch.complex(acc[:, 0], acc[:, 1]) if want_psi else None
+    return gpsi, gprobe, gscan
 
 
 def multislice_intensity(operator, psi, probe, scan, *, fly=1,
@@ -1112,22 +1203,21 @@ other in profiles/autograd_multislice_jvp.md; the tests compare them."""
 
 
 def _multislice_jvp_chunks(op, psi, probe, scan, d_psi, d_probe, d_scan, fly,
-                           primal=True):
+                           primal=True, sink=None):
     """(I or None, dI): the chunk loop of `multislice_intensity_jvp` for
     D > 1 slices on contiguous device tensors; at least one tangent is not
-    None."""
+    None.  sink: as in `_jvp_chunks`."""
     from .ptycho.solvers.lstsq import _workspace
     D, (H, W) = psi.shape[0], psi.shape[-2:]
     N, S, det = scan.shape[0], probe.shape[2], op.detector_shape
     dev = psi.device
     A.current_device()  # (hands the library its deterministic-mode scratch)
     st = A.stream_ptr()
-    inten = (torch.empty((N // fly, det, det), dtype=torch.float32, device=dev)
-             if primal else None)
-    tangent = torch.empty((N // fly, det, det), dtype=torch.float32,
-                          device=dev)
+    inten, tangent = _jvp_outputs(op, psi, scan, fly, primal, sink)
     if N == 0:
         return inten, tangent
+    if sink is None:
+        sink = _tangent_sink(inten, tangent, fly, "multislice_intensity_jvp")
     fused = _fused_route(op, probe)
     # one set more than the forward: the tangent (the general route keeps the
     # forward's chunk, which bounds a launch, not the memory)
@@ -1197,13 +1287,7 @@ def _multislice_jvp_chunks(op, psi, probe, scan, d_psi, d_probe, d_scan, fly,
         check(lib.tike_fft2(A.ptr(dwave), A.ptr(dwave), n * S, det, 0,
                             fwd_scale, st),
               "multislice_intensity_jvp (tangent far plane)")
-        # the S * fly planes of a frame are adjacent
-        check(
-            lib.tike_intensity_tangent(
-                A.ptr(far), A.ptr(dwave),
-                A.ptr(inten[lo // fly:]) if primal else None,
-                A.ptr(tangent[lo // fly:]), n // fly, S * fly, det * det, st),
-            "multislice_intensity_jvp (tangent intensity)")
+        sink(lo, hi, far, dwave)
     return inten, tangent
 
 
@@ -1288,10 +1372,10 @@ def multislice_gauss_newton_product(operator, psi, probe, scan, *, d_psi=None,
 
 # ------------------------------------------------ forward mode, eigen probes
 def _eigen_jvp_chunks(op, psi, probe, scan, eigen, weights, d_psi, d_probe,
-                      d_scan, d_eigen, d_weights, fly, primal=True):
+                      d_scan, d_eigen, d_weights, fly, primal=True, sink=None):
     """(I or None, dI): the chunk loop of `eigen_intensity_jvp` on contiguous
     device tensors (eigen, d_eigen: None for C = 0); at least one tangent is
-    not None."""
+    not None.  sink: as in `_jvp_chunks`."""
     from .ptycho.solvers.lstsq import chunk_positions
     N, S = scan.shape[0], probe.shape[2]
     C, M = (0, 0) if eigen is None else eigen.shape[1:3]
@@ -1300,12 +1384,11 @@ def _eigen_jvp_chunks(op, psi, probe, scan, eigen, weights, d_psi, d_probe,
     dev = psi.device
     A.current_device()  # (hands the library its deterministic-mode scratch)
     st = A.stream_ptr()
-    inten = (torch.empty((N // fly, det, det), dtype=torch.float32, device=dev)
-             if primal else None)
-    tangent = torch.empty((N // fly, det, det), dtype=torch.float32,
-                          device=dev)
+    inten, tangent = _jvp_outputs(op, psi, scan, fly, primal, sink)
     if N == 0:
         return inten, tangent
+    if sink is None:
+        sink = _tangent_sink(inten, tangent, fly, "eigen_intensity_jvp")
     # the far plane and its tangent are both resident; whole frames
     chunk = max(1, chunk_positions(S, det) // 2 // fly) * fly
     rows = min(chunk, N)
@@ -1331,13 +1414,7 @@ def _eigen_jvp_chunks(op, psi, probe, scan, eigen, weights, d_psi, d_probe,
         check(lib.tike_fft2(A.ptr(dfar), A.ptr(dfar), n * S, det, 0,
                             fwd_scale, st),
               "eigen_intensity_jvp (tangent far plane)")
-        # the S * fly planes of a frame are adjacent
-        check(
-            lib.tike_intensity_tangent(
-                A.ptr(far), A.ptr(dfar),
-                A.ptr(inten[lo // fly:]) if primal else None,
-                A.ptr(tangent[lo // fly:]), n // fly, S * fly, det * det, st),
-            "eigen_intensity_jvp (tangent intensity)")
+        sink(lo, hi, far, dfar)
     return inten, tangent
 
 
@@ -1463,3 +1540,437 @@ def eigen_gauss_newton_product(operator, psi, probe, scan, *, eigen_probe=None,
                                       operator, fly)
         return torch.autograd.grad(inten, [leaves[k] for k in wrt],
                                    grad_outputs=tangent)
+
+
+# ------------------------------------------------- the noise-model cost
+_MODELS = {"gaussian": 0, "poisson": 1}
+"""The noise models of `Ptycho.cost` and their number in the C ABI."""
+
+COST_FLOOR = 1e-9
+"""The project's guard (`1e-9` in the factors of both models): the default
+`floor` of `cost_gauss_newton_product`."""
+
+
+def _checked_cost(name, operator, data, measured_pixels, model, psi, probe,
+                  scan, eigen_probe, eigen_weights, fly, check_positions,
+                  checked):
+    """Every refusal of the cost functions, none of which needs a device until
+    the last: (fly, whatever `checked` returns besides, counts, mask or None,
+    num_measured, the model's number).  checked(slices): the form's own
+    `_checked*` call, which returns fly or (fly, tangents)."""
+    if not isinstance(data, torch.Tensor):
+        raise TypeError(
+            f"{name}: data must be a torch device tensor, not "
+            f"{type(data).__name__}")
+    if data.dtype not in (torch.float32, torch.uint16):
+        raise TypeError(
+            f"{name}: data must be torch.float32 or torch.uint16, not "
+            f"{data.dtype}")
+    det = operator.detector_shape
+    frames = _frames(scan, fly)
+    if data.ndim != 3 or tuple(data.shape[1:]) != (det, det) or (
+            frames is not None and data.shape[0] != frames):
+        raise ValueError(
+            f"{name}: data must be (N // fly, det, det) = "
+            f"({'?' if frames is None else frames}, {det}, {det}), not "
+            f"{tuple(data.shape)}")
+    mask, num_measured = None, det * det
+    if measured_pixels is not None:
+        mask = measured_pixels
+        if not isinstance(mask, torch.Tensor):
+            raise TypeError(
+                f"{name}: measured_pixels must be a torch device tensor, not "
+                f"{type(mask).__name__}")
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(
+                f"{name}: measured_pixels must be torch.bool or torch.uint8, "
+                f"not {mask.dtype}")
+        if tuple(mask.shape) != (det, det):
+            raise ValueError(
+                f"{name}: measured_pixels must be ({det}, {det}), not "
+                f"{tuple(mask.shape)}")
+        num_measured = int((mask != 0).sum())
+        if num_measured == 0:
+            raise ValueError(
+                f"{name}: measured_pixels measures no pixel (the cost is a "
+                "mean over the measured pixels)")
+    if model not in _MODELS:
+        raise ValueError(
+            f"{name}: unknown noise model {model!r}; one of "
+            f"{tuple(_MODELS)}")
+    slices = isinstance(psi, torch.Tensor) and psi.ndim == 3 and psi.shape[0] > 1
+    if slices and (eigen_weights is not None or eigen_probe is not None):
+        raise NotImplementedError(
+            f"{name}: several slices (psi.shape[0] = {psi.shape[0]}) with "
+            "eigen probes: multislice_intensity has no varying probe")
+    out = checked(slices)
+    for what, x in (("data", data), ("measured_pixels", mask)):
+        if x is not None and x.device.type != "cuda":
+            raise TypeError(
+                f"{name}: {what} lives on {x.device}; tike_amd runs on the "
+                "GPU only and there is no CPU fallback")
+    if mask is not None:
+        mask = (mask != 0).to(torch.uint8).contiguous()
+    return out, data.detach().contiguous(), mask, num_measured, _MODELS[model]
+
+
+class _Counts:
+    """The counts, the mask and the noise model of one call, and the two
+    entries on a chunk's far plane."""
+
+    def __init__(self, data, mask, num_measured, model, fly):
+        self.data, self.mask, self.nm = data, mask, num_measured
+        self.model, self.fly = model, fly
+        self.u16 = int(data.dtype == torch.uint16)
+
+    def factor(self, lo, hi, far, upstream, costs, table):
+        """tike_cost_factor on the frames of the positions lo ... hi - 1."""
+        fly = self.fly
+        flo, nf = lo // fly, (hi - lo) // fly
+        check(
+            lib.tike_cost_factor(
+                A.ptr(far), A.ptr(self.data[flo:]), self.u16,
+                A.ptr(self.mask),
+                None if upstream is None else A.ptr(upstream[flo:]),
+                None if costs is None else A.ptr(costs[flo:]), A.ptr(table),
+                nf, far.shape[-3] * fly, far.shape[-1] * far.shape[-2],
+                self.model, self.nm, A.stream_ptr()),
+            "cost (tike_cost_factor)")
+
+    def curvature(self, lo, hi, far, dfar, upstream, costs, dcosts, table,
+                  floor=COST_FLOOR):
+        """tike_cost_curvature on the frames of the positions lo ... hi - 1."""
+        fly = self.fly
+        flo, nf = lo // fly, (hi - lo) // fly
+        check(
+            lib.tike_cost_curvature(
+                A.ptr(far), A.ptr(dfar),
+                # (the curvature itself does not read the counts)
+                None if costs is None and dcosts is None else
+                A.ptr(self.data[flo:]), self.u16, A.ptr(self.mask),
+                None if upstream is None else A.ptr(upstream[flo:]),
+                None if costs is None else A.ptr(costs[flo:]),
+                None if dcosts is None else A.ptr(dcosts[flo:]),
+                A.ptr(table), nf, far.shape[-3] * fly,
+                far.shape[-1] * far.shape[-2], self.model, float(floor),
+                self.nm, A.stream_ptr()),
+            "cost (tike_cost_curvature)")
+
+
+def _cost_chunk_rows(op, probe, fly, halve=False):
+    """Positions per chunk of the one-slice forms, whole frames."""
+    from .ptycho.solvers.lstsq import chunk_positions
+    chunk = chunk_positions(probe.shape[2], op.detector_shape)
+    return max(1, chunk // (2 if halve else 1) // fly) * fly
+
+
+def _cost_forward(op, counts, psi, probe, scan, eigen, weights):
+    """(frames,) costs: per chunk the form's forward and tike_cost_factor."""
+    fly = counts.fly
+    N, S, det = scan.shape[0], probe.shape[2], op.detector_shape
+    A.current_device()  # (hands the library its deterministic-mode scratch)
+    costs = torch.empty(N // fly, dtype=torch.float32, device=psi.device)
+    if N == 0:
+        return costs
+    if psi.shape[0] > 1:
+        fused = _fused_route(op, probe)
+        chunk = _slices_chunk(op, psi, probe, fly, fused)
+        if fused:
+            far_all, _, beams, _ = _fused_buffers(op, psi, probe,
+                                                  min(chunk, N))
+        for lo in range(0, N, chunk):
+            hi = min(N, lo + chunk)
+            sc = scan[lo:hi]
+            far = (_fused_far(op, psi, sc, probe, far_all, beams) if fused
+                   else _general_far(op, psi, sc, probe)[0])
+            counts.factor(lo, hi, far, None, costs, None)
+        return costs
+    chunk = _cost_chunk_rows(op, probe, fly)
+    far_all = torch.empty((min(chunk, N), 1, S, det, det),
+                          dtype=torch.complex64, device=psi.device)
+    for lo in range(0, N, chunk):
+        hi = min(N, lo + chunk)
+        far = far_all[:hi - lo]
+        if weights is None:
+            op.fwd_device(probe, scan[lo:hi], psi, out=far)
+        else:
+            op.fwd_device(probe, scan[lo:hi], psi, eigen, weights[lo:hi],
+                          out=far)
+        counts.factor(lo, hi, far, None, costs, None)
+    return costs
+
+
+class _Cost(torch.autograd.Function):
+    """The per-frame cost of every form of the model.  The backward is the
+    form's own backward whose upstream table of a chunk comes from
+    tike_cost_factor on the chunk's recomputed far plane."""
+
+    @staticmethod
+    def forward(ctx, psi, probe, scan, eigen_probe, eigen_weights, operator,
+                counts):
+        psi, probe, scan = (x.detach().contiguous() for x in (psi, probe, scan))
+        eigen = (None if eigen_probe is None else
+                 eigen_probe.detach().contiguous())
+        weights = (None if eigen_weights is None else
+                   eigen_weights.detach().contiguous())
+        ctx.operator, ctx.counts = operator, counts
+        ctx.have = (eigen is not None, weights is not None)
+        ctx.save_for_backward(psi, probe, scan,
+                              *(x for x in (eigen, weights) if x is not None))
+        return _cost_forward(operator, counts, psi, probe, scan, eigen,
+                             weights)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        psi, probe, scan = ctx.saved_tensors[:3]
+        rest = list(ctx.saved_tensors[3:])
+        eigen = rest.pop(0) if ctx.have[0] else None
+        weights = rest.pop(0) if ctx.have[1] else None
+        op, counts = ctx.operator, ctx.counts
+        fly, det = counts.fly, op.detector_shape
+        g = g.to(torch.float32).contiguous()
+        A.current_device()  # (hands the library its deterministic-mode scratch)
+        tables = {}
+
+        def table_of(lo, hi, far):
+            # one chunk of table, reused: the chain reads it before the next
+            # chunk's entry writes it (one stream)
+            nf = (hi - lo) // fly
+            if "t" not in tables or tables["t"].shape[0] < nf:
+                tables["t"] = torch.empty((nf, det, det), dtype=torch.float32,
+                                          device=psi.device)
+            table = tables["t"][:nf]
+            counts.factor(lo, hi, far, g, None, table)
+            return table
+
+        want = tuple(ctx.needs_input_grad[:5])
+        if psi.shape[0] > 1:
+            grads = _multislice_backward_chunks(op, fly, psi, probe, scan,
+                                                want[:3], table_of)
+            return grads + (None, None, None, None)
+        grads = _backward_chunks(op, fly, psi, probe, scan, want, table_of,
+                                 eigen, weights)
+        return grads + (None, None)
+
+
+def cost(operator, data, psi, probe, scan, *, model="gaussian",
+         measured_pixels=None, eigen_probe=None, eigen_weights=None, fly=1,
+         check_positions=True):
+    """The per-frame cost (N // fly,) float32 of the model's intensity against
+    the counts `data` (N // fly, det, det) float32 or uint16 under the
+    project's noise models -- "gaussian": mean of (sqrt(I) - sqrt(d))^2,
+    "poisson": mean of I - d log(I + 1e-9) -- over the measured pixels
+    (measured_pixels (det, det) bool or uint8, None: all), differentiable once
+    with respect to whichever of psi, probe, scan, eigen_probe and
+    eigen_weights requires a gradient.  ``cost(...).mean()`` is
+    ``Ptycho.cost(data, psi, scan, probe, model=, fly=)`` for one slice and
+    the shared probe.  psi (D, H, W) with D > 1 is the model of
+    `multislice_intensity`, eigen_weights that of `intensity(...,
+    eigen_probe=, eigen_weights=)`, otherwise `intensity`.
+
+    The gradient factors are the solvers': 1 - sqrt(d) / (sqrt(I) + 1e-9) and
+    1 - d / (I + 1e-9), finite at I = 0; a count under the mask may be NaN: it
+    is selected away.  Forward, per chunk of whole frames: the form's forward,
+    then tike_cost_factor (costs).  Backward, per chunk: the forward again,
+    tike_cost_factor with grad_output for the upstream (the chunk's table),
+    and the form's backward chain from the point where it reads the table.  No
+    tensor of N // fly * det * det elements exists at any time.
+
+    Raises what the form's intensity raises, TypeError / ValueError for data
+    or measured_pixels of another type, dtype or shape, ValueError for a mask
+    that measures nothing or an unknown model, NotImplementedError for several
+    slices with eigen probes.  measured_pixels costs a read-back per call.
+    """
+    name = "cost"
+
+    def checked(slices):
+        return _checked(operator, psi, probe, scan, fly, check_positions,
+                        name=name, slices=slices, eigen_probe=eigen_probe,
+                        eigen_weights=eigen_weights)
+
+    fly, data, mask, nm, model = _checked_cost(
+        name, operator, data, measured_pixels, model, psi, probe, scan,
+        eigen_probe, eigen_weights, fly, check_positions, checked)
+    return _Cost.apply(psi, probe, scan, eigen_probe, eigen_weights, operator,
+                       _Counts(data, mask, nm, model, fly))
+
+
+def _cost_tangents(name, operator, data, measured_pixels, model, psi, probe,
+                   scan, eigen_probe, eigen_weights, d_psi, d_probe, d_scan,
+                   d_eigen_probe, d_eigen_weights, fly, check_positions):
+    """The checks of `cost_jvp` and `cost_gauss_newton_product`: (counts, the
+    five primals detached and contiguous, the five tangents)."""
+    if eigen_weights is None and (d_eigen_probe is not None
+                                  or d_eigen_weights is not None):
+        raise ValueError(
+            f"{name}: d_eigen_probe or d_eigen_weights without eigen_weights")
+
+    def checked(slices):
+        if eigen_weights is not None:
+            return _checked_eigen_jvp(
+                name, operator, psi, probe, scan, eigen_probe, eigen_weights,
+                d_psi, d_probe, d_scan, d_eigen_probe, d_eigen_weights, fly,
+                check_positions)
+        f, t = _checked_jvp(name, operator, psi, probe, scan, d_psi, d_probe,
+                            d_scan, fly, check_positions, slices=slices)
+        return f, list(t) + [None, None]
+
+    (fly, tangents), data, mask, nm, model = _checked_cost(
+        name, operator, data, measured_pixels, model, psi, probe, scan,
+        eigen_probe, eigen_weights, fly, check_positions, checked)
+    primals = [None if x is None else x.detach().contiguous()
+               for x in (psi, probe, scan, eigen_probe, eigen_weights)]
+    return _Counts(data, mask, nm, model, fly), primals, list(tangents)
+
+
+def _cost_jvp_chunks(op, primals, tangents, fly, sink):
+    """The form's forward-mode chunk loop with `sink` in the place of
+    tike_intensity_tangent."""
+    psi, probe, scan, eigen, weights = primals
+    if weights is not None:
+        _eigen_jvp_chunks(op, psi, probe, scan, eigen, weights, *tangents,
+                          fly, primal=False, sink=sink)
+    elif psi.shape[0] > 1:
+        _multislice_jvp_chunks(op, psi, probe, scan, *tangents[:3], fly,
+                               primal=False, sink=sink)
+    else:
+        _jvp_chunks(op, psi, probe, scan, *tangents[:3], fly, primal=False,
+                    sink=sink)
+
+
+def cost_jvp(operator, data, psi, probe, scan, *, model="gaussian",
+             measured_pixels=None, eigen_probe=None, eigen_weights=None,
+             d_psi=None, d_probe=None, d_scan=None, d_eigen_probe=None,
+             d_eigen_weights=None, fly=1, check_positions=True):
+    """(costs, dcosts), both (N // fly,) float32 outside any autograd graph:
+    the costs of `cost` -- the same bits -- and their directional derivative
+    along the tangents of the form's `*_jvp` function (each None or of its
+    primal's shape): the exact slope of a line search.  The form's
+    forward-mode chunk loop with tike_cost_curvature in the place of
+    tike_intensity_tangent: neither I nor dI is stored.  With no tangent
+    dcosts is zeros and only the primal launches.
+
+    Raises what `cost` and the form's `*_jvp` function raise.
+    """
+    counts, primals, tangents = _cost_tangents(
+        "cost_jvp", operator, data, measured_pixels, model, psi, probe, scan,
+        eigen_probe, eigen_weights, d_psi, d_probe, d_scan, d_eigen_probe,
+        d_eigen_weights, fly, check_positions)
+    fly = counts.fly
+    if all(t is None for t in tangents):
+        costs = _cost_forward(operator, counts, *primals)
+        return costs, torch.zeros_like(costs)
+    costs = torch.empty(primals[2].shape[0] // fly, dtype=torch.float32,
+                        device=primals[0].device)
+    dcosts = torch.empty_like(costs)
+    _cost_jvp_chunks(
+        operator, primals, tangents, fly,
+        lambda lo, hi, far, dfar: counts.curvature(lo, hi, far, dfar, None,
+                                                   costs, dcosts, None))
+    return costs, dcosts
+
+
+def cost_gauss_newton_product(operator, data, psi, probe, scan, *,
+                              model="gaussian", measured_pixels=None,
+                              eigen_probe=None, eigen_weights=None, d_psi=None,
+                              d_probe=None, d_scan=None, d_eigen_probe=None,
+                              d_eigen_weights=None, upstream=None,
+                              floor=COST_FLOOR, fly=1, wrt=None,
+                              check_positions=True):
+    """J^T diag(upstream_f c / (num_measured (I + floor))) J v on the measured
+    pixels: the Gauss-Newton matrix of sum_f upstream_f cost_f applied to the
+    tangents v of `cost_jvp` -- c = 1/2 for "gaussian" (the curvature
+    1 / (2 I) of the amplitude residual), 1 for "poisson" (the Fisher
+    information 1 / I).  One tensor per name in `wrt` (default: every input
+    of the form; the names and the order of the form's `*_gauss_newton_product`),
+    in the `.grad` convention of `cost`.  upstream: (N // fly,) float32 device
+    tensor or None (ones); floor >= 0, the project's 1e-9 by default.  `data`
+    only names dtype and shape here: the curvature does not depend on the
+    counts.
+
+    One slice (with or without eigen probes): ONE chunk loop with the far
+    plane resident -- the form's forward-mode launches, tike_cost_curvature
+    (the chunk's table), then the backward chain of the form on the SAME far
+    plane: no third forward, no I, dI or weight over all frames.  Several
+    slices: composed -- the forward-mode chunks with tike_cost_curvature write
+    the (N // fly, det, det) table, then the backward of
+    `multislice_intensity` runs with it.  Only what `wrt` names is launched
+    behind the table.
+
+    Raises what `cost_jvp` raises, ValueError for names in `wrt` the form does
+    not have (or none, or one twice), for a negative or non-finite floor,
+    TypeError / ValueError for an upstream of another type, dtype, shape or
+    device.
+    """
+    name = "cost_gauss_newton_product"
+    names = _EIGEN_WRT if eigen_weights is not None else _WRT
+    wrt = _checked_product(name, operator, psi, scan, None, fly,
+                           names if wrt is None else wrt, names=names)
+    if "eigen_probe" in wrt and eigen_probe is None:
+        raise ValueError(
+            f'{name}: "eigen_probe" in wrt with eigen_probe=None (there is no '
+            "eigen probe to differentiate with respect to)")
+    floor = float(floor)
+    if not (floor >= 0.0 and floor != float("inf")):
+        raise ValueError(f"{name}: floor must be finite and >= 0, not {floor}")
+    if upstream is not None:
+        if not isinstance(upstream, torch.Tensor):
+            raise TypeError(
+                f"{name}: upstream must be a torch device tensor, not "
+                f"{type(upstream).__name__}")
+        if upstream.dtype != torch.float32:
+            raise TypeError(
+                f"{name}: upstream must be torch.float32, not "
+                f"{upstream.dtype}")
+        frames = _frames(scan, fly)
+        if frames is not None and tuple(upstream.shape) != (frames,):
+            raise ValueError(
+                f"{name}: upstream must be (N // fly,) = ({frames},), not "
+                f"{tuple(upstream.shape)}")
+        if isinstance(psi, torch.Tensor) and upstream.device != psi.device:
+            raise ValueError(
+                f"{name}: upstream lives on {upstream.device}, psi on "
+                f"{psi.device}")
+        upstream = upstream.detach().contiguous()
+    counts, primals, tangents = _cost_tangents(
+        name, operator, data, measured_pixels, model, psi, probe, scan,
+        eigen_probe, eigen_weights, d_psi, d_probe, d_scan, d_eigen_probe,
+        d_eigen_weights, fly, check_positions)
+    fly = counts.fly
+    psi, probe, scan, eigen, weights = primals
+    by_name = dict(zip(_EIGEN_WRT, primals))
+    if all(t is None for t in tangents) or scan.shape[0] == 0:
+        return tuple(torch.zeros_like(by_name[k]) for k in wrt)
+    op, det, dev = operator, operator.detector_shape, psi.device
+    want = tuple(k in wrt for k in _EIGEN_WRT)
+    if psi.shape[0] > 1:
+        table = torch.empty((scan.shape[0] // fly, det, det),
+                            dtype=torch.float32, device=dev)
+        _cost_jvp_chunks(
+            op, primals, tangents, fly,
+            lambda lo, hi, far, dfar: counts.curvature(
+                lo, hi, far, dfar, upstream, None, None,
+                table[lo // fly:hi // fly], floor))
+        grads = _multislice_backward_chunks(
+            op, fly, psi, probe, scan, want[:3],
+            lambda lo, hi, far: table[lo // fly:hi // fly]) + (None, None)
+    else:
+        rows = min(_cost_chunk_rows(op, probe, fly, halve=True),
+                   scan.shape[0])
+        back = _Back(op, fly, psi, probe, scan, want, rows, eigen, weights,
+                     resident=True)
+        table_all = torch.empty((rows // fly, det, det), dtype=torch.float32,
+                                device=dev)
+
+        def sink(lo, hi, far, dfar):
+            table = table_all[:(hi - lo) // fly]
+            counts.curvature(lo, hi, far, dfar, upstream, None, None, table,
+                             floor)
+            # (the tangent far plane is dead behind the table: the scaled
+            # inverse writes there)
+            back.run(lo, hi, far, table, spare=dfar)
+
+        _cost_jvp_chunks(op, primals, tangents, fly, sink)
+        grads = back.result()
+    return tuple(dict(zip(_EIGEN_WRT, grads))[k] for k in wrt)

@@ -14,6 +14,7 @@
 // bytes of counts, npix bytes of mask when there is one.
 #include "../../include/tike_amd.h"
 #include "common.h"
+#include "noise_model.h"
 
 namespace {
 
@@ -29,28 +30,15 @@ constexpr int FLY_PX = 4;  // pixels of a lane per sweep: two 16-byte far-plane 
 // One pixel whose intensity is complete: its cost term into `cost` (measured
 // pixels only) and the factor the far plane is multiplied by, -(gradient
 // factor) on measured pixels and unmeasured_scaling - 1 elsewhere.  The count
-// of an unmeasured pixel may be NaN: selected away, never multiplied.
+// of an unmeasured pixel may be NaN: selected away, never multiplied.  The
+// formulas live in noise_model.h.
 template <int MODEL>
 __device__ __forceinline__ float fly_pixel(float I, float d, bool measured, float ums1,
                                            double& cost) {
-  float term, g;
-  if (MODEL == 0) {
-    const float sI = sqrtf(I), sd = sqrtf(d);
-    const float diff = sI - sd;
-    term = diff * diff;
-    g = -(1.0f - sd / (sI + 1e-9f));
-  } else {
-    term = I - d * logf(I + 1e-9f);
-    g = -(1.0f - d / (I + 1e-9f));
-  }
+  float term;
+  const float g = -tk_noise_pixel<MODEL>(I, d, term);
   cost += measured ? (double)term : 0.0;
   return measured ? g : ums1;
-}
-
-__device__ __forceinline__ double fly_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // One workgroup per frame; a lane owns FLY_PX consecutive pixels per sweep.
@@ -171,7 +159,7 @@ __global__ __launch_bounds__(256) void fly_farplane_gradient_kernel(
       for (int j = 0; j < P; ++j) F[j * npix + p] = F[j * npix + p] * g;
   }
   if (costs != nullptr) {
-    cost = fly_wave_sum(cost);
+    cost = tk_wave_sum_f64(cost);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cost;
     __syncthreads();
     if (threadIdx.x == 0)
