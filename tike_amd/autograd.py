@@ -107,7 +107,9 @@ tangent are both resident --
 and with no tangent at all only the primal launches.  `intensity` on
 ``torch.autograd.forward_ad`` dual tensors (any subset of psi, probe, scan)
 returns a dual whose tangent is this dI: `_Intensity.jvp` runs the same chunk
-loop.  The eigen-probe form and `multislice_intensity` have no forward-mode
+loop (`_jvp_chunks`, the one loop of the one-slice forms: with eigen weights
+it launches tike_eigen_wave_tangent, as below).  The eigen-probe form and
+`multislice_intensity` have no forward-mode
 RULE: under `forward_ad` they keep torch's own refusal ("you must implement
 the jvp function"); their forward mode is a function each,
 `eigen_intensity_jvp` and `multislice_intensity_jvp` below.
@@ -132,9 +134,10 @@ Fresnel step of the tangent of the exit wave in front of it:
 Per chunk of whole frames -- the far plane, the D - 1 sets of incident beams
 and ONE tangent set are resident, one set more than the forward holds --
 
-    the primal as `multislice_intensity` runs it (`_fused_far` or
-    `_general_far`: I has its bits; both leave the beam incident on every
-    slice) -> per slice tike_slice_wave_tangent, de_d written over dbeam_d in
+    the primal as `multislice_intensity` runs it (`_SlicesForward`, the one
+    forward of a chunk, over `_fused_far` or `_general_far`: I has its bits;
+    both leave the beam incident on every slice) -> per slice
+    tike_slice_wave_tangent, de_d written over dbeam_d in
     place (slice 0: the shared probe and d_probe), and between two slices the
     Fresnel step of the tangent (fused route: tike_fft2_pass1 ->
     tike_fresnel_colpass -> tike_fft2_pass2_inplace with the scale of
@@ -186,12 +189,13 @@ differentiable with respect to every input of the form it dispatches to
     gaussian: cost_f = mean_p (sqrt(I) - sqrt(d))^2,  l' = 1 - sqrt(d) / (sqrt(I) + 1e-9)
     poisson:  cost_f = mean_p I - d log(I + 1e-9),    l' = 1 - d / (I + 1e-9)
 
-Forward, per chunk of whole frames: the form's forward -> tike_cost_factor
-(costs).  Backward, per chunk: the forward again -> tike_cost_factor (the
-chunk's table upstream_f l' / num_measured, 0 under the mask) -> the form's
-backward chain from the point where it reads the table (`_Back.run`,
-`_fused_back`, `_general_back`: shared with the three backwards above, which
-hand them ``g[lo // fly:hi // fly]``).  ``cost_jvp`` runs the form's
+Forward, per chunk of whole frames: the form's forward (`_one_slice_far` or
+`_SlicesForward`, as everywhere in this module) -> tike_cost_factor (costs).
+Backward, per chunk: the forward again -> tike_cost_factor (the chunk's table
+upstream_f l' / num_measured, 0 under the mask) -> the form's backward chain
+from the point where it reads the table (`_Back.run`, `_fused_back`,
+`_general_back`: shared with the three backwards above, which hand them
+``g[lo // fly:hi // fly]``).  ``cost_jvp`` runs the form's
 forward-mode chunk loop with tike_cost_curvature in the place of
 tike_intensity_tangent: (costs, dcosts = sum_p l' dI / num_measured).
 ``cost_gauss_newton_product`` is J^T diag(upstream_f c / (num_measured
@@ -206,6 +210,12 @@ loop with the far plane resident --
 followed by the backward of `multislice_intensity`.  No tensor of
 N // fly * det * det elements exists in `cost`, `cost_jvp` or the one-slice
 product.
+
+The entries share their bodies: the three `*_jvp` functions are `_jvp`, the
+three `*_gauss_newton_product` functions `_gauss_newton`, over `_checked_jvp`
+(the refusals), `_apply` (the form's `Function`) and `_jvp_loop` (its
+forward-mode chunk loop), each of which tells the forms apart by the inputs
+(psi, probe, scan, eigen_probe, eigen_weights) it is handed.
 """
 import importlib
 
@@ -329,6 +339,26 @@ def _checked(operator, psi, probe, scan, fly, check_positions,
     return fly
 
 
+def _chunk_rows(op, probe, fly, halve=False):
+    """Positions per chunk of the one-slice forms, whole frames.  halve: the
+    far plane and its tangent are both resident."""
+    from .ptycho.solvers.lstsq import chunk_positions
+    chunk = chunk_positions(probe.shape[2], op.detector_shape)
+    return max(1, chunk // (2 if halve else 1) // fly) * fly
+
+
+def _one_slice_far(op, psi, probe, scan, eigen, weights, lo, hi, out):
+    """The far plane of the positions lo ... hi - 1 of a one-slice form in
+    out[:hi - lo]: tike_ptycho_fwd, with the eigen operands unless weights is
+    None."""
+    far = out[:hi - lo]
+    if weights is None:
+        op.fwd_device(probe, scan[lo:hi], psi, out=far)
+    else:
+        op.fwd_device(probe, scan[lo:hi], psi, eigen, weights[lo:hi], out=far)
+    return far
+
+
 class _Back:
     """The backward chain of the one-slice forms behind the far plane, shared
     by `_Intensity.backward`, `_EigenIntensity.backward`, the backward of
@@ -386,14 +416,8 @@ class _Back:
     def forward(self, lo, hi):
         """The far plane of the positions lo ... hi - 1 in the chunk's own
         buffer."""
-        far = self.far_all[:hi - lo]
-        w = None if self.weights is None else self.weights[lo:hi]
-        if w is None:
-            self.op.fwd_device(self.probe, self.scan[lo:hi], self.psi, out=far)
-        else:
-            self.op.fwd_device(self.probe, self.scan[lo:hi], self.psi,
-                               self.eigen, w, out=far)
-        return far
+        return _one_slice_far(self.op, self.psi, self.probe, self.scan,
+                              self.eigen, self.weights, lo, hi, self.far_all)
 
     def run(self, lo, hi, far, table, spare=None):
         """The chain behind `far` (n, 1, S, det, det), which it may overwrite,
@@ -472,9 +496,8 @@ def _backward_chunks(op, fly, psi, probe, scan, want, table_of, eigen=None,
     """The backward of the one-slice forms: per chunk of whole frames the
     recomputed forward, the upstream table of the chunk -- table_of(lo, hi,
     far), frames lo // fly ... hi // fly - 1 -- and the chain of `_Back`."""
-    from .ptycho.solvers.lstsq import chunk_positions
-    N, S = scan.shape[0], probe.shape[2]
-    chunk = max(1, chunk_positions(S, op.detector_shape) // fly) * fly
+    N = scan.shape[0]
+    chunk = _chunk_rows(op, probe, fly)
     back = _Back(op, fly, psi, probe, scan, want, min(chunk, N), eigen,
                  weights)
     for lo in range(0, N, chunk):
@@ -484,24 +507,37 @@ def _backward_chunks(op, fly, psi, probe, scan, want, table_of, eigen=None,
     return back.result()
 
 
+def _one_slice_forward(ctx, operator, fly, psi, probe, scan, eigen_probe=None,
+                       eigen_weights=None):
+    """The forward of `_Intensity` and `_EigenIntensity`: (the inputs that are
+    not None, detached and contiguous, saved for backward in the order psi,
+    probe, scan, eigen_weights, eigen_probe; the intensity)."""
+    from .ptycho.ptycho import _intensity_chunks
+    psi, probe, scan, eigen_weights, eigen_probe = (
+        None if x is None else x.detach().contiguous()
+        for x in (psi, probe, scan, eigen_weights, eigen_probe))
+    saved = tuple(x for x in (psi, probe, scan, eigen_weights, eigen_probe)
+                  if x is not None)
+    ctx.operator, ctx.fly = operator, fly
+    ctx.save_for_backward(*saved)
+    A.current_device()  # (hands the library its deterministic-mode scratch)
+    det = operator.detector_shape
+    if scan.shape[0] == 0:
+        return saved, torch.empty((0, det, det), dtype=torch.float32,
+                                  device=psi.device)
+    # chunked; the far plane of a chunk dies with the chunk
+    frames = [inten for _, _, inten in _intensity_chunks(
+        operator, psi, scan, probe, eigen_probe, eigen_weights, fly=fly)]
+    return saved, frames[0] if len(frames) == 1 else torch.cat(frames)
+
+
 class _Intensity(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, psi, probe, scan, operator, fly):
-        from .ptycho.ptycho import _intensity_chunks
-        psi, probe, scan = (x.detach().contiguous() for x in (psi, probe, scan))
-        ctx.operator, ctx.fly = operator, fly
-        ctx.save_for_backward(psi, probe, scan)
-        ctx.save_for_forward(psi, probe, scan)
-        A.current_device()  # (hands the library its deterministic-mode scratch)
-        det = operator.detector_shape
-        if scan.shape[0] == 0:
-            return torch.empty((0, det, det), dtype=torch.float32,
-                               device=psi.device)
-        # chunked; the far plane of a chunk dies with the chunk
-        frames = [inten for _, _, inten in _intensity_chunks(
-            operator, psi, scan, probe, fly=fly)]
-        return frames[0] if len(frames) == 1 else torch.cat(frames)
+        saved, inten = _one_slice_forward(ctx, operator, fly, psi, probe, scan)
+        ctx.save_for_forward(*saved)
+        return inten
 
     @staticmethod
     def jvp(ctx, d_psi, d_probe, d_scan, _operator, _fly):
@@ -515,8 +551,8 @@ class _Intensity(torch.autograd.Function):
         psi, probe, scan = ctx.saved_tensors
         tangents = [None if t is None else t.detach().contiguous()
                     for t in (d_psi, d_probe, d_scan)]
-        return _jvp_chunks(ctx.operator, psi, probe, scan, *tangents, ctx.fly,
-                           primal=False)[1]
+        return _jvp_chunks(ctx.operator, (psi, probe, scan, None, None),
+                           tangents + [None, None], ctx.fly, primal=False)[1]
 
     @staticmethod
     @once_differentiable
@@ -539,24 +575,9 @@ class _EigenIntensity(torch.autograd.Function):
     @staticmethod
     def forward(ctx, psi, probe, scan, eigen_probe, eigen_weights, operator,
                 fly):
-        from .ptycho.ptycho import _intensity_chunks
-        psi, probe, scan, eigen_weights = (
-            x.detach().contiguous()
-            for x in (psi, probe, scan, eigen_weights))
-        if eigen_probe is not None:
-            eigen_probe = eigen_probe.detach().contiguous()
-        ctx.operator, ctx.fly = operator, fly
         ctx.eigen = eigen_probe is not None
-        ctx.save_for_backward(psi, probe, scan, eigen_weights,
-                              *((eigen_probe,) if ctx.eigen else ()))
-        A.current_device()  # (hands the library its deterministic-mode scratch)
-        det = operator.detector_shape
-        if scan.shape[0] == 0:
-            return torch.empty((0, det, det), dtype=torch.float32,
-                               device=psi.device)
-        frames = [inten for _, _, inten in _intensity_chunks(
-            operator, psi, scan, probe, eigen_probe, eigen_weights, fly=fly)]
-        return frames[0] if len(frames) == 1 else torch.cat(frames)
+        return _one_slice_forward(ctx, operator, fly, psi, probe, scan,
+                                  eigen_probe, eigen_weights)[1]
 
     @staticmethod
     @once_differentiable
@@ -649,63 +670,91 @@ def _jvp_outputs(op, psi, scan, fly, primal, sink):
                         device=psi.device))
 
 
-def _jvp_chunks(op, psi, probe, scan, d_psi, d_probe, d_scan, fly, primal=True,
-                sink=None):
-    """(I or None, dI): the chunk loop of `intensity_jvp` and `_Intensity.jvp`
-    on contiguous device tensors; at least one tangent is not None.  sink(lo,
-    hi, far, dfar): called per chunk in the place of tike_intensity_tangent
-    (`cost_jvp`, `cost_gauss_newton_product`; both far planes are its to
-    overwrite); then (None, None) is returned and no frame-sized tensor
-    exists."""
-    from .ptycho.solvers.lstsq import chunk_positions
+def _jvp_chunks(op, primals, tangents, fly, primal=True, sink=None):
+    """(I or None, dI): the forward-mode chunk loop of the one-slice forms
+    (`intensity_jvp`, `_Intensity.jvp`, `eigen_intensity_jvp`) on contiguous
+    device tensors: primals (psi, probe, scan, eigen, weights) and their five
+    tangents, at least one of which is not None.  weights None: the plain
+    form, tike_conv_fwd_tangent; otherwise (eigen, d_eigen: None for C = 0)
+    tike_eigen_wave_tangent.  sink(lo, hi, far, dfar): called per chunk in the
+    place of tike_intensity_tangent (`cost_jvp`, `cost_gauss_newton_product`;
+    both far planes are its to overwrite); then (None, None) is returned and
+    no frame-sized tensor exists."""
+    psi, probe, scan, eigen, weights = primals
+    d_psi, d_probe, d_scan, d_eigen, d_weights = tangents
+    # (the form's public function, for `check`)
+    what = "intensity_jvp" if weights is None else "eigen_intensity_jvp"
     N, S = scan.shape[0], probe.shape[2]
     pw, det = op.probe_shape, op.detector_shape
     H, W = psi.shape[-2:]
-    dev = psi.device
     A.current_device()  # (hands the library its deterministic-mode scratch)
     st = A.stream_ptr()
     inten, tangent = _jvp_outputs(op, psi, scan, fly, primal, sink)
     if N == 0:
         return inten, tangent
     if sink is None:
-        sink = _tangent_sink(inten, tangent, fly, "intensity_jvp")
+        sink = _tangent_sink(inten, tangent, fly, what)
     # the far plane and its tangent are both resident; whole frames
-    chunk = max(1, chunk_positions(S, det) // 2 // fly) * fly
-    rows = min(chunk, N)
-    far_all = torch.empty((rows, 1, S, det, det), dtype=torch.complex64,
-                          device=dev)
+    chunk = _chunk_rows(op, probe, fly, halve=True)
+    far_all = torch.empty((min(chunk, N), 1, S, det, det),
+                          dtype=torch.complex64, device=psi.device)
     dfar_all = torch.empty_like(far_all)
     fwd_scale = fft_scales(det, op.norm)[0]
     for lo in range(0, N, chunk):
         hi = min(N, lo + chunk)
         n = hi - lo
         sc = scan[lo:hi]
-        far, dfar = far_all[:n], dfar_all[:n]
-        op.fwd_device(probe, sc, psi, out=far)
-        check(
-            lib.tike_conv_fwd_tangent(
-                A.ptr(psi), A.ptr(d_psi), A.ptr(sc),
-                None if d_scan is None else A.ptr(d_scan[lo:hi]),
-                A.ptr(probe), A.ptr(d_probe), A.ptr(dfar), n, S, pw, det, H,
-                W, st), "intensity_jvp (tangent exit waves)")
+        dsc = None if d_scan is None else A.ptr(d_scan[lo:hi])
+        far = _one_slice_far(op, psi, probe, scan, eigen, weights, lo, hi,
+                             far_all)
+        dfar = dfar_all[:n]
+        if weights is None:
+            check(
+                lib.tike_conv_fwd_tangent(
+                    A.ptr(psi), A.ptr(d_psi), A.ptr(sc), dsc, A.ptr(probe),
+                    A.ptr(d_probe), A.ptr(dfar), n, S, pw, det, H, W, st),
+                f"{what} (tangent exit waves)")
+        else:
+            C, M = (0, 0) if eigen is None else eigen.shape[1:3]
+            check(
+                lib.tike_eigen_wave_tangent(
+                    A.ptr(psi), A.ptr(d_psi), A.ptr(sc), dsc, A.ptr(probe),
+                    A.ptr(d_probe), A.ptr(eigen), A.ptr(d_eigen),
+                    A.ptr(weights[lo:hi]),
+                    None if d_weights is None else A.ptr(d_weights[lo:hi]), C,
+                    M, A.ptr(dfar), n, S, pw, det, H, W, st),
+                f"{what} (tangent exit waves)")
         check(lib.tike_fft2(A.ptr(dfar), A.ptr(dfar), n * S, det, 0,
-                            fwd_scale, st),
-              "intensity_jvp (tangent far plane)")
+                            fwd_scale, st), f"{what} (tangent far plane)")
         sink(lo, hi, far, dfar)
     return inten, tangent
 
 
-def _checked_tangents(name, psi, probe, scan, d_psi, d_probe, d_scan,
-                      more=()):
-    """A tangent matches its primal in type, dtype, shape and device; the
-    tangents detached and contiguous (None stays None).  more: further
-    (what, primal, tangent) behind the three -- the eigen probes and their
-    weights."""
-    out = []
-    for what, x, t in (("psi", psi, d_psi), ("probe", probe, d_probe),
-                       ("scan", scan, d_scan)) + tuple(more):
+def _jvp_loop(op, primals, tangents, fly, primal=True, sink=None):
+    """The forward-mode chunk loop of the form that the primals (psi, probe,
+    scan, eigen, weights) have: several slices or one."""
+    if primals[0].shape[0] > 1:
+        return _multislice_jvp_chunks(op, *primals[:3], *tangents[:3], fly,
+                                      primal, sink)
+    return _jvp_chunks(op, primals, tangents, fly, primal, sink)
+
+
+def _apply(primals, operator, fly):
+    """The `Function` of the form that the primals (psi, probe, scan, eigen,
+    weights) have."""
+    if primals[4] is not None:
+        return _EigenIntensity.apply(*primals, operator, fly)
+    function = _MultisliceIntensity if primals[0].shape[0] > 1 else _Intensity
+    return function.apply(*primals[:3], operator, fly)
+
+
+def _checked_tangents(name, given):
+    """A tangent matches its primal in type, dtype, shape and device: {what:
+    the tangent detached and contiguous} for the (what, primal, tangent) of
+    `given` whose tangent is not None."""
+    out = {}
+    for what, x, t in given:
         if t is None:
-            out.append(None)
             continue
         if not isinstance(t, torch.Tensor):
             raise TypeError(
@@ -722,22 +771,80 @@ def _checked_tangents(name, psi, probe, scan, d_psi, d_probe, d_scan,
         if t.device != x.device:
             raise ValueError(
                 f"{name}: d_{what} lives on {t.device}, {what} on {x.device}")
-        out.append(t.detach().contiguous())
+        out[what] = t.detach().contiguous()
     return out
 
 
-def _checked_jvp(name, operator, psi, probe, scan, d_psi, d_probe, d_scan,
-                 fly, check_positions, slices=False):
+def _checked_jvp(name, operator, primals, tangents, fly, check_positions,
+                 slices=False, eigen=False):
     """Every refusal of the forward-mode entries that needs no device, the
-    tangents' among them, before `_checked` asks for device tensors."""
-    tangents = None
-    if all(isinstance(x, torch.Tensor) for x in (psi, probe, scan)):
+    tangents' among them, before `_checked` asks for device tensors: (fly, the
+    five tangents).  primals: (psi, probe, scan, eigen_probe, eigen_weights);
+    eigen: the eigen form, which must have eigen_weights; the other forms
+    look at the first three of either."""
+    psi, probe, scan, eigen_probe, eigen_weights = primals
+    given = list(zip(_EIGEN_WRT, primals, tangents))
+    if not eigen:
+        given, eigen_probe, eigen_weights = given[:3], None, None
+    elif eigen_probe is None:
+        if tangents[3] is not None:
+            raise ValueError(
+                f"{name}: d_eigen_probe without eigen_probe (there is no "
+                "eigen probe it could be the tangent of)")
+        del given[3]
+    checked = None
+    if all(isinstance(x, torch.Tensor) for _, x, _ in given):
         # (host arrays: `_checked` below names them)
-        tangents = _checked_tangents(name, psi, probe, scan, d_psi, d_probe,
-                                     d_scan)
+        checked = _checked_tangents(name, given)
+    if eigen and eigen_weights is None:
+        raise TypeError(
+            f"{name}: eigen_weights is required (without them `intensity_jvp` "
+            "is the forward mode of the model)")
     fly = _checked(operator, psi, probe, scan, fly, check_positions, name=name,
-                   slices=slices)
-    return fly, tangents
+                   slices=slices, eigen_probe=eigen_probe,
+                   eigen_weights=eigen_weights)
+    return fly, [checked.get(k) for k in _EIGEN_WRT]
+
+
+def _jvp(name, operator, primals, tangents, fly, check_positions, **form):
+    """The body of the three `*_jvp` functions on (psi, probe, scan,
+    eigen_probe, eigen_weights) and their tangents; form: `slices` or `eigen`
+    of `_checked_jvp`."""
+    fly, tangents = _checked_jvp(name, operator, primals, tangents, fly,
+                                 check_positions, **form)
+    primals = [None if x is None else x.detach().contiguous()
+               for x in primals]
+    if all(t is None for t in tangents):
+        with torch.no_grad():
+            inten = _apply(primals, operator, fly)
+        return inten, torch.zeros_like(inten)
+    return _jvp_loop(operator, primals, tangents, fly)
+
+
+def _gauss_newton(name, names, operator, primals, tangents, weight, fly, wrt,
+                  check_positions, **form):
+    """The body of the three `*_gauss_newton_product` functions: the
+    forward-mode loop of the form without the primal intensity, then its
+    `Function` with weight * dI upstream.  names: the inputs of the form;
+    form: as in `_jvp`."""
+    wrt = _checked_product(name, operator, primals, weight, fly, wrt, names)
+    fly, tangents = _checked_jvp(name, operator, primals, tangents, fly,
+                                 check_positions, **form)
+    leaves = [None if x is None else
+              x.detach().contiguous().requires_grad_(k in wrt)
+              for k, x in zip(_EIGEN_WRT, primals)]
+    by_name = dict(zip(_EIGEN_WRT, leaves))
+    if all(t is None for t in tangents):
+        return tuple(torch.zeros_like(by_name[k]) for k in wrt)
+    tangent = _jvp_loop(operator,
+                        [None if x is None else x.detach() for x in leaves],
+                        tangents, fly, primal=False)[1]
+    if weight is not None:
+        tangent = tangent * weight.detach()
+    with torch.enable_grad():
+        inten = _apply(leaves, operator, fly)
+        return torch.autograd.grad(inten, [by_name[k] for k in wrt],
+                                   grad_outputs=tangent)
 
 
 def intensity_jvp(operator, psi, probe, scan, *, d_psi=None, d_probe=None,
@@ -757,15 +864,8 @@ def intensity_jvp(operator, psi, probe, scan, *, d_psi=None, d_probe=None,
     a probe per position, TypeError, ValueError), and TypeError / ValueError
     for a tangent that does not match its primal, before any launch.
     """
-    fly, (d_psi, d_probe, d_scan) = _checked_jvp(
-        "intensity_jvp", operator, psi, probe, scan, d_psi, d_probe, d_scan,
-        fly, check_positions)
-    psi, probe, scan = (x.detach().contiguous() for x in (psi, probe, scan))
-    if d_psi is None and d_probe is None and d_scan is None:
-        with torch.no_grad():
-            inten = _Intensity.apply(psi, probe, scan, operator, fly)
-        return inten, torch.zeros_like(inten)
-    return _jvp_chunks(operator, psi, probe, scan, d_psi, d_probe, d_scan, fly)
+    return _jvp("intensity_jvp", operator, (psi, probe, scan, None, None),
+                (d_psi, d_probe, d_scan, None, None), fly, check_positions)
 
 
 _WRT = ("psi", "probe", "scan")
@@ -802,52 +902,51 @@ def gauss_newton_product(operator, psi, probe, scan, *, d_psi=None,
     than the three (or none, or one twice), TypeError / ValueError for a
     weight of another type, dtype, shape or device.
     """
-    name = "gauss_newton_product"
-    wrt = _checked_product(name, operator, psi, scan, weight, fly, wrt)
-    fly, (d_psi, d_probe, d_scan) = _checked_jvp(
-        name, operator, psi, probe, scan, d_psi, d_probe, d_scan, fly,
-        check_positions)
-    leaves = {k: x.detach().contiguous().requires_grad_(k in wrt)
-              for k, x in zip(_WRT, (psi, probe, scan))}
-    if d_psi is None and d_probe is None and d_scan is None:
-        return tuple(torch.zeros_like(leaves[k]) for k in wrt)
-    tangent = _jvp_chunks(operator, *(leaves[k].detach() for k in _WRT), d_psi,
-                          d_probe, d_scan, fly, primal=False)[1]
-    if weight is not None:
-        tangent = tangent * weight.detach()
-    with torch.enable_grad():
-        inten = _Intensity.apply(leaves["psi"], leaves["probe"],
-                                 leaves["scan"], operator, fly)
-        return torch.autograd.grad(inten, [leaves[k] for k in wrt],
-                                   grad_outputs=tangent)
+    return _gauss_newton("gauss_newton_product", _WRT, operator,
+                         (psi, probe, scan, None, None),
+                         (d_psi, d_probe, d_scan, None, None), weight, fly,
+                         wrt, check_positions)
 
 
-def _checked_product(name, operator, psi, scan, weight, fly, wrt, names=_WRT):
+def _checked_frame_tensor(name, what, x, operator, psi, scan, fly, planes):
+    """The refusals of a float32 tensor with a row per frame: `weight`
+    (N // fly, det, det) with planes, `upstream` (N // fly,) without."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(
+            f"{name}: {what} must be a torch device tensor, not "
+            f"{type(x).__name__}")
+    if x.dtype != torch.float32:
+        raise TypeError(
+            f"{name}: {what} must be torch.float32, not {x.dtype}")
+    frames = _frames(scan, fly)
+    det = operator.detector_shape
+    shape = (frames,) + ((det, det) if planes else ())
+    if frames is not None and tuple(x.shape) != shape:
+        raise ValueError(
+            f"{name}: {what} must be "
+            f"{'(N // fly, det, det)' if planes else '(N // fly,)'} = "
+            f"{shape}, not {tuple(x.shape)}")
+    if isinstance(psi, torch.Tensor) and x.device != psi.device:
+        raise ValueError(
+            f"{name}: {what} lives on {x.device}, psi on {psi.device}")
+
+
+def _checked_product(name, operator, primals, weight, fly, wrt, names):
     """The `wrt` and `weight` refusals of the Gauss-Newton products; wrt as a
-    tuple.  names: what `wrt` may name."""
+    tuple.  primals: (psi, probe, scan, eigen_probe, eigen_weights); names:
+    what `wrt` may name."""
     wrt = tuple(wrt)
     if not wrt or len(set(wrt)) != len(wrt) or any(w not in names
                                                    for w in wrt):
         raise ValueError(
             f"{name}: wrt must name some of {names}, each once; got {wrt}")
     if weight is not None:
-        if not isinstance(weight, torch.Tensor):
-            raise TypeError(
-                f"{name}: weight must be a torch device tensor, not "
-                f"{type(weight).__name__}")
-        if weight.dtype != torch.float32:
-            raise TypeError(
-                f"{name}: weight must be torch.float32, not {weight.dtype}")
-        frames = _frames(scan, fly)
-        det = operator.detector_shape
-        if frames is not None and tuple(weight.shape) != (frames, det, det):
-            raise ValueError(
-                f"{name}: weight must be (N // fly, det, det) = ({frames}, "
-                f"{det}, {det}), not {tuple(weight.shape)}")
-        if isinstance(psi, torch.Tensor) and weight.device != psi.device:
-            raise ValueError(
-                f"{name}: weight lives on {weight.device}, psi on "
-                f"{psi.device}")
+        _checked_frame_tensor(name, "weight", weight, operator, primals[0],
+                              primals[2], fly, planes=True)
+    if "eigen_probe" in wrt and primals[3] is None:
+        raise ValueError(
+            f'{name}: "eigen_probe" in wrt with eigen_probe=None (there is no '
+            "eigen probe to differentiate with respect to)")
     return wrt
 
 
@@ -928,23 +1027,67 @@ def _general_far(op, psi, sc, probe):
     return op.propagation.fwd(wave, overwrite=True), beams
 
 
-def _fused_back(op, psi, sc, probe, table_of, fly, bufs, want, acc,
-                gprobe):
-    """One chunk of the backward on the two-pass kernels: the launches of
-    cgrad's `_multislice_chunk_fused` with the upstream gradient for the cost
+class _SlicesForward:
+    """The forward of `multislice_intensity` chunk by chunk, for its four
+    users (the forward, the backward, the forward mode, the cost): the route,
+    the chunk of whole frames (`extra`: as in `_slices_chunk`), on the fused
+    route the workspace buffers, and per chunk the far plane and the beams.
+    Iterating yields (lo, hi, far (n, S, det, det), beams) with beams[d]
+    (n, S, pw, pw) the beam incident on slice d >= 1.  On the general route
+    far and beams are fresh tensors that the iteration does not hold on to:
+    they live as long as the caller keeps them."""
+
+    def __init__(self, op, fly, psi, probe, scan, extra=0):
+        self.op, self.psi, self.probe, self.scan = op, psi, probe, scan
+        self.fused = _fused_route(op, probe)
+        self.chunk = _slices_chunk(op, psi, probe, fly, self.fused,
+                                   extra=extra)
+        self.nmax = min(self.chunk, scan.shape[0])
+        if self.fused:
+            (self.far_all, self.mid, self.beams_all,
+             self.objproj) = _fused_buffers(op, psi, probe, max(self.nmax, 1))
+
+    def tangent(self):
+        """(nmax, S, det, det) for the forward mode's tangent: of the
+        workspace on the fused route."""
+        from .ptycho.solvers.lstsq import _workspace
+        S, det = self.probe.shape[2], self.op.detector_shape
+        if self.fused:
+            return _workspace(self.op).get(
+                "ms_tangent", (self.nmax, S, det, det), torch.complex64,
+                self.psi.device)
+        return torch.empty((self.nmax, S, det, det), dtype=torch.complex64,
+                           device=self.psi.device)
+
+    def __iter__(self):
+        op, psi, probe, N = self.op, self.psi, self.probe, self.scan.shape[0]
+        for lo in range(0, N, self.chunk):
+            hi = min(N, lo + self.chunk)
+            sc = self.scan[lo:hi]
+            if self.fused:
+                far = _fused_far(op, psi, sc, probe, self.far_all,
+                                 self.beams_all)
+                yield lo, hi, far, [probe[0]] + [
+                    b[:hi - lo] for b in self.beams_all[:psi.shape[0] - 1]]
+            else:
+                yield (lo, hi) + _general_far(op, psi, sc, probe)
+
+
+def _fused_back(op, psi, sc, probe, far, beams, table, fly, mid, objproj, want,
+                acc, gprobe):
+    """One chunk of the backward on the two-pass kernels behind the far plane
+    and the incident beams of `_SlicesForward`: the launches of cgrad's
+    `_multislice_chunk_fused` with the upstream gradient `table` for the cost
     kernel and F^H for the last transform's inverse.  Leaves objproj_d in
-    bufs[3][d, :n] when the object or the positions want it."""
+    objproj[d, :n] when the object or the positions want it."""
     cgrad = _cgrad()
     want_psi, want_probe, want_scan = want
     D, (H, W) = psi.shape[0], psi.shape[-2:]
     n, S, det = sc.shape[0], probe.shape[-3], op.detector_shape
-    far, mid, beams, objproj = bufs
     need_proj = want_psi or want_scan
     st = A.stream_ptr()
     fwd_scale, inv_scale = fft_scales(det, op.norm)
     prop = op.diffraction.propagation._propagator((det, det), psi.device)
-    far = _fused_far(op, psi, sc, probe, far, beams)
-    table = table_of(far)
     mid = mid[:n]
     if PASS1_TAKES_TABLE:
         # S * fly planes share a frame's table
@@ -964,7 +1107,7 @@ def _fused_back(op, psi, sc, probe, table_of, fly, bufs, want, acc,
     scale = 2.0 * fwd_scale
     one_launch = cgrad.MULTISLICE_STEP_BACK_FUSED and det in (128, 256)
     for d in range(D - 1, 0, -1):
-        beam = beams[d - 1, :n]
+        beam = beams[d]
         proj = objproj[d, :n] if need_proj else None
         if one_launch:
             check(
@@ -1013,19 +1156,18 @@ def _fused_back(op, psi, sc, probe, table_of, fly, bufs, want, acc,
             "slice)")
 
 
-def _general_back(op, psi, sc, probe, table_of, fly, objproj, want, acc,
-                  gprobe):
-    """One chunk of the backward through the general operators, as cgrad's
-    `_multislice_chunk_general` walks back; table_of(far) is the upstream
-    table of the chunk's frames; objproj (D, nmax, pw, pw) or None."""
+def _general_back(op, psi, sc, probe, far, beams, table, fly, objproj, want,
+                  acc, gprobe):
+    """One chunk of the backward through the general operators behind the far
+    plane and the incident beams of `_SlicesForward`, as cgrad's
+    `_multislice_chunk_general` walks back; table: the upstream table of the
+    chunk's frames; objproj (D, nmax, pw, pw) or None."""
     want_psi, want_probe, want_scan = want
     D, (H, W) = psi.shape[0], psi.shape[-2:]
     n, S, det = sc.shape[0], probe.shape[-3], op.detector_shape
     conv, fresnel = op.diffraction.diffraction, op.diffraction.propagation
     need_proj = want_psi or want_scan
     st = A.stream_ptr()
-    far, beams = _general_far(op, psi, sc, probe)
-    table = table_of(far)
     check(
         lib.tike_farplane_scale(A.ptr(far), A.ptr(table), n // fly, S * fly,
                                 det * det, 2.0, st),
@@ -1084,16 +1226,8 @@ class _MultisliceIntensity(torch.autograd.Function):
                             device=psi.device)
         if N == 0:
             return inten
-        fused = _fused_route(op, probe)
-        chunk = _slices_chunk(op, psi, probe, fly, fused)
-        if fused:
-            far_all, _, beams, _ = _fused_buffers(op, psi, probe,
-                                                  min(chunk, N))
-        for lo in range(0, N, chunk):
-            hi = min(N, lo + chunk)
-            sc = scan[lo:hi]
-            far = (_fused_far(op, psi, sc, probe, far_all, beams) if fused
-                   else _general_far(op, psi, sc, probe)[0])
+        for lo, hi, far, beams in _SlicesForward(op, fly, psi, probe, scan):
+            del beams  # (general route: only the far plane is kept)
             # the S * fly planes of a frame are adjacent
             check(
                 lib.tike_intensity(A.ptr(far), A.ptr(inten[lo // fly:]),
@@ -1122,31 +1256,31 @@ def _multislice_backward_chunks(op, fly, psi, probe, scan, want, table_of):
     scan gradient over the D objproj planes.  (psi, probe, scan) gradients."""
     want_psi, want_probe, want_scan = want
     D, (H, W) = psi.shape[0], psi.shape[-2:]
-    N, pw = scan.shape[0], op.probe_shape
+    pw = op.probe_shape
     dev = psi.device
     acc = (torch.zeros((D, 2, H, W), dtype=torch.float32, device=dev)
            if want_psi else None)
     gprobe = torch.zeros_like(probe) if want_probe else None
     gscan = torch.empty_like(scan) if want_scan else None
-    fused = _fused_route(op, probe)
-    chunk = _slices_chunk(op, psi, probe, fly, fused)
-    nmax = min(chunk, N)
-    if fused:
-        bufs = _fused_buffers(op, psi, probe, max(nmax, 1))
-        objproj = bufs[3]
+    forward = _SlicesForward(op, fly, psi, probe, scan)
+    nmax = forward.nmax
+    if forward.fused:
+        objproj = forward.objproj
     else:
         objproj = (torch.empty((D, nmax, pw, pw), dtype=torch.complex64,
                                device=dev)
                    if want_psi or want_scan else None)
-    for lo in range(0, N, chunk):
-        hi = min(N, lo + chunk)
+    for lo, hi, far, beams in forward:
         sc = scan[lo:hi]
-        of = lambda far, lo=lo, hi=hi: table_of(lo, hi, far)
-        if fused:
-            _fused_back(op, psi, sc, probe, of, fly, bufs, want, acc, gprobe)
+        table = table_of(lo, hi, far)
+        if forward.fused:
+            _fused_back(op, psi, sc, probe, far, beams, table, fly,
+                        forward.mid, objproj, want, acc, gprobe)
         else:
-            _general_back(op, psi, sc, probe, of, fly, objproj, want, acc,
-                          gprobe)
+            _general_back(op, psi, sc, probe, far, beams, table, fly, objproj,
+                          want, acc, gprobe)
+        # (general route: fresh tensors, gone before the next chunk's are made)
+        del far, beams
         if want_scan:
             check(
                 lib.tike_scan_gradient_slices(
@@ -1207,10 +1341,8 @@ def _multislice_jvp_chunks(op, psi, probe, scan, d_psi, d_probe, d_scan, fly,
     """(I or None, dI): the chunk loop of `multislice_intensity_jvp` for
     D > 1 slices on contiguous device tensors; at least one tangent is not
     None.  sink: as in `_jvp_chunks`."""
-    from .ptycho.solvers.lstsq import _workspace
     D, (H, W) = psi.shape[0], psi.shape[-2:]
     N, S, det = scan.shape[0], probe.shape[2], op.detector_shape
-    dev = psi.device
     A.current_device()  # (hands the library its deterministic-mode scratch)
     st = A.stream_ptr()
     inten, tangent = _jvp_outputs(op, psi, scan, fly, primal, sink)
@@ -1218,30 +1350,20 @@ def _multislice_jvp_chunks(op, psi, probe, scan, d_psi, d_probe, d_scan, fly,
         return inten, tangent
     if sink is None:
         sink = _tangent_sink(inten, tangent, fly, "multislice_intensity_jvp")
-    fused = _fused_route(op, probe)
     # one set more than the forward: the tangent (the general route keeps the
     # forward's chunk, which bounds a launch, not the memory)
-    chunk = _slices_chunk(op, psi, probe, fly, fused, extra=1)
-    nmax = min(chunk, N)
+    forward = _SlicesForward(op, fly, psi, probe, scan, extra=1)
+    fused = forward.fused
     fresnel = op.diffraction.propagation
     fwd_scale, inv_scale = fft_scales(det, op.norm)
+    dwave_all = forward.tangent()
     if fused:
-        far_all, mid, beams, _ = _fused_buffers(op, psi, probe, nmax)
-        dwave_all = _workspace(op).get("ms_tangent", (nmax, S, det, det),
-                                       torch.complex64, dev)
-        prop = fresnel._propagator((det, det), dev)
-    else:
-        dwave_all = torch.empty((nmax, S, det, det), dtype=torch.complex64,
-                                device=dev)
-    for lo in range(0, N, chunk):
-        hi = min(N, lo + chunk)
+        mid = forward.mid
+        prop = fresnel._propagator((det, det), psi.device)
+    for lo, hi, far, beams in forward:
         n = hi - lo
         sc = scan[lo:hi]
         dsc = None if d_scan is None else d_scan[lo:hi]
-        if fused:
-            far = _fused_far(op, psi, sc, probe, far_all, beams)
-        else:
-            far, incident = _general_far(op, psi, sc, probe)
         dwave = dwave_all[:n]
         for d in range(D):
             dslice = None if d_psi is None else d_psi[d]
@@ -1275,8 +1397,7 @@ def _multislice_jvp_chunks(op, psi, probe, scan, d_psi, d_probe, d_scan, fly,
                           "tangent: pass 2)")
                 else:
                     dwave = fresnel.fwd(dwave, overwrite=True)
-                beam = beams[d - 1, :n] if fused else incident[d]
-                per_scan, dbeam, dper_scan = 1, dwave, 1
+                beam, per_scan, dbeam, dper_scan = beams[d], 1, dwave, 1
             # (de_d goes over dbeam_d where that is per position)
             check(
                 lib.tike_slice_wave_tangent(
@@ -1313,19 +1434,10 @@ def multislice_intensity_jvp(operator, psi, probe, scan, *, d_psi=None,
     for a tangent that does not match its primal -- a (1, H, W) tangent of a
     (D, H, W) object among them --, before any launch.
     """
-    name = "multislice_intensity_jvp"
-    fly, (d_psi, d_probe, d_scan) = _checked_jvp(
-        name, operator, psi, probe, scan, d_psi, d_probe, d_scan, fly,
-        check_positions, slices=True)
-    psi, probe, scan = (x.detach().contiguous() for x in (psi, probe, scan))
-    single = psi.shape[0] == 1
-    if d_psi is None and d_probe is None and d_scan is None:
-        with torch.no_grad():
-            inten = (_Intensity if single else _MultisliceIntensity).apply(
-                psi, probe, scan, operator, fly)
-        return inten, torch.zeros_like(inten)
-    return (_jvp_chunks if single else _multislice_jvp_chunks)(
-        operator, psi, probe, scan, d_psi, d_probe, d_scan, fly)
+    return _jvp("multislice_intensity_jvp", operator,
+                (psi, probe, scan, None, None),
+                (d_psi, d_probe, d_scan, None, None), fly, check_positions,
+                slices=True)
 
 
 def multislice_gauss_newton_product(operator, psi, probe, scan, *, d_psi=None,
@@ -1348,105 +1460,13 @@ def multislice_gauss_newton_product(operator, psi, probe, scan, *, d_psi=None,
     `wrt` other than the three (or none, or one twice), TypeError / ValueError
     for a weight of another type, dtype, shape or device.
     """
-    name = "multislice_gauss_newton_product"
-    wrt = _checked_product(name, operator, psi, scan, weight, fly, wrt)
-    fly, (d_psi, d_probe, d_scan) = _checked_jvp(
-        name, operator, psi, probe, scan, d_psi, d_probe, d_scan, fly,
-        check_positions, slices=True)
-    leaves = {k: x.detach().contiguous().requires_grad_(k in wrt)
-              for k, x in zip(_WRT, (psi, probe, scan))}
-    if d_psi is None and d_probe is None and d_scan is None:
-        return tuple(torch.zeros_like(leaves[k]) for k in wrt)
-    single = psi.shape[0] == 1
-    tangent = (_jvp_chunks if single else _multislice_jvp_chunks)(
-        operator, *(leaves[k].detach() for k in _WRT), d_psi, d_probe, d_scan,
-        fly, primal=False)[1]
-    if weight is not None:
-        tangent = tangent * weight.detach()
-    with torch.enable_grad():
-        inten = (_Intensity if single else _MultisliceIntensity).apply(
-            leaves["psi"], leaves["probe"], leaves["scan"], operator, fly)
-        return torch.autograd.grad(inten, [leaves[k] for k in wrt],
-                                   grad_outputs=tangent)
+    return _gauss_newton("multislice_gauss_newton_product", _WRT, operator,
+                         (psi, probe, scan, None, None),
+                         (d_psi, d_probe, d_scan, None, None), weight, fly,
+                         wrt, check_positions, slices=True)
 
 
 # ------------------------------------------------ forward mode, eigen probes
-def _eigen_jvp_chunks(op, psi, probe, scan, eigen, weights, d_psi, d_probe,
-                      d_scan, d_eigen, d_weights, fly, primal=True, sink=None):
-    """(I or None, dI): the chunk loop of `eigen_intensity_jvp` on contiguous
-    device tensors (eigen, d_eigen: None for C = 0); at least one tangent is
-    not None.  sink: as in `_jvp_chunks`."""
-    from .ptycho.solvers.lstsq import chunk_positions
-    N, S = scan.shape[0], probe.shape[2]
-    C, M = (0, 0) if eigen is None else eigen.shape[1:3]
-    pw, det = op.probe_shape, op.detector_shape
-    H, W = psi.shape[-2:]
-    dev = psi.device
-    A.current_device()  # (hands the library its deterministic-mode scratch)
-    st = A.stream_ptr()
-    inten, tangent = _jvp_outputs(op, psi, scan, fly, primal, sink)
-    if N == 0:
-        return inten, tangent
-    if sink is None:
-        sink = _tangent_sink(inten, tangent, fly, "eigen_intensity_jvp")
-    # the far plane and its tangent are both resident; whole frames
-    chunk = max(1, chunk_positions(S, det) // 2 // fly) * fly
-    rows = min(chunk, N)
-    far_all = torch.empty((rows, 1, S, det, det), dtype=torch.complex64,
-                          device=dev)
-    dfar_all = torch.empty_like(far_all)
-    fwd_scale = fft_scales(det, op.norm)[0]
-    for lo in range(0, N, chunk):
-        hi = min(N, lo + chunk)
-        n = hi - lo
-        sc, w = scan[lo:hi], weights[lo:hi]
-        far, dfar = far_all[:n], dfar_all[:n]
-        op.fwd_device(probe, sc, psi, eigen, w, out=far)
-        check(
-            lib.tike_eigen_wave_tangent(
-                A.ptr(psi), A.ptr(d_psi), A.ptr(sc),
-                None if d_scan is None else A.ptr(d_scan[lo:hi]),
-                A.ptr(probe), A.ptr(d_probe), A.ptr(eigen), A.ptr(d_eigen),
-                A.ptr(w),
-                None if d_weights is None else A.ptr(d_weights[lo:hi]), C, M,
-                A.ptr(dfar), n, S, pw, det, H, W, st),
-            "eigen_intensity_jvp (tangent exit waves)")
-        check(lib.tike_fft2(A.ptr(dfar), A.ptr(dfar), n * S, det, 0,
-                            fwd_scale, st),
-              "eigen_intensity_jvp (tangent far plane)")
-        sink(lo, hi, far, dfar)
-    return inten, tangent
-
-
-def _checked_eigen_jvp(name, operator, psi, probe, scan, eigen_probe,
-                       eigen_weights, d_psi, d_probe, d_scan, d_eigen_probe,
-                       d_eigen_weights, fly, check_positions):
-    """`_checked_jvp` for the eigen form: (fly, the five tangents)."""
-    if d_eigen_probe is not None and eigen_probe is None:
-        raise ValueError(
-            f"{name}: d_eigen_probe without eigen_probe (there is no eigen "
-            "probe it could be the tangent of)")
-    tangents = None
-    if all(isinstance(x, torch.Tensor)
-           for x in (psi, probe, scan, eigen_weights)) and isinstance(
-               eigen_probe, (torch.Tensor, type(None))):
-        # (host arrays: `_checked` below names them)
-        more = [("eigen_weights", eigen_weights, d_eigen_weights)]
-        if eigen_probe is not None:
-            more.insert(0, ("eigen_probe", eigen_probe, d_eigen_probe))
-        tangents = _checked_tangents(name, psi, probe, scan, d_psi, d_probe,
-                                     d_scan, more)
-        if eigen_probe is None:
-            tangents.insert(3, None)
-    if eigen_weights is None:
-        raise TypeError(
-            f"{name}: eigen_weights is required (without them `intensity_jvp` "
-            "is the forward mode of the model)")
-    fly = _checked(operator, psi, probe, scan, fly, check_positions, name=name,
-                   eigen_probe=eigen_probe, eigen_weights=eigen_weights)
-    return fly, tangents
-
-
 def eigen_intensity_jvp(operator, psi, probe, scan, *, eigen_probe=None,
                         eigen_weights, d_psi=None, d_probe=None, d_scan=None,
                         d_eigen_probe=None, d_eigen_weights=None, fly=1,
@@ -1472,20 +1492,10 @@ def eigen_intensity_jvp(operator, psi, probe, scan, *, eigen_probe=None,
     d_eigen_probe without eigen_probe, and TypeError / ValueError for a
     tangent that does not match its primal, before any launch.
     """
-    fly, (d_psi, d_probe, d_scan, d_eigen, d_weights) = _checked_eigen_jvp(
-        "eigen_intensity_jvp", operator, psi, probe, scan, eigen_probe,
-        eigen_weights, d_psi, d_probe, d_scan, d_eigen_probe, d_eigen_weights,
-        fly, check_positions)
-    psi, probe, scan, weights = (x.detach().contiguous()
-                                 for x in (psi, probe, scan, eigen_weights))
-    eigen = None if eigen_probe is None else eigen_probe.detach().contiguous()
-    if all(t is None for t in (d_psi, d_probe, d_scan, d_eigen, d_weights)):
-        with torch.no_grad():
-            inten = _EigenIntensity.apply(psi, probe, scan, eigen, weights,
-                                          operator, fly)
-        return inten, torch.zeros_like(inten)
-    return _eigen_jvp_chunks(operator, psi, probe, scan, eigen, weights, d_psi,
-                             d_probe, d_scan, d_eigen, d_weights, fly)
+    return _jvp("eigen_intensity_jvp", operator,
+                (psi, probe, scan, eigen_probe, eigen_weights),
+                (d_psi, d_probe, d_scan, d_eigen_probe, d_eigen_weights), fly,
+                check_positions, eigen=True)
 
 
 _EIGEN_WRT = ("psi", "probe", "scan", "eigen_probe", "eigen_weights")
@@ -1514,32 +1524,11 @@ def eigen_gauss_newton_product(operator, psi, probe, scan, *, eigen_probe=None,
     with eigen_probe=None, TypeError / ValueError for a weight of another
     type, dtype, shape or device.
     """
-    name = "eigen_gauss_newton_product"
-    wrt = _checked_product(name, operator, psi, scan, weight, fly, wrt,
-                           names=_EIGEN_WRT)
-    if "eigen_probe" in wrt and eigen_probe is None:
-        raise ValueError(
-            f'{name}: "eigen_probe" in wrt with eigen_probe=None (there is no '
-            "eigen probe to differentiate with respect to)")
-    fly, tangents = _checked_eigen_jvp(
-        name, operator, psi, probe, scan, eigen_probe, eigen_weights, d_psi,
-        d_probe, d_scan, d_eigen_probe, d_eigen_weights, fly, check_positions)
-    leaves = {k: None if x is None else
-              x.detach().contiguous().requires_grad_(k in wrt)
-              for k, x in zip(_EIGEN_WRT, (psi, probe, scan, eigen_probe,
-                                           eigen_weights))}
-    if all(t is None for t in tangents):
-        return tuple(torch.zeros_like(leaves[k]) for k in wrt)
-    tangent = _eigen_jvp_chunks(
-        operator, *(None if leaves[k] is None else leaves[k].detach()
-                    for k in _EIGEN_WRT), *tangents, fly, primal=False)[1]
-    if weight is not None:
-        tangent = tangent * weight.detach()
-    with torch.enable_grad():
-        inten = _EigenIntensity.apply(*(leaves[k] for k in _EIGEN_WRT),
-                                      operator, fly)
-        return torch.autograd.grad(inten, [leaves[k] for k in wrt],
-                                   grad_outputs=tangent)
+    return _gauss_newton(
+        "eigen_gauss_newton_product", _EIGEN_WRT, operator,
+        (psi, probe, scan, eigen_probe, eigen_weights),
+        (d_psi, d_probe, d_scan, d_eigen_probe, d_eigen_weights), weight, fly,
+        wrt, check_positions, eigen=True)
 
 
 # ------------------------------------------------- the noise-model cost
@@ -1657,13 +1646,6 @@ class _Counts:
             "cost (tike_cost_curvature)")
 
 
-def _cost_chunk_rows(op, probe, fly, halve=False):
-    """Positions per chunk of the one-slice forms, whole frames."""
-    from .ptycho.solvers.lstsq import chunk_positions
-    chunk = chunk_positions(probe.shape[2], op.detector_shape)
-    return max(1, chunk // (2 if halve else 1) // fly) * fly
-
-
 def _cost_forward(op, counts, psi, probe, scan, eigen, weights):
     """(frames,) costs: per chunk the form's forward and tike_cost_factor."""
     fly = counts.fly
@@ -1673,29 +1655,17 @@ def _cost_forward(op, counts, psi, probe, scan, eigen, weights):
     if N == 0:
         return costs
     if psi.shape[0] > 1:
-        fused = _fused_route(op, probe)
-        chunk = _slices_chunk(op, psi, probe, fly, fused)
-        if fused:
-            far_all, _, beams, _ = _fused_buffers(op, psi, probe,
-                                                  min(chunk, N))
-        for lo in range(0, N, chunk):
-            hi = min(N, lo + chunk)
-            sc = scan[lo:hi]
-            far = (_fused_far(op, psi, sc, probe, far_all, beams) if fused
-                   else _general_far(op, psi, sc, probe)[0])
+        for lo, hi, far, beams in _SlicesForward(op, fly, psi, probe, scan):
+            del beams  # (general route: only the far plane is kept)
             counts.factor(lo, hi, far, None, costs, None)
         return costs
-    chunk = _cost_chunk_rows(op, probe, fly)
+    chunk = _chunk_rows(op, probe, fly)
     far_all = torch.empty((min(chunk, N), 1, S, det, det),
                           dtype=torch.complex64, device=psi.device)
     for lo in range(0, N, chunk):
         hi = min(N, lo + chunk)
-        far = far_all[:hi - lo]
-        if weights is None:
-            op.fwd_device(probe, scan[lo:hi], psi, out=far)
-        else:
-            op.fwd_device(probe, scan[lo:hi], psi, eigen, weights[lo:hi],
-                          out=far)
+        far = _one_slice_far(op, psi, probe, scan, eigen, weights, lo, hi,
+                             far_all)
         counts.factor(lo, hi, far, None, costs, None)
     return costs
 
@@ -1807,14 +1777,10 @@ def _cost_tangents(name, operator, data, measured_pixels, model, psi, probe,
             f"{name}: d_eigen_probe or d_eigen_weights without eigen_weights")
 
     def checked(slices):
-        if eigen_weights is not None:
-            return _checked_eigen_jvp(
-                name, operator, psi, probe, scan, eigen_probe, eigen_weights,
-                d_psi, d_probe, d_scan, d_eigen_probe, d_eigen_weights, fly,
-                check_positions)
-        f, t = _checked_jvp(name, operator, psi, probe, scan, d_psi, d_probe,
-                            d_scan, fly, check_positions, slices=slices)
-        return f, list(t) + [None, None]
+        return _checked_jvp(
+            name, operator, (psi, probe, scan, eigen_probe, eigen_weights),
+            (d_psi, d_probe, d_scan, d_eigen_probe, d_eigen_weights), fly,
+            check_positions, slices=slices, eigen=eigen_weights is not None)
 
     (fly, tangents), data, mask, nm, model = _checked_cost(
         name, operator, data, measured_pixels, model, psi, probe, scan,
@@ -1822,21 +1788,6 @@ def _cost_tangents(name, operator, data, measured_pixels, model, psi, probe,
     primals = [None if x is None else x.detach().contiguous()
                for x in (psi, probe, scan, eigen_probe, eigen_weights)]
     return _Counts(data, mask, nm, model, fly), primals, list(tangents)
-
-
-def _cost_jvp_chunks(op, primals, tangents, fly, sink):
-    """The form's forward-mode chunk loop with `sink` in the place of
-    tike_intensity_tangent."""
-    psi, probe, scan, eigen, weights = primals
-    if weights is not None:
-        _eigen_jvp_chunks(op, psi, probe, scan, eigen, weights, *tangents,
-                          fly, primal=False, sink=sink)
-    elif psi.shape[0] > 1:
-        _multislice_jvp_chunks(op, psi, probe, scan, *tangents[:3], fly,
-                               primal=False, sink=sink)
-    else:
-        _jvp_chunks(op, psi, probe, scan, *tangents[:3], fly, primal=False,
-                    sink=sink)
 
 
 def cost_jvp(operator, data, psi, probe, scan, *, model="gaussian",
@@ -1864,10 +1815,10 @@ def cost_jvp(operator, data, psi, probe, scan, *, model="gaussian",
     costs = torch.empty(primals[2].shape[0] // fly, dtype=torch.float32,
                         device=primals[0].device)
     dcosts = torch.empty_like(costs)
-    _cost_jvp_chunks(
-        operator, primals, tangents, fly,
-        lambda lo, hi, far, dfar: counts.curvature(lo, hi, far, dfar, None,
-                                                   costs, dcosts, None))
+    _jvp_loop(
+        operator, primals, tangents, fly, primal=False,
+        sink=lambda lo, hi, far, dfar: counts.curvature(
+            lo, hi, far, dfar, None, costs, dcosts, None))
     return costs, dcosts
 
 
@@ -1905,33 +1856,15 @@ def cost_gauss_newton_product(operator, data, psi, probe, scan, *,
     """
     name = "cost_gauss_newton_product"
     names = _EIGEN_WRT if eigen_weights is not None else _WRT
-    wrt = _checked_product(name, operator, psi, scan, None, fly,
-                           names if wrt is None else wrt, names=names)
-    if "eigen_probe" in wrt and eigen_probe is None:
-        raise ValueError(
-            f'{name}: "eigen_probe" in wrt with eigen_probe=None (there is no '
-            "eigen probe to differentiate with respect to)")
+    wrt = _checked_product(
+        name, operator, (psi, probe, scan, eigen_probe, eigen_weights), None,
+        fly, names if wrt is None else wrt, names)
     floor = float(floor)
     if not (floor >= 0.0 and floor != float("inf")):
         raise ValueError(f"{name}: floor must be finite and >= 0, not {floor}")
     if upstream is not None:
-        if not isinstance(upstream, torch.Tensor):
-            raise TypeError(
-                f"{name}: upstream must be a torch device tensor, not "
-                f"{type(upstream).__name__}")
-        if upstream.dtype != torch.float32:
-            raise TypeError(
-                f"{name}: upstream must be torch.float32, not "
-                f"{upstream.dtype}")
-        frames = _frames(scan, fly)
-        if frames is not None and tuple(upstream.shape) != (frames,):
-            raise ValueError(
-                f"{name}: upstream must be (N // fly,) = ({frames},), not "
-                f"{tuple(upstream.shape)}")
-        if isinstance(psi, torch.Tensor) and upstream.device != psi.device:
-            raise ValueError(
-                f"{name}: upstream lives on {upstream.device}, psi on "
-                f"{psi.device}")
+        _checked_frame_tensor(name, "upstream", upstream, operator, psi, scan,
+                              fly, planes=False)
         upstream = upstream.detach().contiguous()
     counts, primals, tangents = _cost_tangents(
         name, operator, data, measured_pixels, model, psi, probe, scan,
@@ -1947,17 +1880,16 @@ def cost_gauss_newton_product(operator, data, psi, probe, scan, *,
     if psi.shape[0] > 1:
         table = torch.empty((scan.shape[0] // fly, det, det),
                             dtype=torch.float32, device=dev)
-        _cost_jvp_chunks(
-            op, primals, tangents, fly,
-            lambda lo, hi, far, dfar: counts.curvature(
+        _jvp_loop(
+            op, primals, tangents, fly, primal=False,
+            sink=lambda lo, hi, far, dfar: counts.curvature(
                 lo, hi, far, dfar, upstream, None, None,
                 table[lo // fly:hi // fly], floor))
         grads = _multislice_backward_chunks(
             op, fly, psi, probe, scan, want[:3],
             lambda lo, hi, far: table[lo // fly:hi // fly]) + (None, None)
     else:
-        rows = min(_cost_chunk_rows(op, probe, fly, halve=True),
-                   scan.shape[0])
+        rows = min(_chunk_rows(op, probe, fly, halve=True), scan.shape[0])
         back = _Back(op, fly, psi, probe, scan, want, rows, eigen, weights,
                      resident=True)
         table_all = torch.empty((rows // fly, det, det), dtype=torch.float32,
@@ -1971,6 +1903,6 @@ def cost_gauss_newton_product(operator, data, psi, probe, scan, *,
             # inverse writes there)
             back.run(lo, hi, far, table, spare=dfar)
 
-        _cost_jvp_chunks(op, primals, tangents, fly, sink)
+        _jvp_loop(op, primals, tangents, fly, primal=False, sink=sink)
         grads = back.result()
     return tuple(dict(zip(_EIGEN_WRT, grads))[k] for k in wrt)
