@@ -646,6 +646,13 @@ int tike_gen_inv_rows_gradients(const void* hand2, const void* patches, const vo
  *   sub-tile (y qM mod p, x qM mod p) at element (y qp mod M, x qp mod M),
  *   qM = M^-1 mod p, qp = p^-1 mod M; the far plane in sub-tile (k1y, k1x) at
  *   (k2y, k2x) is frequency (M qM k1 + p qp k2) mod det.
+ *   At 1024 and 2048 (p = 4, M = det / 4) the same array holds tile row y and
+ *   column x in sub-tile (y mod 4, x mod 4) at element (y / 4, x / 4), i.e.
+ *   sub-tile n1, element n2 is coordinate n1 + 4 n2; the far plane in sub-tile
+ *   (k1y, k1x) at (k2y, k2x) is frequency k2 + M k1.  The sub-tile transforms
+ *   of tike_pfa_fft2 are plain; the twiddle w_det^(n1 k2) between them and the
+ *   4 x 4 DFT belongs to tike_pfa_combine_gradient (its conjugate on the way
+ *   back).
  * A chunk: tike_pfa_fwd_gather -> tike_pfa_fft2(forward) ->
  * tike_pfa_combine_gradient -> tike_pfa_fft2(inverse) -> tike_pfa_inv_products
  * -> tike_scatter_patches; probe arguments as in tike_gen_fwd_rows. */

@@ -192,7 +192,7 @@ template <int P>
 __global__ __launch_bounds__(256) void pfa_fwd_gather_kernel(
     const cf* __restrict__ psi, const float* __restrict__ scan, const TkProbe probe,
     cf* __restrict__ A, cf* __restrict__ patches, PfaGeom g, int nscan, int S, int pw, int H,
-    int W, int chunk) {
+    int W, int chunk, int hoist_fits) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   cf* orow = reinterpret_cast<cf*>(lds_raw);  // pw: the patch row
   cf* prw = orow + pw;                        // S x pw
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(256) void pfa_fwd_gather_kernel(
   const int det = g.det, pad = (det - pw) / 2, M = g.M;
   const long total = (long)H * W;
   const long MM = (long)M * M, tile = (long)det * det;
-  const bool hoist = pfa_hoistable(probe);
+  const bool hoist = hoist_fits && pfa_hoistable(probe);
   const int nchunk = (nscan + chunk - 1) / chunk;
   const unsigned nitem = (unsigned)det * (unsigned)nchunk;
   for (unsigned item = blockIdx.x; item < nitem; item += gridDim.x) {
@@ -658,7 +658,8 @@ template <int P>
 __global__ __launch_bounds__(256) void pfa_inv_products_kernel(
     const cf* __restrict__ C, const cf* __restrict__ patches, const TkProbe probe,
     cf* __restrict__ objproj, cf* __restrict__ chi0, float* __restrict__ mpu, float mpu_scale,
-    float* __restrict__ part, PfaGeom g, int nscan, int S, int pw, int chunk, float inv_scale) {
+    float* __restrict__ part, PfaGeom g, int nscan, int S, int pw, int chunk, float inv_scale,
+    int hoist_fits) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   cf* acc = reinterpret_cast<cf*>(lds_raw);  // S x pw
   cf* prw = acc + S * pw;                    // S x pw
@@ -668,7 +669,7 @@ __global__ __launch_bounds__(256) void pfa_inv_products_kernel(
   const int nchunk = (nscan + chunk - 1) / chunk;
   const unsigned nitem = (unsigned)pw * (unsigned)nchunk;
   const bool grad = mpu != nullptr || part != nullptr;
-  const bool hoist = pfa_hoistable(probe);
+  const bool hoist = hoist_fits && pfa_hoistable(probe);
   for (unsigned item = blockIdx.x; item < nitem; item += gridDim.x) {
     const long c = item / (unsigned)pw;
     const int y = (int)(item - (unsigned)c * (unsigned)pw);
@@ -785,16 +786,24 @@ __global__ __launch_bounds__(256) void pfa_inv_products_kernel(
 // ------------------------------------------------------------------ entries
 // dynamic LDS of the gather (`rows` = 1: the patch row) and of the products
 // (`rows` = S: the accumulators): + the hoisted probe and eigen rows
-static size_t pfa_lds(const TkProbe& p, int rows) {
+// Where the hoisted rows do not fit (many eigen probes: C Sm rows on top of the
+// S that tike_pfa_supported counts), `*hoist_fits` = 0 and the kernel reads
+// the probe per use, as it does for a probe given per position.
+static const size_t PFA_LDS_MAX = 150 * 1024;
+static size_t pfa_lds(const TkProbe& p, int rows, int* hoist_fits) {
   const int ne = p.weights != nullptr && p.eigen != nullptr ? p.C * p.Sm : 0;
-  return sizeof(cf) * (size_t)p.pw * (size_t)(rows + p.S + ne);
+  const size_t own = sizeof(cf) * (size_t)p.pw * (size_t)rows;
+  const size_t all = sizeof(cf) * (size_t)p.pw * (size_t)(rows + p.S + ne);
+  *hoist_fits = all <= PFA_LDS_MAX ? 1 : 0;
+  return *hoist_fits ? all : own;
 }
 
 extern "C" int tike_pfa_supported(int S, int pw, int det) {
   PfaGeom g;
   if (S < 1 || pw < 1 || det < pw || !pfa_geom(det, &g)) return 0;
-  // (LDS of the products: accumulators + probe rows + up to 2 S eigen rows)
-  return sizeof(cf) * (size_t)(4 * S) * pw <= 150 * 1024 ? 1 : 0;
+  // (LDS of the products: accumulators + probe rows + up to 2 S eigen rows;
+  // with more eigen rows than fit, the launchers drop the hoisted rows)
+  return sizeof(cf) * (size_t)(4 * S) * pw <= PFA_LDS_MAX ? 1 : 0;
 }
 
 extern "C" int tike_pfa_fwd_gather(const void* psi, const float* scan, const void* probe,
@@ -820,8 +829,10 @@ extern "C" int tike_pfa_fwd_gather(const void* psi, const float* scan, const voi
   const int chunk = (nscan + nchunk - 1) / nchunk;
   nchunk = (nscan + chunk - 1) / chunk;
   const dim3 grid(tk_grid((long)det * nchunk, 16)), block(256);
-  const size_t lds = pfa_lds(P, 1);
-  if (lds > 150 * 1024) return TK_ERR_UNSUPPORTED;
+  int hoist_fits = 1;
+  const size_t lds = pfa_lds(P, 1, &hoist_fits);
+  // (belt and braces: the patch row alone is 8 pw bytes, far below the limit)
+  if (lds > PFA_LDS_MAX) return TK_ERR_UNSUPPORTED;
   if (lds > 48 * 1024) {
     hipError_t e3 = hipFuncSetAttribute((const void*)pfa_fwd_gather_kernel<3>,
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -840,19 +851,19 @@ extern "C" int tike_pfa_fwd_gather(const void* psi, const float* scan, const voi
   }
   if (g.p == 2)
     hipLaunchKernelGGL(pfa_fwd_gather_kernel<2>, grid, block, lds, stream, (const cf*)psi, scan,
-                       P, (cf*)subtiles, (cf*)patches, g, nscan, S, pw, H, W, chunk);
+                       P, (cf*)subtiles, (cf*)patches, g, nscan, S, pw, H, W, chunk, hoist_fits);
   else if (g.p == 4)
     hipLaunchKernelGGL(pfa_fwd_gather_kernel<4>, grid, block, lds, stream, (const cf*)psi, scan,
-                       P, (cf*)subtiles, (cf*)patches, g, nscan, S, pw, H, W, chunk);
+                       P, (cf*)subtiles, (cf*)patches, g, nscan, S, pw, H, W, chunk, hoist_fits);
   else if (g.p == 3)
     hipLaunchKernelGGL(pfa_fwd_gather_kernel<3>, grid, block, lds, stream, (const cf*)psi, scan,
-                       P, (cf*)subtiles, (cf*)patches, g, nscan, S, pw, H, W, chunk);
+                       P, (cf*)subtiles, (cf*)patches, g, nscan, S, pw, H, W, chunk, hoist_fits);
   else if (g.p == 5)
     hipLaunchKernelGGL(pfa_fwd_gather_kernel<5>, grid, block, lds, stream, (const cf*)psi, scan,
-                       P, (cf*)subtiles, (cf*)patches, g, nscan, S, pw, H, W, chunk);
+                       P, (cf*)subtiles, (cf*)patches, g, nscan, S, pw, H, W, chunk, hoist_fits);
   else
     hipLaunchKernelGGL(pfa_fwd_gather_kernel<7>, grid, block, lds, stream, (const cf*)psi, scan,
-                       P, (cf*)subtiles, (cf*)patches, g, nscan, S, pw, H, W, chunk);
+                       P, (cf*)subtiles, (cf*)patches, g, nscan, S, pw, H, W, chunk, hoist_fits);
   TK_LAUNCH_CHECK();
   return TK_OK;
 }
@@ -1002,8 +1013,11 @@ extern "C" int tike_pfa_inv_products(const void* subtiles, const void* patches,
       if (!part) return TK_ERR_ARG;
     }
   }
-  const size_t lds = pfa_lds(P, S);
-  if (lds > 150 * 1024) return TK_ERR_UNSUPPORTED;
+  int hoist_fits = 1;
+  const size_t lds = pfa_lds(P, S, &hoist_fits);
+  // (belt and braces: the accumulators alone are 8 S pw bytes, a quarter of
+  // what tike_pfa_supported admits)
+  if (lds > PFA_LDS_MAX) return TK_ERR_UNSUPPORTED;
   if (lds > 48 * 1024) {
     hipError_t e3 = hipFuncSetAttribute((const void*)pfa_inv_products_kernel<3>,
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1024,23 +1038,23 @@ extern "C" int tike_pfa_inv_products(const void* subtiles, const void* patches,
   if (g.p == 2)
     hipLaunchKernelGGL(pfa_inv_products_kernel<2>, grid, block, lds, stream, (const cf*)subtiles,
                        (const cf*)patches, P, (cf*)objproj, (cf*)chi0, (float*)m_probe_update,
-                       probe_update_scale, part, g, nscan, S, pw, chunk, inv_scale);
+                       probe_update_scale, part, g, nscan, S, pw, chunk, inv_scale, hoist_fits);
   else if (g.p == 4)
     hipLaunchKernelGGL(pfa_inv_products_kernel<4>, grid, block, lds, stream, (const cf*)subtiles,
                        (const cf*)patches, P, (cf*)objproj, (cf*)chi0, (float*)m_probe_update,
-                       probe_update_scale, part, g, nscan, S, pw, chunk, inv_scale);
+                       probe_update_scale, part, g, nscan, S, pw, chunk, inv_scale, hoist_fits);
   else if (g.p == 3)
     hipLaunchKernelGGL(pfa_inv_products_kernel<3>, grid, block, lds, stream, (const cf*)subtiles,
                        (const cf*)patches, P, (cf*)objproj, (cf*)chi0, (float*)m_probe_update,
-                       probe_update_scale, part, g, nscan, S, pw, chunk, inv_scale);
+                       probe_update_scale, part, g, nscan, S, pw, chunk, inv_scale, hoist_fits);
   else if (g.p == 5)
     hipLaunchKernelGGL(pfa_inv_products_kernel<5>, grid, block, lds, stream, (const cf*)subtiles,
                        (const cf*)patches, P, (cf*)objproj, (cf*)chi0, (float*)m_probe_update,
-                       probe_update_scale, part, g, nscan, S, pw, chunk, inv_scale);
+                       probe_update_scale, part, g, nscan, S, pw, chunk, inv_scale, hoist_fits);
   else
     hipLaunchKernelGGL(pfa_inv_products_kernel<7>, grid, block, lds, stream, (const cf*)subtiles,
                        (const cf*)patches, P, (cf*)objproj, (cf*)chi0, (float*)m_probe_update,
-                       probe_update_scale, part, g, nscan, S, pw, chunk, inv_scale);
+                       probe_update_scale, part, g, nscan, S, pw, chunk, inv_scale, hoist_fits);
   TK_LAUNCH_CHECK();
   if (part) return tk_ordered_sum((float*)m_probe_update, part, nmpu, nchunk, true, stream);
   return TK_OK;
