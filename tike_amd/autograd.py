@@ -70,7 +70,10 @@ exact adjoint through every slice with no division by D:
 
 Per chunk of whole frames, the forward recomputed, on the route `cgrad` takes
 for the shape (`fused_slices`; its `MULTISLICE_FUSED` and
-`MULTISLICE_STEP_BACK_FUSED` are honoured):
+`MULTISLICE_STEP_BACK_FUSED` are honoured) and through cgrad's own code: the
+route, the chunk, the `ms_*` buffers, the forward of a chunk and the fused
+step back are the functions of ptycho/solvers/_multislice.py, called with
+F^H's scale and a projection plane per slice:
 
 * fused (128^2, 256^2, 512^2, at most 8 modes): `fused_forward` ->
   tike_fft2_pass2_inplace -> tike_ifft2_pass1_scaled (g applied while inverse
@@ -135,13 +138,14 @@ Per chunk of whole frames -- the far plane, the D - 1 sets of incident beams
 and ONE tangent set are resident, one set more than the forward holds --
 
     the primal as `multislice_intensity` runs it (`_SlicesForward`, the one
-    forward of a chunk, over `_fused_far` or `_general_far`: I has its bits;
+    forward of a chunk, over `fused_far` or `general_far` of
+    ptycho/solvers/_multislice.py, cgrad's own: I has its bits;
     both leave the beam incident on every slice) -> per slice
     tike_slice_wave_tangent, de_d written over dbeam_d in
     place (slice 0: the shared probe and d_probe), and between two slices the
     Fresnel step of the tangent (fused route: tike_fft2_pass1 ->
     tike_fresnel_colpass -> tike_fft2_pass2_inplace with the scale of
-    `_fused_far`, measured faster; general route: tike_fresnel_spect_prop in
+    `fused_far`, measured faster; general route: tike_fresnel_spect_prop in
     place) -> tike_fft2 (in place, forward scale) -> tike_intensity_tangent
 
 with no torch arithmetic; no tangent at all: only the primal launches.  One
@@ -224,9 +228,9 @@ from torch.autograd.function import once_differentiable
 
 from . import _arrays as A
 from ._lib import check, lib
-from .operators.multislice import (Multislice, chunk_within_hbm, fused_forward,
-                                   fused_slices)
+from .operators.multislice import Multislice
 from .operators.propagation import fft_scales
+from .ptycho.solvers import _multislice
 
 MAX_MODES = 16
 """Probe modes `tike_lstsq_gradients` takes (TK_MAX_MODES)."""
@@ -960,78 +964,22 @@ trip of the far plane through memory; the tests compare the two."""
 
 
 def _cgrad():
-    """cgrad's MODULE, whose levers choose the route (the package exports the
-    solver function under the module's name)."""
+    """cgrad's MODULE, whose levers `MULTISLICE_FUSED` and
+    `MULTISLICE_STEP_BACK_FUSED` choose the route.  Through `importlib`
+    because the solvers package exports the solver FUNCTION under the
+    module's name (`from .ptycho.solvers import cgrad` is the function), and
+    looked up where a lever is read, not once at import: tests and tools set
+    the levers on the module between calls."""
     return importlib.import_module(__package__ + ".ptycho.solvers.cgrad")
-
-
-def _fused_route(op, probe):
-    """True: the two-pass kernels; as `cgrad` chooses."""
-    cgrad = _cgrad()
-    return bool(cgrad.MULTISLICE_FUSED and fused_slices(
-        probe.shape[-1], op.detector_shape, probe.shape[-3]))
-
-
-def _slices_chunk(op, psi, probe, fly, fused, extra=0):
-    """Positions per chunk, whole frames.  Fused route: far + mid + D - 1 sets
-    of incident probes + the D objproj planes (D / S of a set, rounded up)
-    + `extra` sets (the forward mode's tangent) within half the free HBM, as
-    `cgrad` sizes its multislice chunks."""
-    from .ptycho.solvers import lstsq
-    D, S, det = psi.shape[0], probe.shape[-3], op.detector_shape
-    if lstsq.CHUNK_POSITIONS_OVERRIDE or not fused:
-        chunk = lstsq.chunk_positions(S, det)
-    else:
-        chunk = chunk_within_hbm(lstsq._workspace(op), psi.device,
-                                 D + 1 + -(-D // S) + extra, S, det)
-    return max(1, chunk // fly) * fly
-
-
-def _fused_buffers(op, psi, probe, nmax):
-    """(far, mid, beams, objproj (D, nmax, pw, pw)) from the operator's
-    workspace -- the buffers `cgrad` uses for a multislice minibatch."""
-    from .ptycho.solvers.lstsq import _workspace
-    ws, dev, D = _workspace(op), psi.device, psi.shape[0]
-    S, pw, det = probe.shape[-3], probe.shape[-1], op.detector_shape
-    c64 = torch.complex64
-    return (ws.get("ms_far", (nmax, S, det, det), c64, dev),
-            ws.get("ms_mid", (nmax, S, det, det), c64, dev),
-            ws.get("ms_beams", (max(D - 1, 1), nmax, S, pw, pw), c64, dev),
-            ws.get("ms_objproj", (D, nmax, pw, pw), c64, dev))
-
-
-def _fused_far(op, psi, sc, probe, far, beams):
-    """The far plane of a chunk in `far[:n]`, the probes incident on the
-    slices behind the first in `beams[:, :n]`."""
-    n, S, det = sc.shape[0], probe.shape[-3], op.detector_shape
-    fwd_scale, inv_scale = fft_scales(det, op.norm)
-    prop = op.diffraction.propagation._propagator((det, det), psi.device)
-    fused_forward(psi, sc, probe, 0, far[:n], beams, prop,
-                  fwd_scale * inv_scale)
-    check(
-        lib.tike_fft2_pass2_inplace(A.ptr(far), n * S, det, 0, fwd_scale,
-                                    A.stream_ptr()),
-        "multislice_intensity: far field")
-    return far[:n]
-
-
-def _general_far(op, psi, sc, probe):
-    """(far (n, S, det, det), [the probe incident on every slice]) through
-    the general operators."""
-    conv, fresnel = op.diffraction.diffraction, op.diffraction.propagation
-    beams = [probe[0]]  # (1, S, pw, pw), then (n, S, pw, pw)
-    for d in range(psi.shape[0]):
-        wave = conv.fwd(psi=psi[d], scan=sc, probe=beams[d])
-        if d + 1 < psi.shape[0]:
-            beams.append(fresnel.fwd(wave, overwrite=True))
-    return op.propagation.fwd(wave, overwrite=True), beams
 
 
 class _SlicesForward:
     """The forward of `multislice_intensity` chunk by chunk, for its four
     users (the forward, the backward, the forward mode, the cost): the route,
-    the chunk of whole frames (`extra`: as in `_slices_chunk`), on the fused
-    route the workspace buffers, and per chunk the far plane and the beams.
+    the chunk of whole frames (`extra`: sets of (S, det, det) per position a
+    user holds besides; sized as `cgrad` sizes its multislice chunks), on the
+    fused route the workspace buffers, and per chunk the far plane and the
+    beams -- all from `ptycho/solvers/_multislice.py`, which cgrad walks too.
     Iterating yields (lo, hi, far (n, S, det, det), beams) with beams[d]
     (n, S, pw, pw) the beam incident on slice d >= 1.  On the general route
     far and beams are fresh tensors that the iteration does not hold on to:
@@ -1039,13 +987,20 @@ class _SlicesForward:
 
     def __init__(self, op, fly, psi, probe, scan, extra=0):
         self.op, self.psi, self.probe, self.scan = op, psi, probe, scan
-        self.fused = _fused_route(op, probe)
-        self.chunk = _slices_chunk(op, psi, probe, fly, self.fused,
-                                   extra=extra)
+        D, S = psi.shape[0], probe.shape[2]
+        self.fused = _multislice.fused_route(op, probe,
+                                             _cgrad().MULTISLICE_FUSED)
+        # fused route: far + mid + D - 1 sets of incident probes + the D
+        # objproj planes (D / S of a set, rounded up) + `extra` sets
+        chunk = _multislice.chunk_positions(
+            op, psi.device, S, D + 1 + -(-D // S) + extra, self.fused)
+        self.chunk = max(1, chunk // fly) * fly
         self.nmax = min(self.chunk, scan.shape[0])
         if self.fused:
-            (self.far_all, self.mid, self.beams_all,
-             self.objproj) = _fused_buffers(op, psi, probe, max(self.nmax, 1))
+            self.far_all, mid, self.beams_all, self.objproj = (
+                _multislice.fused_buffers(op, psi.device, D, S,
+                                          max(self.nmax, 1), nproj=D))
+            self.mid = mid[0]
 
     def tangent(self):
         """(nmax, S, det, det) for the forward mode's tangent: of the
@@ -1065,29 +1020,26 @@ class _SlicesForward:
             hi = min(N, lo + self.chunk)
             sc = self.scan[lo:hi]
             if self.fused:
-                far = _fused_far(op, psi, sc, probe, self.far_all,
-                                 self.beams_all)
+                far = _multislice.fused_far(op, psi, sc, probe, self.far_all,
+                                            self.beams_all,
+                                            "multislice_intensity")
                 yield lo, hi, far, [probe[0]] + [
                     b[:hi - lo] for b in self.beams_all[:psi.shape[0] - 1]]
             else:
-                yield (lo, hi) + _general_far(op, psi, sc, probe)
+                yield (lo, hi) + _multislice.general_far(op, psi, sc, probe)
 
 
 def _fused_back(op, psi, sc, probe, far, beams, table, fly, mid, objproj, want,
                 acc, gprobe):
     """One chunk of the backward on the two-pass kernels behind the far plane
-    and the incident beams of `_SlicesForward`: the launches of cgrad's
-    `_multislice_chunk_fused` with the upstream gradient `table` for the cost
-    kernel and F^H for the last transform's inverse.  Leaves objproj_d in
-    objproj[d, :n] when the object or the positions want it."""
-    cgrad = _cgrad()
+    and the incident beams of `_SlicesForward`: the upstream gradient `table`
+    applied with pass 1 of F^H, then the walk back that cgrad takes
+    (`_multislice.fused_step_back`).  Leaves objproj_d in objproj[d, :n] when
+    the object or the positions want it."""
     want_psi, want_probe, want_scan = want
-    D, (H, W) = psi.shape[0], psi.shape[-2:]
     n, S, det = sc.shape[0], probe.shape[-3], op.detector_shape
-    need_proj = want_psi or want_scan
     st = A.stream_ptr()
     fwd_scale, inv_scale = fft_scales(det, op.norm)
-    prop = op.diffraction.propagation._propagator((det, det), psi.device)
     mid = mid[:n]
     if PASS1_TAKES_TABLE:
         # S * fly planes share a frame's table
@@ -1104,56 +1056,12 @@ def _fused_back(op, psi, sc, probe, far, beams, table, fly, mid, objproj, want,
         check(lib.tike_fft2_pass1(A.ptr(far), A.ptr(mid), n * S, det, 1, st),
               "multislice_intensity backward (inverse pass 1)")
     # the pass 2 behind it finishes F^H: the FORWARD scale, and the 2 of G
-    scale = 2.0 * fwd_scale
-    one_launch = cgrad.MULTISLICE_STEP_BACK_FUSED and det in (128, 256)
-    for d in range(D - 1, 0, -1):
-        beam = beams[d]
-        proj = objproj[d, :n] if need_proj else None
-        if one_launch:
-            check(
-                lib.tike_slice_step_back(A.ptr(mid), A.ptr(psi[d]), A.ptr(sc),
-                                         A.ptr(beam), A.ptr(proj), A.ptr(far),
-                                         n, S, det, H, W, scale, st),
-                "multislice_intensity backward (step back through a slice)")
-        else:
-            # (objproj is an output of this entry on every call)
-            check(
-                lib.tike_ifft2_pass2_products(
-                    A.ptr(mid), A.ptr(psi[d]), A.ptr(sc), A.ptr(beam), 1,
-                    A.ptr(objproj[d, :n]), None, 1.0, None, 1, n, S, det, H,
-                    W, scale, st),
-                "multislice_intensity backward (inverse pass 2 + object "
-                "projection)")
-            # (beam d - 1 is dead from here on: it takes conj(patch) x wave)
-            check(
-                lib.tike_conv_adj_probe(A.ptr(mid), A.ptr(sc), A.ptr(psi[d]),
-                                        A.ptr(beam), n, S, det, det, H, W, st),
-                "multislice_intensity backward (conj(patch) x wave)")
-            check(lib.tike_fft2_pass1(A.ptr(beam), A.ptr(far), n * S, det, 0,
-                                      st),
-                  "multislice_intensity backward (step back, pass 1)")
-        if want_psi:
-            check(
-                lib.tike_scatter_patches(A.ptr(proj), A.ptr(sc),
-                                         A.ptr(acc[d]), n, det, H, W, st),
-                "multislice_intensity backward (object gradient of a slice)")
-        check(
-            lib.tike_fresnel_colpass(A.ptr(far), A.ptr(prop), 1, A.ptr(mid),
-                                     n * S, det, fwd_scale, st),
-            "multislice_intensity backward (adjoint Fresnel step)")
-        scale = inv_scale
-    check(
-        lib.tike_ifft2_pass2_products(
-            A.ptr(mid), A.ptr(psi[0]), A.ptr(sc), A.ptr(probe), 0,
-            A.ptr(objproj[0, :n]), A.ptr(gprobe), 1.0, None, 0, n, S, det, H,
-            W, scale, st),
-        "multislice_intensity backward (first slice: both products)")
-    if want_psi:
-        check(
-            lib.tike_scatter_patches(A.ptr(objproj[0, :n]), A.ptr(sc),
-                                     A.ptr(acc[0]), n, det, H, W, st),
-            "multislice_intensity backward (object gradient of the first "
-            "slice)")
+    _multislice.fused_step_back(
+        op, psi, sc, probe, far, mid, beams[1:], objproj[:, :n], acc, gprobe,
+        first_scale=2.0 * fwd_scale, scale=inv_scale,
+        want_proj=want_psi or want_scan,
+        one_launch=_cgrad().MULTISLICE_STEP_BACK_FUSED,
+        label="multislice_intensity backward")
 
 
 def _general_back(op, psi, sc, probe, far, beams, table, fly, objproj, want,
@@ -1325,8 +1233,8 @@ def multislice_intensity(operator, psi, probe, scan, *, fly=1,
 TANGENT_FRESNEL_TWO_PASS = True
 """Fused route: the Fresnel step of the tangent between two slices by
 `tike_fft2_pass1` -> `tike_fresnel_colpass` -> `tike_fft2_pass2_inplace` (the
-scale of `_fused_far`, the `ms_mid` workspace for the hand-off) instead of
-`tike_fresnel_spect_prop` in place: 0.68 - 0.77 of its time at 256^2 and 128^2
+scale of `_multislice.fused_far`, the `ms_mid` workspace for the hand-off)
+instead of `tike_fresnel_spect_prop` in place: 0.68 - 0.77 of its time at 256^2 and 128^2
 (profiles/autograd_multislice_jvp.md).  The general route has the one launch
 only; the tests compare the two."""
 

@@ -43,6 +43,40 @@ from ..._lib import check, lib
 MODELS = {"gaussian": 0, "poisson": 1}
 
 
+def stored_farplane_gradient(far, data, mask, costs, n, S, det, model,
+                             unmeasured, nmeasured, st, rule=None, inten=None,
+                             steps=None):
+    """The gradient stage of a STORED far plane `far` (n, S, det, det), in
+    place, with the costs of the n patterns `data` (float32): the one
+    tike_farplane_gradient of lstsq's unfused route and of rpie's multislice
+    paths.  rule: (step_length_start, step_length_weight, dominant mode only)
+    for the Poisson model's per-mode step lengths (exitwave.py:122-234) --
+    tike_intensity -> tike_poisson_steps in front, tike_scale_modes behind;
+    None: the gradient alone.  inten (n, det, det) and steps (n, S) float32:
+    the caller's buffers for them; None: fresh ones."""
+    if rule is not None:
+        if inten is None:
+            inten = torch.empty((n, det, det), dtype=torch.float32,
+                                device=far.device)
+        if steps is None:
+            steps = torch.empty((n, S), dtype=torch.float32,
+                                device=far.device)
+        check(lib.tike_intensity(A.ptr(far), A.ptr(inten), n, S, det * det,
+                                 st), "intensity")
+        check(
+            lib.tike_poisson_steps(A.ptr(far), A.ptr(inten), A.ptr(data),
+                                   A.ptr(mask), A.ptr(steps), n, S, det,
+                                   *rule, st), "poisson step lengths")
+    check(
+        lib.tike_farplane_gradient(A.ptr(far), A.ptr(data), A.ptr(mask), None,
+                                   A.ptr(costs), n, S, det, model, 1,
+                                   unmeasured, nmeasured, st),
+        "farplane gradient")
+    if rule is not None:
+        check(lib.tike_scale_modes(A.ptr(far), A.ptr(steps), A.ptr(mask),
+                                   n * S, det, st), "poisson step scaling")
+
+
 # ------------------------------------------------------------ byte models
 def algorithmic_bytes(name, n, S, det, pw, C, depth=1):
     """HBM bytes the launch `name` must move for n positions (DESIGN.md
@@ -559,24 +593,11 @@ class GradientPlan:
         n, st, d = k.n, c.st, k.data_f32()
         c.op.fwd_device(c.probe, k.scan, c.psi, c.eigen_probe, k.w,
                         out=b.far[:n])
-        if self.poisson:
-            check(lib.tike_intensity(A.ptr(b.far), A.ptr(b.inten), n, S,
-                                     det * det, st), "intensity")
-            check(
-                lib.tike_poisson_steps(
-                    A.ptr(b.far), A.ptr(b.inten), A.ptr(d), A.ptr(c.mask_u8),
-                    A.ptr(b.steps), n, S, det, c.step_start, c.step_weight,
-                    self.dominant, st), "poisson step lengths")
-        check(
-            lib.tike_farplane_gradient(
-                A.ptr(b.far), A.ptr(d), A.ptr(c.mask_u8), None, A.ptr(k.costs),
-                n, S, det, self.model, 1, c.unmeasured, c.nmeasured, st),
-            "farplane gradient")
-        if self.poisson:
-            check(
-                lib.tike_scale_modes(A.ptr(b.far), A.ptr(b.steps),
-                                     A.ptr(c.mask_u8), n * S, det, st),
-                "poisson step scaling")
+        stored_farplane_gradient(
+            b.far, d, c.mask_u8, k.costs, n, S, det, self.model, c.unmeasured,
+            c.nmeasured, st,
+            (c.step_start, c.step_weight, self.dominant) if self.poisson
+            else None, b.inten, b.steps)
         check(
             lib.tike_ifft2_crop(A.ptr(b.far), A.ptr(b.mid), A.ptr(b.chi), n * S,
                                 det, pw, c.inv_scale, st), "ifft2 + crop")

@@ -44,9 +44,13 @@ no variable is recovered, one cost-only evaluation.
   taken back through every slice, conj(patch) x wave between two transforms
   (``tike_slice_step_back``), WITHOUT the division by the number of slices
   that ``Multislice.adj`` keeps from the reference
-  (``_multislice_cost_and_grad``).  One conjugate gradient moves all slices at
-  once, then one the probe; the cost is not linear in the far plane along an
-  object direction any more: every line search is decided on the host.
+  (``_multislice_cost_and_grad``; the route, the chunk, the workspace
+  buffers, the forward of a chunk and the fused walk back are the functions
+  of ``_multislice.py``, which ``tike_amd.autograd`` calls as well, with what
+  differs between the two as arguments).  One conjugate gradient moves all
+  slices at once, then one the probe; the cost is not linear in the far plane
+  along an object direction any more: every line search is decided on the
+  host.
 """
 import logging
 from typing import NamedTuple, Optional
@@ -58,11 +62,10 @@ from ... import _tuning
 from ... import _arrays as A
 from ... import opt
 from ..._lib import check, lib
-from ...operators.multislice import (chunk_within_hbm, fused_forward,
-                                     fused_slices)
 from ...operators.propagation import fft_scales
 from ..exitwave import ExitWaveOptions
 from ..position import gaussian_derivative_taps
+from . import _multislice as M
 from . import lstsq as L
 from ._plan import MODELS
 from .lstsq import (SPLIT_FORWARD_SIZES, _get_nearplane_gradients,
@@ -834,19 +837,14 @@ and 256^2).  False, and always at 512^2: `tike_ifft2_pass2_products(keep_chi)`
 
 def _multislice_chunk_fused(op, psi, sc, probe, d32, costs, cm, want_grad,
                             acc, pacc, bufs):
-    """One chunk on the fused kernels (module docstring; csrc/multislice.hip).
-    acc (D, 2, H, W) float32 or None and pacc (S, pw, pw) complex64 or None
-    receive MINUS the gradients of the chunk."""
-    D, (H, W) = psi.shape[0], psi.shape[-2:]
+    """One chunk on the fused kernels (module docstring; csrc/multislice.hip):
+    the far plane and the walk back of `_multislice.py` around the cost
+    kernel.  acc (D, 2, H, W) float32 or None and pacc (S, pw, pw) complex64
+    or None receive MINUS the gradients of the chunk."""
     n, S, det = sc.shape[0], probe.shape[-3], op.detector_shape
     far, mid, beams, objproj = bufs
-    far, mid, objproj = far[:n], mid[:n], objproj[:n]
     st = A.stream_ptr()
-    fwd_scale, inv_scale = fft_scales(det, op.norm)
-    prop = op.diffraction.propagation._propagator((det, det), psi.device)
-    fused_forward(psi, sc, probe, 0, far, beams, prop, fwd_scale * inv_scale)
-    check(lib.tike_fft2_pass2_inplace(A.ptr(far), n * S, det, 0, fwd_scale, st),
-          "multislice cgrad: far field")
+    far = M.fused_far(op, psi, sc, probe, far, beams, "multislice cgrad")
     check(
         lib.tike_farplane_gradient(A.ptr(far), A.ptr(d32), A.ptr(cm.mask),
                                    None, A.ptr(costs), n, S, det, cm.model,
@@ -855,55 +853,16 @@ def _multislice_chunk_fused(op, psi, sc, probe, d32, costs, cm, want_grad,
     if not want_grad:
         return
     # the far plane holds MINUS the gradient, 0 at unmeasured pixels
+    mid = mid[0, :n]
     check(lib.tike_fft2_pass1(A.ptr(far), A.ptr(mid), n * S, det, 1, st),
           "multislice cgrad: inverse pass 1")
-    one_launch = MULTISLICE_STEP_BACK_FUSED and det in (128, 256)
-    for d in range(D - 1, 0, -1):
-        beam = beams[d - 1, :n]
-        if one_launch:
-            # (no object gradient wanted: no projection, the beams unread)
-            check(
-                lib.tike_slice_step_back(A.ptr(mid), A.ptr(psi[d]), A.ptr(sc),
-                                         A.ptr(beam),
-                                         A.ptr(objproj) if acc is not None
-                                         else None, A.ptr(far), n, S, det, H,
-                                         W, inv_scale, st),
-                "multislice cgrad: step back through a slice")
-        else:
-            check(
-                lib.tike_ifft2_pass2_products(
-                    A.ptr(mid), A.ptr(psi[d]), A.ptr(sc), A.ptr(beam), 1,
-                    A.ptr(objproj), None, 1.0, None, 1, n, S, det, H, W,
-                    inv_scale, st),
-                "multislice cgrad: inverse pass 2 + object projection")
-            # (beam d - 1 is dead from here on: it takes conj(patch) x wave)
-            check(
-                lib.tike_conv_adj_probe(A.ptr(mid), A.ptr(sc), A.ptr(psi[d]),
-                                        A.ptr(beam), n, S, det, det, H, W, st),
-                "multislice cgrad: conj(patch) x wave")
-            check(lib.tike_fft2_pass1(A.ptr(beam), A.ptr(far), n * S, det, 0,
-                                      st),
-                  "multislice cgrad: step back, pass 1")
-        if acc is not None:
-            check(
-                lib.tike_scatter_patches(A.ptr(objproj), A.ptr(sc),
-                                         A.ptr(acc[d]), n, det, H, W, st),
-                "multislice cgrad: object gradient of a slice")
-        check(
-            lib.tike_fresnel_colpass(A.ptr(far), A.ptr(prop), 1, A.ptr(mid),
-                                     n * S, det, fwd_scale, st),
-            "multislice cgrad: adjoint Fresnel step, column passes")
-    check(
-        lib.tike_ifft2_pass2_products(
-            A.ptr(mid), A.ptr(psi[0]), A.ptr(sc), A.ptr(probe), 0,
-            A.ptr(objproj), A.ptr(pacc), 1.0, None, 0, n, S, det, H, W,
-            inv_scale, st),
-        "multislice cgrad: first slice, inverse pass 2 + both products")
-    if acc is not None:
-        check(
-            lib.tike_scatter_patches(A.ptr(objproj), A.ptr(sc), A.ptr(acc[0]),
-                                     n, det, H, W, st),
-            "multislice cgrad: object gradient of the first slice")
+    # (no object gradient wanted: the one launch forms no projection)
+    inv_scale = fft_scales(det, op.norm)[1]
+    M.fused_step_back(op, psi, sc, probe, far, mid, beams[:, :n],
+                      objproj[:, :n], acc, pacc, first_scale=inv_scale,
+                      scale=inv_scale, want_proj=acc is not None,
+                      one_launch=MULTISLICE_STEP_BACK_FUSED,
+                      label="multislice cgrad")
 
 
 def _multislice_chunk_general(op, psi, sc, probe, d32, costs, cm, want_grad,
@@ -914,12 +873,7 @@ def _multislice_chunk_general(op, psi, sc, probe, d32, costs, cm, want_grad,
     D = psi.shape[0]
     n, S, det = sc.shape[0], probe.shape[-3], op.detector_shape
     conv, fresnel = op.diffraction.diffraction, op.diffraction.propagation
-    beams = [probe[0]]  # (1, S, pw, pw), then (n, S, pw, pw)
-    for d in range(D):
-        wave = conv.fwd(psi=psi[d], scan=sc, probe=beams[d])
-        if d + 1 < D:
-            beams.append(fresnel.fwd(wave, overwrite=True))
-    far = op.propagation.fwd(wave, overwrite=True)
+    far, beams = M.general_far(op, psi, sc, probe)
     check(
         lib.tike_farplane_gradient(A.ptr(far), A.ptr(d32), A.ptr(cm.mask),
                                    None, A.ptr(costs), n, S, det, cm.model,
@@ -947,12 +901,9 @@ def _multislice_chunk(op, psi, probe):
     mid + D - 1 sets of incident probes within HALF the HBM that is free right
     now, as rpie's fused multislice chunks are sized (asked once per
     minibatch: every evaluation of its line searches then splits alike)."""
-    S, pw, det = probe.shape[-3], probe.shape[-1], op.detector_shape
-    if (L.CHUNK_POSITIONS_OVERRIDE
-            or not (MULTISLICE_FUSED and fused_slices(pw, det, S))):
-        return chunk_positions(S, det)
-    return chunk_within_hbm(_workspace(op), psi.device, psi.shape[0] + 1, S,
-                            det)
+    return M.chunk_positions(
+        op, psi.device, probe.shape[-3], psi.shape[0] + 1,
+        M.fused_route(op, probe, MULTISLICE_FUSED))
 
 
 def _multislice_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, *,
@@ -965,22 +916,15 @@ def _multislice_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, *,
     positions each; None: `_multislice_chunk`); a line-search probe (want_grad
     False) stops behind the cost."""
     op.diffraction._check_slices(psi)
-    dev, D = psi.device, psi.shape[0]
-    S, pw, det = probe.shape[-3], probe.shape[-1], op.detector_shape
+    dev, D, S = psi.device, psi.shape[0], probe.shape[-3]
     N = hi - lo
     ws = _workspace(op)
-    fused = MULTISLICE_FUSED and fused_slices(pw, det, S)
+    fused = M.fused_route(op, probe, MULTISLICE_FUSED)
     want_psi, want_probe = want_grad and want_psi, want_grad and want_probe
     if chunk is None:
         chunk = _multislice_chunk(op, psi, probe)
     if fused:
-        nmax = max(1, min(chunk, N))
-        bufs = (ws.get("ms_far", (nmax, S, det, det), torch.complex64, dev),
-                ws.get("ms_mid", (1, nmax, S, det, det), torch.complex64,
-                       dev)[0],
-                ws.get("ms_beams", (max(D - 1, 1), nmax, S, pw, pw),
-                       torch.complex64, dev),
-                ws.get("ms_objproj", (nmax, pw, pw), torch.complex64, dev))
+        bufs = M.fused_buffers(op, dev, D, S, max(1, min(chunk, N)))
     costs = ws.get("costs", (max(N, 1),), torch.float32, dev)[:N]
     # (fused: the planar accumulators of the grouped scatter)
     grads, gpsi, gprobe = _gradient_buffer(

@@ -42,12 +42,14 @@ from ... import linalg
 from ... import opt
 from ... import random as trandom
 from ..._lib import check, lib
-from ...operators.multislice import (chunk_within_hbm, fused_forward,
-                                     fused_slices, next_incident_probe)
+from ...operators.multislice import (fused_forward, fused_slices,
+                                     next_incident_probe)
 from ...operators.propagation import fft_scales
 from ..position import check_allowed_positions
 from ..probe import get_varying_probe
+from . import _multislice as M
 from . import lstsq as L
+from ._plan import stored_farplane_gradient
 
 logger = logging.getLogger(__name__)
 
@@ -345,15 +347,11 @@ def _gradients_multislice_fused(data, psi, scan, probe, eigen_probe,
     # Measured (c3rpie2, same box): 64 / 128 / 256 / 512 / 1000 positions per
     # chunk -> 45.2 / 47.4 / 49.5 / 51.2 / 52.4 k patterns/s: these stages
     # hand nothing over through the Infinity Cache, longer launches win.
-    chunk = (L.chunk_positions(S, det) if L.CHUNK_POSITIONS_OVERRIDE else
-             chunk_within_hbm(ws, dev, 2 * D, S, det))
+    chunk = M.chunk_positions(op, dev, S, 2 * D)
     nmax = max(1, min(chunk, B))
-    far = ws.get("ms_far", (nmax, S, det, det), torch.complex64, dev)
     nback = D if step_back_in_frequency else 1
-    mids = ws.get("ms_mid", (nback, nmax, S, det, det), torch.complex64, dev)
-    beams = ws.get("ms_beams", (max(D - 1, 1), nmax, S, pw, pw),
-                   torch.complex64, dev)
-    objproj = ws.get("ms_objproj", (nmax, pw, pw), torch.complex64, dev)
+    far, mids, beams, objproj = M.fused_buffers(op, dev, D, S, nmax, nback)
+    objproj = objproj[0]
     acc = torch.zeros((D, 2, H, W), dtype=torch.float32, device=dev)
     pacc = torch.zeros((D, S, pw, pw), dtype=torch.complex64, device=dev)
     prop = op.diffraction.propagation._propagator((pw, pw), dev)
@@ -471,6 +469,16 @@ def _gradients_multislice_fused(data, psi, scan, probe, eigen_probe,
     return costs[:B], chi0[:B], None if patches0 is None else patches0[:B]
 
 
+def _poisson_rule(exitwave_options):
+    """`rule` of `stored_farplane_gradient`: the step-length options of the
+    Poisson model, None under the gaussian model."""
+    if exitwave_options.noise_model != "poisson":
+        return None
+    return (float(exitwave_options.step_length_start),
+            float(exitwave_options.step_length_weight),
+            int(exitwave_options.step_length_usemodes == "dominant_mode"))
+
+
 def _stored_farplane_gradient(far, mid, data, lo, hi, mask_u8, costs,
                               fwd_scale, unmeasured, nmeasured,
                               exitwave_options):
@@ -481,32 +489,13 @@ def _stored_farplane_gradient(far, mid, data, lo, hi, mask_u8, costs,
     transform."""
     n, S, det = far.shape[0], far.shape[1], far.shape[-1]
     st = A.stream_ptr()
-    poisson = exitwave_options.noise_model == "poisson"
     dchunk = A.data_f32(data, lo, hi)
     check(lib.tike_fft2_pass2_inplace(A.ptr(far), n * S, det, 0, fwd_scale, st),
           "last slice: far field")
-    if poisson:
-        inten = torch.empty((n, det, det), dtype=torch.float32,
-                            device=far.device)
-        steps = torch.empty((n, S), dtype=torch.float32, device=far.device)
-        check(lib.tike_intensity(A.ptr(far), A.ptr(inten), n, S, det * det,
-                                 st), "intensity")
-        check(
-            lib.tike_poisson_steps(
-                A.ptr(far), A.ptr(inten), A.ptr(dchunk), A.ptr(mask_u8),
-                A.ptr(steps), n, S, det,
-                float(exitwave_options.step_length_start),
-                float(exitwave_options.step_length_weight),
-                int(exitwave_options.step_length_usemodes == "dominant_mode"),
-                st), "poisson step lengths")
-    check(
-        lib.tike_farplane_gradient(
-            A.ptr(far), A.ptr(dchunk), A.ptr(mask_u8), None, A.ptr(costs), n,
-            S, det, L._MODELS[exitwave_options.noise_model], 1, unmeasured,
-            nmeasured, st), "farplane gradient")
-    if poisson:
-        check(lib.tike_scale_modes(A.ptr(far), A.ptr(steps), A.ptr(mask_u8),
-                                   n * S, det, st), "poisson step scaling")
+    stored_farplane_gradient(
+        far, dchunk, mask_u8, costs, n, S, det,
+        L._MODELS[exitwave_options.noise_model], unmeasured, nmeasured, st,
+        _poisson_rule(exitwave_options))
     check(lib.tike_fft2_pass1(A.ptr(far), A.ptr(mid), n * S, det, 1, st),
           "last slice: inverse pass 1")
 
@@ -531,7 +520,7 @@ def _gradients_multislice(data, psi, scan, probe, eigen_probe, eigen_weights,
     _, inv_scale = fft_scales(det, op.norm)
     nmeasured, mask_u8 = L.mask_info(exitwave_options, det)
     model = L._MODELS[exitwave_options.noise_model]
-    poisson = exitwave_options.noise_model == "poisson"
+    rule, inten, steps = _poisson_rule(exitwave_options), None, None
     unmeasured = float(exitwave_options.unmeasured_pixels_scaling)
     costs = torch.empty(max(B, 1), dtype=torch.float32, device=dev)
     chi0 = torch.empty((max(B, 1), pw, pw), dtype=torch.complex64, device=dev)
@@ -551,29 +540,13 @@ def _gradients_multislice(data, psi, scan, probe, eigen_probe, eigen_weights,
                                                         psi=psi)
         far = far.contiguous()
         dchunk = A.data_f32(data, clo, chi_hi)
-        if poisson:
+        if rule:  # (a chunk's pair lives until the next chunk's is made)
             inten = torch.empty((n, det, det), dtype=torch.float32,
                                 device=dev)
             steps = torch.empty((n, S), dtype=torch.float32, device=dev)
-            check(lib.tike_intensity(A.ptr(far), A.ptr(inten), n, S,
-                                     det * det, st), "intensity")
-            check(
-                lib.tike_poisson_steps(
-                    A.ptr(far), A.ptr(inten), A.ptr(dchunk),
-                    A.ptr(mask_u8), A.ptr(steps), n, S, det,
-                    float(exitwave_options.step_length_start),
-                    float(exitwave_options.step_length_weight),
-                    int(exitwave_options.step_length_usemodes ==
-                        "dominant_mode"), st), "poisson step lengths")
-        check(
-            lib.tike_farplane_gradient(
-                A.ptr(far), A.ptr(dchunk), A.ptr(mask_u8), None,
-                A.ptr(costs[blo:blo + n]), n, S, det, model, 1, unmeasured,
-                nmeasured, st), "farplane gradient")
-        if poisson:
-            check(lib.tike_scale_modes(A.ptr(far), A.ptr(steps),
-                                       A.ptr(mask_u8), n * S, det, st),
-                  "poisson step scaling")
+        stored_farplane_gradient(far, dchunk, mask_u8, costs[blo:blo + n], n,
+                                 S, det, model, unmeasured, nmeasured, st,
+                                 rule, inten, steps)
         # diff = propagation.adj(farplane)[..., pad:end, pad:end]; a
         # multislice object has pad = 0
         diff = op.propagation.adj(far, overwrite=True)[:, 0].contiguous()

@@ -71,7 +71,6 @@ def legs(det, S, D, frames, fly, repeats, warm):
                     probe_wavelength=WAVELENGTH,
                     probe_FOV_lengths=(det * PIXEL, det * PIXEL),
                     multislice_propagation_distance=DISTANCE) as op:
-        row["fused_route"] = autograd._fused_route(op, probe)
 
         def forward():
             with torch.no_grad():
@@ -109,9 +108,10 @@ def legs(det, S, D, frames, fly, repeats, warm):
         row["gauss_newton_product_ms"] = timed(
             lambda: autograd.multislice_gauss_newton_product(
                 op, psi, probe, scan, fly=fly, **tangents), repeats, warm)
-        chunk = autograd._slices_chunk(op, psi, probe, fly,
-                                       row["fused_route"], extra=1)
-        n = row["chunk_positions"] = min(chunk, N)
+        # the route and the chunk of the model (ptycho/solvers/_multislice.py)
+        route = autograd._SlicesForward(op, fly, psi, probe, scan, extra=1)
+        row["fused_route"] = route.fused
+        n = row["chunk_positions"] = min(route.chunk, N)
         # ------------------------------------- the launches on one chunk
         st = A.stream_ptr()
         P, Q, Sc = psi.detach(), probe.detach(), scan.detach()[:n]

@@ -126,7 +126,6 @@ def legs(det, S, D, frames, fly, repeats, warm, with_cgrad):
                             for x in (p.psi, p.probe, p.scan))
         g = torch.randn((frames, det, det), device=dev)
         f = autograd.multislice_intensity
-        row["fused_route"] = autograd._fused_route(op, probe)
 
         def forward():
             with torch.no_grad():
@@ -144,9 +143,11 @@ def legs(det, S, D, frames, fly, repeats, warm, with_cgrad):
          row["forward_backward_two_launch_table_ms"]) = timed_alternating(
              [both, lambda: both(False)], repeats, warm)
         row["pass1_takes_table"] = bool(autograd.PASS1_TAKES_TABLE)
-        chunk = autograd._slices_chunk(op, psi, probe, fly,
-                                       row["fused_route"])
-        row["chunk_positions"] = min(chunk, N)
+        # the route and the chunk of the model (ptycho/solvers/_multislice.py)
+        route = autograd._SlicesForward(op, fly, psi.detach(), probe.detach(),
+                                        scan.detach())
+        row["fused_route"] = route.fused
+        row["chunk_positions"] = min(route.chunk, N)
         if with_cgrad:
             cm = C._cost_model(p.exitwave_options, det)
             one = lambda: C._multislice_cost_and_grad(  # noqa: E731
