@@ -16,14 +16,10 @@
 // footprints of neighbouring positions overlap), 8 bytes written;
 // tike_scan_gradient_slices reads that much per slice and writes 8 bytes.
 #include "../../include/tike_amd.h"
-#include "common.h"
+#include "frame_lanes.h"
+#include "patch_taps.h"
 
 namespace {
-
-// 16-byte accesses whose ADDRESS is only as aligned as an element (a plane
-// starts at a multiple of npix elements): see position_pd.hip.
-typedef float ag_f4 __attribute__((ext_vector_type(4), aligned(8)));  // two cf
-typedef float ag_t4 __attribute__((ext_vector_type(4), aligned(4)));  // four factors
 
 constexpr int AG_PX = 4;  // pixels of a lane: two 16-byte far-plane accesses per plane
 
@@ -42,17 +38,17 @@ __global__ __launch_bounds__(256) void farplane_scale_kernel(cf* __restrict__ fa
   const long nvec = npix / AG_PX;
   if (v < nvec) {
     const long p = v * AG_PX;
-    ag_t4 t = *reinterpret_cast<const ag_t4*>(T + p);
+    tk_f4a4 t = *reinterpret_cast<const tk_f4a4*>(T + p);
     t *= scale;
 #pragma unroll 4
     for (int j = 0; j < P; ++j) {
       cf* at = F + j * npix + p;
-      ag_f4 a = *reinterpret_cast<const ag_f4*>(at);
-      ag_f4 b = *reinterpret_cast<const ag_f4*>(at + 2);
+      tk_f4a8 a = *reinterpret_cast<const tk_f4a8*>(at);
+      tk_f4a8 b = *reinterpret_cast<const tk_f4a8*>(at + 2);
       a.x *= t.x, a.y *= t.x, a.z *= t.y, a.w *= t.y;
       b.x *= t.z, b.y *= t.z, b.z *= t.w, b.w *= t.w;
-      *reinterpret_cast<ag_f4*>(at) = a;
-      *reinterpret_cast<ag_f4*>(at + 2) = b;
+      *reinterpret_cast<tk_f4a8*>(at) = a;
+      *reinterpret_cast<tk_f4a8*>(at + 2) = b;
     }
     return;
   }
@@ -63,32 +59,29 @@ __global__ __launch_bounds__(256) void farplane_scale_kernel(cf* __restrict__ fa
   for (int j = 0; j < P; ++j) F[j * npix + p] = F[j * npix + p] * t;
 }
 
-__device__ __forceinline__ double ag_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ cf ag_lane_up(cf v) {  // lane i receives lane i + 1
-  return mk(__shfl_down(v.x, 1, 64), __shfl_down(v.y, 1, 64));
-}
-
-constexpr int AG_COLS = 63;  // patch columns of a wave: lane 63 is the halo column
+constexpr int AG_COLS = 63;  // patch columns of a wave: lane 63 is the halo lane
 constexpr int AG_ROWS = 8;   // patch rows of a strip
 
-// One workgroup per position.  The patch is cut into items of AG_ROWS rows x
-// AG_COLS columns, dealt to the four waves in turn.  A lane owns one OBJECT
-// column of its item and walks down the strip: AG_ROWS + 1 object rows, each
-// loaded once -- row y + 1 of pixel row y is row y of pixel row y + 1, and a
-// row serves Dy and Dx alike -- and the tap to the right comes from the next
-// lane by wave shuffle (lane 63 only feeds lane 62).  With the taps
-//   O00 = psi[sy + y][sx + x], O01 the pixel to its right, O10 the pixel below,
-//   O11 below right, and the weights of tk_corner,
-//   Dy = (1 - fx)(O10 - O00) + fx (O11 - O01)      d patch / d scan[n][0]
-//   Dx = (1 - fy)(O01 - O00) + fy (O11 - O10)      d patch / d scan[n][1]
-// (the integer part of the position held fixed).  Every load is unconditional
-// (clamped address, value selected): a tap outside the object counts as zero
-// and nothing outside the arrays is touched, whatever the positions.
+// The lanes' float64 sums of a position into out[0 ... 1], in a fixed order: wave
+// shuffles, then the four waves through LDS.
+__device__ __forceinline__ void ag_store_sums(double gy, double gx, int wave, int lane,
+                                              double (&red)[4][2], float* out) {
+  gy = tk_wave_sum(gy);
+  gx = tk_wave_sum(gx);
+  if (lane == 0) {
+    red[wave][0] = gy;
+    red[wave][1] = gx;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const int i = threadIdx.x;
+    out[i] = (float)((red[0][i] + red[1][i]) + (red[2][i] + red[3][i]));
+  }
+}
+
+// One workgroup per position.  The halo-LANE scheme of patch_taps.h over the
+// (pw, pw) patch, its items dealt to the four waves in turn; a row of a strip
+// serves Dy and Dx alike.
 //
 // The products are float32; the sums are float64 in a fixed order (lane, wave
 // shuffles, the four waves through LDS).  The terms cancel over the patch down
@@ -134,16 +127,16 @@ __global__ __launch_bounds__(256) void scan_gradient_kernel(const cf* __restrict
       const int yq = y0 + j < pw ? y0 + j : pw - 1;
       qq[j] = tk_ld_stream(q + (long)yq * pw + xq);
     }
-    cf right = ag_lane_up(o[0]);
+    cf right = tk_cf_lane_up(o[0]);
 #pragma unroll
     for (int j = 0; j < AG_ROWS; ++j) {
       const cf o00 = o[j], o01 = right, o10 = o[j + 1];
-      const cf o11 = ag_lane_up(o10);
+      const cf o11 = tk_cf_lane_up(o10);
       right = o11;
-      const float dyr = (1.0f - fx) * (o10.x - o00.x) + fx * (o11.x - o01.x);
-      const float dyi = (1.0f - fx) * (o10.y - o00.y) + fx * (o11.y - o01.y);
-      const float dxr = (1.0f - fy) * (o01.x - o00.x) + fy * (o11.x - o10.x);
-      const float dxi = (1.0f - fy) * (o01.y - o00.y) + fy * (o11.y - o10.y);
+      const float dyr = tk_slope(fx, o00.x, o10.x, o01.x, o11.x);
+      const float dyi = tk_slope(fx, o00.y, o10.y, o01.y, o11.y);
+      const float dxr = tk_slope(fy, o00.x, o01.x, o10.x, o11.x);
+      const float dxi = tk_slope(fy, o00.y, o01.y, o10.y, o11.y);
       const float ty = dyr * qq[j].x + dyi * qq[j].y;  // Re(Dy conj(objproj))
       const float tx = dxr * qq[j].x + dxi * qq[j].y;
       const bool live = pixel && y0 + j < pw;
@@ -151,28 +144,17 @@ __global__ __launch_bounds__(256) void scan_gradient_kernel(const cf* __restrict
       gx += live ? (double)tx : 0.;
     }
   }
-  gy = ag_wave_sum(gy);
-  gx = ag_wave_sum(gx);
-  if (lane == 0) {
-    red[wave][0] = gy;
-    red[wave][1] = gx;
-  }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    const int i = threadIdx.x;
-    grad[2 * n + i] = (float)((red[0][i] + red[1][i]) + (red[2][i] + red[3][i]));
-  }
+  ag_store_sums(gy, gx, wave, lane, red, grad + 2 * n);
 }
 
 // The same sum over the D slices of a multislice object, slice d with its own
 // objproj plane (`slice_stride` elements apart) and its own object (H, W): one
-// workgroup per position walks the slices OUTERMOST with the item / strip /
-// halo-lane scheme of scan_gradient_kernel, every lane keeping ONE float64
-// running sum per coordinate over all slices and pixels, reduced once at the
-// end -- so D == 1 gives the bits of scan_gradient_kernel, and there is no
-// float32 rounding between two slices.  Loads as there: unconditional, clamped
-// address, selected value.  All offsets are `long`: d * slice_stride +
-// n * pw * pw passes 2^31.
+// workgroup per position walks the slices OUTERMOST with the items of
+// scan_gradient_kernel, every lane keeping ONE float64 running sum per
+// coordinate over all slices and pixels, reduced once at the end -- so D == 1
+// gives the bits of scan_gradient_kernel, and there is no float32 rounding
+// between two slices.  All offsets are `long`: d * slice_stride + n * pw * pw
+// passes 2^31.
 __global__ __launch_bounds__(256) void scan_gradient_slices_kernel(
     const cf* __restrict__ objproj, long slice_stride, const float* __restrict__ scan,
     const cf* __restrict__ psi, float* __restrict__ grad, int D, int pw, int H, int W) {
@@ -195,7 +177,7 @@ __global__ __launch_bounds__(256) void scan_gradient_slices_kernel(
       const int y0 = (item / nseg) * AG_ROWS;
       const long X = sx + x;
       const bool okx = X >= 0 && X < W;
-      const long Xc = X < 0 ? 0 : (X < W ? X : W - 1);
+        const long Xc = X < 0 ? 0 : (X < W ? X : W - 1);
       const bool pixel = lane < AG_COLS && x < pw;
       const int xq = x < pw ? x : pw - 1;
       cf o[AG_ROWS + 1], qq[AG_ROWS];
@@ -212,16 +194,16 @@ __global__ __launch_bounds__(256) void scan_gradient_slices_kernel(
         const int yq = y0 + j < pw ? y0 + j : pw - 1;
         qq[j] = tk_ld_stream(q + (long)yq * pw + xq);
       }
-      cf right = ag_lane_up(o[0]);
+      cf right = tk_cf_lane_up(o[0]);
 #pragma unroll
       for (int j = 0; j < AG_ROWS; ++j) {
         const cf o00 = o[j], o01 = right, o10 = o[j + 1];
-        const cf o11 = ag_lane_up(o10);
+        const cf o11 = tk_cf_lane_up(o10);
         right = o11;
-        const float dyr = (1.0f - fx) * (o10.x - o00.x) + fx * (o11.x - o01.x);
-        const float dyi = (1.0f - fx) * (o10.y - o00.y) + fx * (o11.y - o01.y);
-        const float dxr = (1.0f - fy) * (o01.x - o00.x) + fy * (o11.x - o10.x);
-        const float dxi = (1.0f - fy) * (o01.y - o00.y) + fy * (o11.y - o10.y);
+        const float dyr = tk_slope(fx, o00.x, o10.x, o01.x, o11.x);
+        const float dyi = tk_slope(fx, o00.y, o10.y, o01.y, o11.y);
+        const float dxr = tk_slope(fy, o00.x, o01.x, o10.x, o11.x);
+        const float dxi = tk_slope(fy, o00.y, o01.y, o10.y, o11.y);
         const float ty = dyr * qq[j].x + dyi * qq[j].y;  // Re(Dy conj(objproj))
         const float tx = dxr * qq[j].x + dxi * qq[j].y;
         const bool live = pixel && y0 + j < pw;
@@ -230,17 +212,7 @@ __global__ __launch_bounds__(256) void scan_gradient_slices_kernel(
       }
     }
   }
-  gy = ag_wave_sum(gy);
-  gx = ag_wave_sum(gx);
-  if (lane == 0) {
-    red[wave][0] = gy;
-    red[wave][1] = gx;
-  }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    const int i = threadIdx.x;
-    grad[2 * n + i] = (float)((red[0][i] + red[1][i]) + (red[2][i] + red[3][i]));
-  }
+  ag_store_sums(gy, gx, wave, lane, red, grad + 2 * n);
 }
 
 }  // namespace

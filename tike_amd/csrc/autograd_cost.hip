@@ -21,42 +21,14 @@
 // counts, npix bytes of mask when there is one, npix * 4 bytes of table
 // written; 4 or 8 bytes of costs.  Nothing is read twice.
 #include "../../include/tike_amd.h"
-#include "common.h"
+#include "frame_lanes.h"
 #include "noise_model.h"
 
 #include <cmath>
 
 namespace {
 
-// 16-byte accesses whose ADDRESS is only as aligned as an element (a plane
-// starts at a multiple of npix elements): see fly.hip.
-typedef float ct_f4 __attribute__((ext_vector_type(4), aligned(8)));  // two cf
-typedef float ct_d4 __attribute__((ext_vector_type(4), aligned(4)));  // four floats
-typedef unsigned short ct_h4 __attribute__((ext_vector_type(4), aligned(2)));
-typedef unsigned char ct_m4 __attribute__((ext_vector_type(4), aligned(1)));
-
 constexpr int CT_PX = 4;  // pixels of a lane per sweep: two 16-byte far-plane loads
-
-// The counts and the mask of the CT_PX pixels at p; d stays 0 without counts.
-template <bool U16>
-__device__ __forceinline__ void ct_counts(const void* __restrict__ data, long p, float d[CT_PX]) {
-  if (U16) {
-    const ct_h4 c = *reinterpret_cast<const ct_h4*>((const unsigned short*)data + p);
-#pragma unroll
-    for (int k = 0; k < CT_PX; ++k) d[k] = (float)c[k];
-  } else {
-    const ct_d4 c = *reinterpret_cast<const ct_d4*>((const float*)data + p);
-#pragma unroll
-    for (int k = 0; k < CT_PX; ++k) d[k] = c[k];
-  }
-}
-
-__device__ __forceinline__ void ct_mask(const unsigned char* __restrict__ mask, long p,
-                                        bool measured[CT_PX]) {
-  const ct_m4 m = *reinterpret_cast<const ct_m4*>(mask + p);
-#pragma unroll
-  for (int k = 0; k < CT_PX; ++k) measured[k] = m[k] != 0;
-}
 
 // The layout of fly_farplane_gradient_kernel without its scaling: one
 // workgroup per frame, a lane owns CT_PX consecutive pixels per sweep and walks
@@ -91,21 +63,21 @@ __global__ __launch_bounds__(256) void cost_factor_kernel(
     const long p = v * PX;
     // the counts and the mask are requested with the planes, not behind them
     float d[PX];
-    ct_counts<U16>(data, p, d);
+    tk_counts4<U16>(data, p, d);
     bool measured[PX] = {true, true, true, true};
-    if (mask != nullptr) ct_mask(mask, p, measured);
+    if (mask != nullptr) tk_mask4(mask, p, measured);
     float I[PX] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
     for (int j = 0; j < P; ++j) {
       const cf* at = F + j * npix + p;
-      const ct_f4 a = *reinterpret_cast<const ct_f4*>(at);
-      const ct_f4 b = *reinterpret_cast<const ct_f4*>(at + 2);
+      const tk_f4a8 a = *reinterpret_cast<const tk_f4a8*>(at);
+      const tk_f4a8 b = *reinterpret_cast<const tk_f4a8*>(at + 2);
       I[0] += a.x * a.x + a.y * a.y;
       I[1] += a.z * a.z + a.w * a.w;
       I[2] += b.x * b.x + b.y * b.y;
       I[3] += b.z * b.z + b.w * b.w;
     }
-    ct_d4 o;
+    tk_f4a4 o;
 #pragma unroll
     for (int k = 0; k < PX; ++k) {
       float term;
@@ -113,7 +85,7 @@ __global__ __launch_bounds__(256) void cost_factor_kernel(
       cost += measured[k] ? (double)term : 0.0;
       o[k] = measured[k] ? up * lp : 0.0f;
     }
-    if (T != nullptr) *reinterpret_cast<ct_d4*>(T + p) = o;
+    if (T != nullptr) *reinterpret_cast<tk_f4a4*>(T + p) = o;
   }
   // scalar tail: fewer than CT_PX pixels, one per lane
   for (long p = nvec * PX + threadIdx.x; p < npix; p += blockDim.x) {
@@ -166,19 +138,19 @@ __global__ __launch_bounds__(256) void cost_curvature_kernel(
     const long p = v * PX;
     // the counts and the mask are requested with the planes, not behind them
     float d[PX] = {0.f, 0.f, 0.f, 0.f};
-    if (counts) ct_counts<U16>(data, p, d);
+    if (counts) tk_counts4<U16>(data, p, d);
     bool measured[PX] = {true, true, true, true};
-    if (mask != nullptr) ct_mask(mask, p, measured);
+    if (mask != nullptr) tk_mask4(mask, p, measured);
     float I[PX] = {0.f, 0.f, 0.f, 0.f};
     float G[PX] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
     for (int j = 0; j < P; ++j) {
       const cf* at = F + j * npix + p;
       const cf* dt = D + j * npix + p;
-      const ct_f4 a = *reinterpret_cast<const ct_f4*>(at);
-      const ct_f4 b = *reinterpret_cast<const ct_f4*>(at + 2);
-      const ct_f4 da = *reinterpret_cast<const ct_f4*>(dt);
-      const ct_f4 db = *reinterpret_cast<const ct_f4*>(dt + 2);
+      const tk_f4a8 a = *reinterpret_cast<const tk_f4a8*>(at);
+      const tk_f4a8 b = *reinterpret_cast<const tk_f4a8*>(at + 2);
+      const tk_f4a8 da = *reinterpret_cast<const tk_f4a8*>(dt);
+      const tk_f4a8 db = *reinterpret_cast<const tk_f4a8*>(dt + 2);
       I[0] += a.x * a.x + a.y * a.y;
       I[1] += a.z * a.z + a.w * a.w;
       I[2] += b.x * b.x + b.y * b.y;
@@ -188,7 +160,7 @@ __global__ __launch_bounds__(256) void cost_curvature_kernel(
       G[2] += b.x * db.x + b.y * db.y;
       G[3] += b.z * db.z + b.w * db.w;
     }
-    ct_d4 o;
+    tk_f4a4 o;
 #pragma unroll
     for (int k = 0; k < PX; ++k) {
       const float dI = 2.0f * G[k];
@@ -200,7 +172,7 @@ __global__ __launch_bounds__(256) void cost_curvature_kernel(
       }
       o[k] = measured[k] ? (up / (I[k] + floor_)) * dI : 0.0f;
     }
-    if (T != nullptr) *reinterpret_cast<ct_d4*>(T + p) = o;
+    if (T != nullptr) *reinterpret_cast<tk_f4a4*>(T + p) = o;
   }
   // scalar tail: fewer than CT_PX pixels, one per lane
   for (long p = nvec * PX + threadIdx.x; p < npix; p += blockDim.x) {

@@ -31,12 +31,6 @@ constexpr int EG_MAX_MODES = 16;   // S
 constexpr int EG_MAX_PLANES = 16;  // C * M
 constexpr int EG_BATCH = 8;        // positions whose wave sums share a trip through LDS
 
-__device__ __forceinline__ double eg_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // The bilinear gather of tk_gather (common.h) in two halves, so that the taps
 // can be in flight while other work goes on: the same clamped addresses, the
 // same weights -- exactly zero for a tap behind the allocation -- and the same
@@ -319,7 +313,7 @@ __global__ __launch_bounds__(256, SC > 0 ? 3 : 1) void eigen_grad_kernel(
         if constexpr (BUTTERFLY) {
           tt[s] = t;
         } else if (sums) {
-          const double ts = eg_wave_sum((double)t);
+          const double ts = tk_wave_sum((double)t);
           if (lane == 0) red[wave][slot][s] = ts;
         }
       }
@@ -347,7 +341,7 @@ __global__ __launch_bounds__(256, SC > 0 ? 3 : 1) void eigen_grad_kernel(
           if constexpr (BUTTERFLY) {
             tt[SM + j] = t;
           } else if (sums) {
-            const double ts = eg_wave_sum((double)t);
+            const double ts = tk_wave_sum((double)t);
             if (lane == 0) red[wave][slot][S + j] = ts;
           }
         }

@@ -26,7 +26,7 @@
 // and 8 of dscan.  P and dP are never in memory: a per-position P would add
 // two more trips of the size of the writes.
 #include "../../include/tike_amd.h"
-#include "common.h"
+#include "patch_taps.h"
 
 namespace {
 
@@ -35,56 +35,17 @@ constexpr int EW_MAX_PLANES = 16;  // C * M, as tike_eigen_probe_gradients
 constexpr int EW_COLS = 64;        // detector columns of an item: every lane owns one
 constexpr int EW_ROWS = 8;         // detector rows of a strip
 
-__device__ __forceinline__ cf ew_lane_up(cf v) {  // lane i receives lane i + 1
-  return mk(__shfl_down(v.x, 1, 64), __shfl_down(v.y, 1, 64));
-}
-
-// The tap to the right of a lane's own: from the next lane by wave shuffle,
-// in lane 63 from the halo column, whose row j lane j holds.
-__device__ __forceinline__ cf ew_right(cf own, cf halo, int j, int lane) {
-  const cf next = ew_lane_up(own);
-  const cf edge = mk(__shfl(halo.x, j, 64), __shfl(halo.y, j, 64));
-  return lane == EW_COLS - 1 ? edge : next;
-}
-
-// The bilinear patch pixel from its four taps, in the order of tk_gather.
-__device__ __forceinline__ cf ew_bilinear(cf o00, cf o01, cf o10, cf o11, const TkCorner& c) {
-  cf r = mk(o00.x * c.w00, o00.y * c.w00);
-  r.x += o01.x * c.w01;
-  r.y += o01.y * c.w01;
-  r.x += o10.x * c.w10;
-  r.y += o10.y * c.w10;
-  r.x += o11.x * c.w11;
-  r.y += o11.y * c.w11;
-  return r;
-}
-
-// grid (position, group of four items): the (det, det) plane of a position is
-// cut into items of EW_ROWS rows x EW_COLS columns, one per wave, the layout
-// of slice_wave_tangent_kernel (autograd_jvp.hip) laid over the DETECTOR
-// plane: all 64 lanes own a column, so a row segment of an item is 512
-// contiguous bytes that start on a multiple of 512 bytes within the row.  A
-// lane loads the EW_ROWS + 1 object rows of its column once (and those of
-// dpsi when given) -- they serve the patch, Dy, Dx and every mode --; the tap
-// to the right comes from the next lane by wave shuffle, and lane 63 takes it
-// from the halo column, the column behind the item, which ONE more load per
-// lane fetches (lane j its row j, j <= EW_ROWS; the other lanes repeat the
-// last row).  With the taps O00, O01, O10, O11 and the weights of tk_corner,
-//   patch = w00 O00 + w01 O01 + w10 O10 + w11 O11
-//   Dy = (1 - fx)(O10 - O00) + fx (O11 - O01)      d patch / d scan[n][0]
-//   Dx = (1 - fy)(O01 - O00) + fy (O11 - O10)      d patch / d scan[n][1]
-// as tike_scan_gradient has them (the integer part of the position held
-// fixed).  The modes are the outer loop: w[n][:][s] and dw[n][:][s] are
+// grid (position, group of four items): the halo-COLUMN scheme of
+// patch_taps.h laid over the (det, det) DETECTOR plane, one item per wave: all
+// 64 lanes own a column.  The strips of psi and of dpsi serve the patch, Dy, Dx
+// and every mode.  The modes are the outer loop: w[n][:][s] and dw[n][:][s] are
 // uniform in a workgroup (scalar loads), and P and dP of a pixel are built in
 // registers from probe, E, dprobe and dE, which come from cache.  Rows c + 1
 // of w and dw are not read for s >= M.  A NULL tangent is a zero tangent: its
 // loads are skipped (uniform) and its terms are left out or computed on
 // zeros; with all five NULL the plane is written as exactly 0.0 and nothing
-// is loaded.  Every load that is made is unconditional (clamped address,
-// value selected): a tap outside the object counts as zero, a pixel outside
-// the centred pw window is written as exactly 0.0, and nothing outside the
-// arrays is touched, whatever the positions.  An item that lies in the
-// padding altogether only writes its zeros.  Products are float32; every
+// is loaded.  A pixel outside the centred pw window is written as exactly 0.0;
+// an item that lies in the padding altogether only writes its zeros.  Every
 // output element has one owner: no atomics.  All offsets are `long`.
 __global__ __launch_bounds__(256) void eigen_wave_tangent_kernel(
     const cf* __restrict__ psi, const cf* __restrict__ dpsi, const float* __restrict__ scan,
@@ -154,26 +115,22 @@ __global__ __launch_bounds__(256) void eigen_wave_tangent_kernel(
     }
   }
   cf pat[EW_ROWS], dpat[EW_ROWS];
-  cf right = ew_right(o[0], ho, 0, lane);
+  cf right = tk_right_tap<EW_COLS>(o[0], ho, 0, lane);
 #pragma unroll
   for (int j = 0; j < EW_ROWS; ++j) {
     const cf o00 = o[j], o01 = right, o10 = o[j + 1];
-    const cf o11 = ew_right(o10, ho, j + 1, lane);
+    const cf o11 = tk_right_tap<EW_COLS>(o10, ho, j + 1, lane);
     right = o11;
-    const float dyr = (1.0f - fx) * (o10.x - o00.x) + fx * (o11.x - o01.x);
-    const float dyi = (1.0f - fx) * (o10.y - o00.y) + fx * (o11.y - o01.y);
-    const float dxr = (1.0f - fy) * (o01.x - o00.x) + fy * (o11.x - o10.x);
-    const float dxi = (1.0f - fy) * (o01.y - o00.y) + fy * (o11.y - o10.y);
-    pat[j] = ew_bilinear(o00, o01, o10, o11, c);
+    const float dyr = tk_slope(fx, o00.x, o10.x, o01.x, o11.x);
+    const float dyi = tk_slope(fx, o00.y, o10.y, o01.y, o11.y);
+    const float dxr = tk_slope(fy, o00.x, o01.x, o10.x, o11.x);
+    const float dxi = tk_slope(fy, o00.y, o01.y, o10.y, o11.y);
+    pat[j] = tk_bilinear(o00, o01, o10, o11, c);
     cf t = mk(0.f, 0.f);
     if (dpsi != nullptr)  // uniform
-      t = ew_bilinear(d[j], ew_right(d[j], hd, j, lane), d[j + 1],
-                      ew_right(d[j + 1], hd, j + 1, lane), c);
-    t.x += dsy * dyr;
-    t.y += dsy * dyi;
-    t.x += dsx * dxr;
-    t.y += dsx * dxi;
-    dpat[j] = t;
+      t = tk_bilinear(d[j], tk_right_tap<EW_COLS>(d[j], hd, j, lane), d[j + 1],
+                      tk_right_tap<EW_COLS>(d[j + 1], hd, j + 1, lane), c);
+    dpat[j] = tk_patch_tangent(t, dsy, dyr, dyi, dsx, dxr, dxi);
   }
   const bool colin = px >= 0 && px < pw;
   const int pxc = px < 0 ? 0 : (px < pw ? px : pw - 1);
@@ -258,9 +215,8 @@ extern "C" int tike_eigen_wave_tangent(const void* psi, const void* dpsi, const 
   TK_CHECK_ARG(C == 0 || (M >= 1 && M <= S && eigen_probe != nullptr));
   if (nscan == 0) return TK_OK;
   TK_CHECK_ARG(nscan <= 0x7fffffffL);  // one grid column per position: grid.x
-  const long items = (long)((det + EW_COLS - 1) / EW_COLS) * ((det + EW_ROWS - 1) / EW_ROWS);
-  const long groups = (items + 3) / 4;  // one item per wave
-  TK_CHECK_ARG(groups <= (long)tike_max_grid_dim_y());
+  const long groups = tk_item_groups(det, EW_COLS, EW_ROWS);
+  TK_CHECK_ARG(groups > 0);
   if (C == 0) deigen_probe = nullptr;  // no plane it could be the tangent of
   hipLaunchKernelGGL(eigen_wave_tangent_kernel, dim3((unsigned)nscan, (unsigned)groups),
                      dim3(256), 0, stream, (const cf*)psi, (const cf*)dpsi, scan, dscan,

@@ -28,51 +28,23 @@
 // 2 * P * npix * 8 bytes of far plane and tangent read once, npix * 4 bytes of
 // dI written, npix * 4 more with I.
 #include "../../include/tike_amd.h"
-#include "common.h"
+#include "frame_lanes.h"
+#include "patch_taps.h"
 
 namespace {
 
 constexpr int JV_MAX_MODES = 16;  // TK_MAX_MODES of the gradient kernels
-constexpr int JV_COLS = 63;       // detector columns of a wave: lane 63 is the halo column
+constexpr int JV_COLS = 63;       // detector columns of a wave: lane 63 is the halo lane
 constexpr int JV_ROWS = 8;        // detector rows of a strip
 
-__device__ __forceinline__ cf jv_lane_up(cf v) {  // lane i receives lane i + 1
-  return mk(__shfl_down(v.x, 1, 64), __shfl_down(v.y, 1, 64));
-}
-
-// The bilinear patch pixel from its four taps, in the order of tk_gather.
-__device__ __forceinline__ cf jv_bilinear(cf o00, cf o01, cf o10, cf o11, const TkCorner& c) {
-  cf r = mk(o00.x * c.w00, o00.y * c.w00);
-  r.x += o01.x * c.w01;
-  r.y += o01.y * c.w01;
-  r.x += o10.x * c.w10;
-  r.y += o10.y * c.w10;
-  r.x += o11.x * c.w11;
-  r.y += o11.y * c.w11;
-  return r;
-}
-
-// grid (position, group of four items): the (det, det) plane of a position is
-// cut into items of JV_ROWS rows x JV_COLS columns, one per wave, with the
-// strip / halo-lane scheme of scan_gradient_kernel (autograd.hip) laid over
-// the DETECTOR plane: a lane owns one column of its item and walks down the
-// strip, JV_ROWS + 1 object rows of psi (and of dpsi when given), each loaded
-// once -- they serve the patch, Dy, Dx and every mode -- and the tap to the
-// right comes from the next lane by wave shuffle (lane 63 only feeds lane 62
-// and owns no output).  With the taps O00, O01, O10, O11 and the weights of
-// tk_corner,
-//   patch = w00 O00 + w01 O01 + w10 O10 + w11 O11
-//   Dy = (1 - fx)(O10 - O00) + fx (O11 - O01)      d patch / d scan[n][0]
-//   Dx = (1 - fy)(O01 - O00) + fy (O11 - O10)      d patch / d scan[n][1]
-// as tike_scan_gradient has them (the integer part of the position held
-// fixed).  A NULL tangent is a zero tangent: its loads are skipped (uniform)
-// and its terms are computed on zeros.  Every load that is made is
-// unconditional (clamped address, value selected): a tap outside the object
-// counts as zero, a pixel outside the centred pw window is written as exactly
-// 0.0, and nothing outside the arrays is touched, whatever the positions.  An
-// item that lies in the padding altogether only writes its zeros.  Products
-// are float32; every output element has one owner: no atomics.  All offsets
-// are `long`.
+// grid (position, group of four items): the halo-LANE scheme of patch_taps.h
+// laid over the (det, det) DETECTOR plane, one item per wave; lane 63 owns no
+// output.  The strips of psi and of dpsi serve the patch, Dy, Dx and every
+// mode.  A NULL tangent is a zero tangent: its loads are skipped (uniform)
+// and its terms are computed on zeros.  A pixel outside the centred pw window
+// is written as exactly 0.0; an item that lies in the padding altogether only
+// writes its zeros.  Every output element has one owner: no atomics.  All
+// offsets are `long`.
 __global__ __launch_bounds__(256) void conv_fwd_tangent_kernel(
     const cf* __restrict__ psi, const cf* __restrict__ dpsi, const float* __restrict__ scan,
     const float* __restrict__ dscan, const cf* __restrict__ probe, const cf* __restrict__ dprobe,
@@ -124,26 +96,22 @@ __global__ __launch_bounds__(256) void conv_fwd_tangent_kernel(
   const bool colin = px >= 0 && px < pw;
   const int pxc = px < 0 ? 0 : (px < pw ? px : pw - 1);
   cf pat[JV_ROWS], dpat[JV_ROWS];
-  cf right = jv_lane_up(o[0]), dright = jv_lane_up(d[0]);
+  cf right = tk_cf_lane_up(o[0]), dright = tk_cf_lane_up(d[0]);
 #pragma unroll
   for (int j = 0; j < JV_ROWS; ++j) {
     const cf o00 = o[j], o01 = right, o10 = o[j + 1];
-    const cf o11 = jv_lane_up(o10);
+    const cf o11 = tk_cf_lane_up(o10);
     right = o11;
     const cf d00 = d[j], d01 = dright, d10 = d[j + 1];
-    const cf d11 = jv_lane_up(d10);
+    const cf d11 = tk_cf_lane_up(d10);
     dright = d11;
-    const float dyr = (1.0f - fx) * (o10.x - o00.x) + fx * (o11.x - o01.x);
-    const float dyi = (1.0f - fx) * (o10.y - o00.y) + fx * (o11.y - o01.y);
-    const float dxr = (1.0f - fy) * (o01.x - o00.x) + fy * (o11.x - o10.x);
-    const float dxi = (1.0f - fy) * (o01.y - o00.y) + fy * (o11.y - o10.y);
-    pat[j] = jv_bilinear(o00, o01, o10, o11, c);
-    cf t = jv_bilinear(d00, d01, d10, d11, c);
-    t.x += dsy * dyr;
-    t.y += dsy * dyi;
-    t.x += dsx * dxr;
-    t.y += dsx * dxi;
-    dpat[j] = t;
+    const float dyr = tk_slope(fx, o00.x, o10.x, o01.x, o11.x);
+    const float dyi = tk_slope(fx, o00.y, o10.y, o01.y, o11.y);
+    const float dxr = tk_slope(fy, o00.x, o01.x, o10.x, o11.x);
+    const float dxi = tk_slope(fy, o00.y, o01.y, o10.y, o11.y);
+    pat[j] = tk_bilinear(o00, o01, o10, o11, c);
+    cf t = tk_bilinear(d00, d01, d10, d11, c);
+    dpat[j] = tk_patch_tangent(t, dsy, dyr, dyi, dsx, dxr, dxi);
   }
   const long pp = (long)pw * pw;
   for (int s = 0; s < S; ++s) {
@@ -164,30 +132,13 @@ __global__ __launch_bounds__(256) void conv_fwd_tangent_kernel(
 constexpr int SW_COLS = 64;  // columns of an item: every lane owns one
 constexpr int SW_ROWS = 8;   // rows of a strip
 
-// The tap to the right of a lane's own: from the next lane by wave shuffle,
-// in lane 63 from the halo column, whose row j lane j holds.
-__device__ __forceinline__ cf sw_right(cf own, cf halo, int j, int lane) {
-  const cf next = jv_lane_up(own);
-  const cf edge = mk(__shfl(halo.x, j, 64), __shfl(halo.y, j, 64));
-  return lane == SW_COLS - 1 ? edge : next;
-}
-
 // grid (position, group of four items): conv_fwd_tangent_kernel for ONE slice
 // of a multislice object, whose (pw, pw) plane has no padding (probe window =
 // detector), with a beam and a tangent beam that may differ from position to
-// position (stride 0: shared).  The plane is cut into items of SW_ROWS rows x
-// SW_COLS columns, one per wave; all 64 lanes own a column, so a row segment
-// of an item is 512 contiguous bytes that start on a multiple of 512 bytes
-// within the row.  A lane loads the SW_ROWS + 1 object rows of its column once
-// (they serve the patch, Dy, Dx and every mode); the tap to the right comes
-// from the next lane by wave shuffle, and lane 63 takes it from the halo
-// column, the column behind the item, which ONE more load per lane fetches
-// (lane j its row j, j <= SW_ROWS; the other lanes repeat the last row).  The
-// formulas, the float32 products, the unconditional clamped loads with a
-// selected value and the zero tap outside the object are those of
-// conv_fwd_tangent_kernel.  A NULL tangent is a zero tangent whose loads are
-// skipped (uniform); with all three NULL the plane is written as exactly 0.0
-// and nothing is loaded.
+// position (stride 0: shared).  The halo-COLUMN scheme of patch_taps.h, one
+// item per wave: all 64 lanes own a column.  A NULL tangent is a zero tangent
+// whose loads are skipped (uniform); with all three NULL the plane is written
+// as exactly 0.0 and nothing is loaded.
 //
 // dwave may be dbeam itself (stride S * pw * pw): the SW_ROWS elements of a
 // mode that a lane owns are loaded into registers before the first of them is
@@ -258,26 +209,22 @@ __global__ __launch_bounds__(256) void slice_wave_tangent_kernel(
     }
   }
   cf pat[SW_ROWS], dpat[SW_ROWS];
-  cf right = sw_right(o[0], ho, 0, lane);
+  cf right = tk_right_tap<SW_COLS>(o[0], ho, 0, lane);
 #pragma unroll
   for (int j = 0; j < SW_ROWS; ++j) {
     const cf o00 = o[j], o01 = right, o10 = o[j + 1];
-    const cf o11 = sw_right(o10, ho, j + 1, lane);
+    const cf o11 = tk_right_tap<SW_COLS>(o10, ho, j + 1, lane);
     right = o11;
-    const float dyr = (1.0f - fx) * (o10.x - o00.x) + fx * (o11.x - o01.x);
-    const float dyi = (1.0f - fx) * (o10.y - o00.y) + fx * (o11.y - o01.y);
-    const float dxr = (1.0f - fy) * (o01.x - o00.x) + fy * (o11.x - o10.x);
-    const float dxi = (1.0f - fy) * (o01.y - o00.y) + fy * (o11.y - o10.y);
-    pat[j] = jv_bilinear(o00, o01, o10, o11, c);
+    const float dyr = tk_slope(fx, o00.x, o10.x, o01.x, o11.x);
+    const float dyi = tk_slope(fx, o00.y, o10.y, o01.y, o11.y);
+    const float dxr = tk_slope(fy, o00.x, o01.x, o10.x, o11.x);
+    const float dxi = tk_slope(fy, o00.y, o01.y, o10.y, o11.y);
+    pat[j] = tk_bilinear(o00, o01, o10, o11, c);
     cf t = mk(0.f, 0.f);
     if (dpsi != nullptr)  // uniform
-      t = jv_bilinear(d[j], sw_right(d[j], hd, j, lane), d[j + 1],
-                      sw_right(d[j + 1], hd, j + 1, lane), c);
-    t.x += dsy * dyr;
-    t.y += dsy * dyi;
-    t.x += dsx * dxr;
-    t.y += dsx * dxi;
-    dpat[j] = t;
+      t = tk_bilinear(d[j], tk_right_tap<SW_COLS>(d[j], hd, j, lane), d[j + 1],
+                      tk_right_tap<SW_COLS>(d[j + 1], hd, j + 1, lane), c);
+    dpat[j] = tk_patch_tangent(t, dsy, dyr, dyi, dsx, dxr, dxi);
   }
   const cf* __restrict__ bsrc = beam + n * beam_stride;
   const cf* dbsrc = dbeam != nullptr ? dbeam + n * dbeam_stride : nullptr;
@@ -299,11 +246,6 @@ __global__ __launch_bounds__(256) void slice_wave_tangent_kernel(
     }
   }
 }
-
-// 16-byte accesses whose ADDRESS is only as aligned as an element (a plane
-// starts at a multiple of npix elements): see autograd.hip.
-typedef float jv_f4 __attribute__((ext_vector_type(4), aligned(8)));  // two cf
-typedef float jv_t4 __attribute__((ext_vector_type(4), aligned(4)));  // four sums
 
 constexpr int JV_PX = 4;  // pixels of a lane: two 16-byte accesses per plane and far plane
 
@@ -333,10 +275,10 @@ __global__ __launch_bounds__(256) void intensity_tangent_kernel(
     for (int j = 0; j < P; ++j) {
       const cf* at = F + j * npix + p;
       const cf* dt = D + j * npix + p;
-      const jv_f4 a = *reinterpret_cast<const jv_f4*>(at);
-      const jv_f4 b = *reinterpret_cast<const jv_f4*>(at + 2);
-      const jv_f4 da = *reinterpret_cast<const jv_f4*>(dt);
-      const jv_f4 db = *reinterpret_cast<const jv_f4*>(dt + 2);
+      const tk_f4a8 a = *reinterpret_cast<const tk_f4a8*>(at);
+      const tk_f4a8 b = *reinterpret_cast<const tk_f4a8*>(at + 2);
+      const tk_f4a8 da = *reinterpret_cast<const tk_f4a8*>(dt);
+      const tk_f4a8 db = *reinterpret_cast<const tk_f4a8*>(dt + 2);
       I[0] += a.x * a.x + a.y * a.y;
       I[1] += a.z * a.z + a.w * a.w;
       I[2] += b.x * b.x + b.y * b.y;
@@ -346,15 +288,15 @@ __global__ __launch_bounds__(256) void intensity_tangent_kernel(
       T[2] += b.x * db.x + b.y * db.y;
       T[3] += b.z * db.z + b.w * db.w;
     }
-    jv_t4 t;
+    tk_f4a4 t;
 #pragma unroll
     for (int k = 0; k < JV_PX; ++k) t[k] = 2.0f * T[k];
-    *reinterpret_cast<jv_t4*>(dintensity + f * npix + p) = t;
+    *reinterpret_cast<tk_f4a4*>(dintensity + f * npix + p) = t;
     if (intensity != nullptr) {
-      jv_t4 o;
+      tk_f4a4 o;
 #pragma unroll
       for (int k = 0; k < JV_PX; ++k) o[k] = I[k];
-      *reinterpret_cast<jv_t4*>(intensity + f * npix + p) = o;
+      *reinterpret_cast<tk_f4a4*>(intensity + f * npix + p) = o;
     }
     return;
   }
@@ -384,9 +326,8 @@ extern "C" int tike_conv_fwd_tangent(const void* psi, const void* dpsi, const fl
   if (S > JV_MAX_MODES) return TK_ERR_UNSUPPORTED;
   if (nscan == 0) return TK_OK;
   TK_CHECK_ARG(nscan <= 0x7fffffffL);  // one grid column per position: grid.x
-  const long items = (long)((det + JV_COLS - 1) / JV_COLS) * ((det + JV_ROWS - 1) / JV_ROWS);
-  const long groups = (items + 3) / 4;  // one item per wave
-  TK_CHECK_ARG(groups <= (long)tike_max_grid_dim_y());
+  const long groups = tk_item_groups(det, JV_COLS, JV_ROWS);
+  TK_CHECK_ARG(groups > 0);
   hipLaunchKernelGGL(conv_fwd_tangent_kernel, dim3((unsigned)nscan, (unsigned)groups), dim3(256),
                      0, stream, (const cf*)psi, (const cf*)dpsi, scan, dscan, (const cf*)probe,
                      (const cf*)dprobe, (cf*)nearplane, S, pw, det, H, W);
@@ -405,9 +346,8 @@ extern "C" int tike_slice_wave_tangent(const void* psi, const void* dpsi, const 
   if (S > JV_MAX_MODES) return TK_ERR_UNSUPPORTED;
   if (nscan == 0) return TK_OK;
   TK_CHECK_ARG(nscan <= 0x7fffffffL);  // one grid column per position: grid.x
-  const long items = (long)((pw + SW_COLS - 1) / SW_COLS) * ((pw + SW_ROWS - 1) / SW_ROWS);
-  const long groups = (items + 3) / 4;  // one item per wave
-  TK_CHECK_ARG(groups <= (long)tike_max_grid_dim_y());
+  const long groups = tk_item_groups(pw, SW_COLS, SW_ROWS);
+  TK_CHECK_ARG(groups > 0);
   const long set = (long)S * pw * pw;
   hipLaunchKernelGGL(slice_wave_tangent_kernel, dim3((unsigned)nscan, (unsigned)groups),
                      dim3(256), 0, stream, (const cf*)psi, (const cf*)dpsi, scan, dscan,

@@ -79,6 +79,11 @@ __device__ __forceinline__ float tk_wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ double tk_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 
 // Block-wide sum for 256-thread blocks; result valid in every thread.
 // `red` must hold >= 4 floats of LDS; contains barriers.

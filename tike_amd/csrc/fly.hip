@@ -13,17 +13,10 @@
 // far plane read once (and written once with apply_gradient), npix * 4 (or * 2)
 // bytes of counts, npix bytes of mask when there is one.
 #include "../../include/tike_amd.h"
-#include "common.h"
+#include "frame_lanes.h"
 #include "noise_model.h"
 
 namespace {
-
-// 16-byte accesses whose ADDRESS is only as aligned as an element (a plane
-// starts at a multiple of npix elements): see position_pd.hip.
-typedef float fly_f4 __attribute__((ext_vector_type(4), aligned(8)));  // two cf
-typedef float fly_d4 __attribute__((ext_vector_type(4), aligned(4)));  // four counts
-typedef unsigned short fly_h4 __attribute__((ext_vector_type(4), aligned(2)));
-typedef unsigned char fly_m4 __attribute__((ext_vector_type(4), aligned(1)));
 
 constexpr int FLY_PX = 4;  // pixels of a lane per sweep: two 16-byte far-plane loads
 
@@ -68,30 +61,18 @@ __global__ __launch_bounds__(256) void fly_farplane_gradient_kernel(
     const long p = v * PX;
     // the counts and the mask are requested with the planes, not behind them
     float d[PX];
-    if (U16) {
-      const fly_h4 c = *reinterpret_cast<const fly_h4*>(d16 + p);
-#pragma unroll
-      for (int k = 0; k < PX; ++k) d[k] = (float)c[k];
-    } else {
-      const fly_d4 c = *reinterpret_cast<const fly_d4*>(d32 + p);
-#pragma unroll
-      for (int k = 0; k < PX; ++k) d[k] = c[k];
-    }
+    tk_counts4<U16>(U16 ? (const void*)d16 : (const void*)d32, p, d);
     bool measured[PX] = {true, true, true, true};
-    if (mask != nullptr) {
-      const fly_m4 m = *reinterpret_cast<const fly_m4*>(mask + p);
-#pragma unroll
-      for (int k = 0; k < PX; ++k) measured[k] = m[k] != 0;
-    }
+    if (mask != nullptr) tk_mask4(mask, p, measured);
     float I[PX] = {0.f, 0.f, 0.f, 0.f};
-    fly_f4 r[RR][2];
+    tk_f4a8 r[RR][2];
     if (GRAD && R > 0) {
 #pragma unroll
       for (int j = 0; j < RR; ++j) {
         if (j < P) {
           const cf* at = F + j * npix + p;
-          r[j][0] = *reinterpret_cast<const fly_f4*>(at);
-          r[j][1] = *reinterpret_cast<const fly_f4*>(at + 2);
+          r[j][0] = *reinterpret_cast<const tk_f4a8*>(at);
+          r[j][1] = *reinterpret_cast<const tk_f4a8*>(at + 2);
         }
       }
 #pragma unroll
@@ -106,8 +87,8 @@ __global__ __launch_bounds__(256) void fly_farplane_gradient_kernel(
     } else {
       for (int j = 0; j < P; ++j) {
         const cf* at = F + j * npix + p;
-        const fly_f4 a = *reinterpret_cast<const fly_f4*>(at);
-        const fly_f4 b = *reinterpret_cast<const fly_f4*>(at + 2);
+        const tk_f4a8 a = *reinterpret_cast<const tk_f4a8*>(at);
+        const tk_f4a8 b = *reinterpret_cast<const tk_f4a8*>(at + 2);
         I[0] += a.x * a.x + a.y * a.y;
         I[1] += a.z * a.z + a.w * a.w;
         I[2] += b.x * b.x + b.y * b.y;
@@ -118,32 +99,32 @@ __global__ __launch_bounds__(256) void fly_farplane_gradient_kernel(
 #pragma unroll
     for (int k = 0; k < PX; ++k) g[k] = fly_pixel<MODEL>(I[k], d[k], measured[k], ums1, cost);
     if (intensity != nullptr) {
-      fly_d4 o;
+      tk_f4a4 o;
 #pragma unroll
       for (int k = 0; k < PX; ++k) o[k] = I[k];
-      *reinterpret_cast<fly_d4*>(intensity + n * npix + p) = o;
+      *reinterpret_cast<tk_f4a4*>(intensity + n * npix + p) = o;
     }
     if (GRAD && R > 0) {
 #pragma unroll
       for (int j = 0; j < RR; ++j) {
         if (j < P) {
           cf* at = F + j * npix + p;
-          fly_f4 a = r[j][0], b = r[j][1];
+          tk_f4a8 a = r[j][0], b = r[j][1];
           a.x *= g[0], a.y *= g[0], a.z *= g[1], a.w *= g[1];
           b.x *= g[2], b.y *= g[2], b.z *= g[3], b.w *= g[3];
-          *reinterpret_cast<fly_f4*>(at) = a;
-          *reinterpret_cast<fly_f4*>(at + 2) = b;
+          *reinterpret_cast<tk_f4a8*>(at) = a;
+          *reinterpret_cast<tk_f4a8*>(at + 2) = b;
         }
       }
     } else if (GRAD) {
       for (int j = 0; j < P; ++j) {
         cf* at = F + j * npix + p;
-        fly_f4 a = *reinterpret_cast<const fly_f4*>(at);
-        fly_f4 b = *reinterpret_cast<const fly_f4*>(at + 2);
+        tk_f4a8 a = *reinterpret_cast<const tk_f4a8*>(at);
+        tk_f4a8 b = *reinterpret_cast<const tk_f4a8*>(at + 2);
         a.x *= g[0], a.y *= g[0], a.z *= g[1], a.w *= g[1];
         b.x *= g[2], b.y *= g[2], b.z *= g[3], b.w *= g[3];
-        *reinterpret_cast<fly_f4*>(at) = a;
-        *reinterpret_cast<fly_f4*>(at + 2) = b;
+        *reinterpret_cast<tk_f4a8*>(at) = a;
+        *reinterpret_cast<tk_f4a8*>(at + 2) = b;
       }
     }
   }
@@ -159,7 +140,7 @@ __global__ __launch_bounds__(256) void fly_farplane_gradient_kernel(
       for (int j = 0; j < P; ++j) F[j * npix + p] = F[j * npix + p] * g;
   }
   if (costs != nullptr) {
-    cost = tk_wave_sum_f64(cost);
+    cost = tk_wave_sum(cost);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cost;
     __syncthreads();
     if (threadIdx.x == 0)

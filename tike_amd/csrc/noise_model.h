@@ -25,17 +25,11 @@ __device__ __forceinline__ float tk_noise_pixel(float I, float d, float& term) {
   return 1.0f - d / (I + 1e-9f);
 }
 
-__device__ __forceinline__ double tk_wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // The sum of a 256-lane workgroup's per-lane float64 partial sums in thread 0:
 // wave shuffles, then the four waves through `red` (>= 4 doubles of LDS) as
 // (w0 + w1) + (w2 + w3).  Contains a barrier; only thread 0's result counts.
 __device__ __forceinline__ double tk_frame_sum_f64(double v, double* red) {
-  v = tk_wave_sum_f64(v);
+  v = tk_wave_sum(v);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   return (red[0] + red[1]) + (red[2] + red[3]);

@@ -6,17 +6,12 @@
 // Byte model per position: 3 * S * npix * 8 bytes of far plane and npix * 4
 // (or * 2) bytes of pattern are read once; 24 bytes are written.
 #include "../../include/tike_amd.h"
-#include "common.h"
+#include "frame_lanes.h"
 
 namespace {
 
-// 16-byte loads whose ADDRESS is only as aligned as an element: a row starts
-// at (n * S + s) * npix elements, which is a multiple of 16 bytes only when
-// npix is a multiple of the vector width.  gfx950 under HSA serves misaligned
-// global loads; the type tells the compiler not to assume more.
-typedef float pd_f4 __attribute__((ext_vector_type(4), aligned(8)));   // two cf
-typedef float pd_d4 __attribute__((ext_vector_type(4), aligned(4)));   // four counts
-typedef unsigned short pd_h8 __attribute__((ext_vector_type(8), aligned(2)));  // eight counts
+// eight counts in one 16-byte load, element-aligned as the types of frame_lanes.h
+typedef unsigned short pd_h8 __attribute__((ext_vector_type(8), aligned(2)));
 
 // Everything past the loads is float64.  The five sums are not sums of
 // positive terms: a r and b r (and a b) cancel over the pixels down to a small
@@ -52,12 +47,6 @@ __device__ __forceinline__ void pd_mode(double& I, double& a, double& b, float f
   a += (r0 - (double)fyr) * r0 + (i0 - (double)fyi) * i0;
 }
 
-__device__ __forceinline__ double pd_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // One workgroup per position.  A lane owns PX consecutive pixels per sweep
 // (PX * 2 or 4 bytes of pattern = one 16-byte load) and walks the modes with
 // I, a and b of those pixels in registers; the last npix % PX pixels are taken
@@ -86,9 +75,9 @@ __global__ __launch_bounds__(256) void position_pd_sums_kernel(
       const long at = row + s * npix + p;
 #pragma unroll
       for (int h = 0; h < PX / 2; ++h) {
-        const pd_f4 f0 = *reinterpret_cast<const pd_f4*>(far0 + at + 2 * h);
-        const pd_f4 fx = *reinterpret_cast<const pd_f4*>(far_dx + at + 2 * h);
-        const pd_f4 fy = *reinterpret_cast<const pd_f4*>(far_dy + at + 2 * h);
+        const tk_f4a8 f0 = *reinterpret_cast<const tk_f4a8*>(far0 + at + 2 * h);
+        const tk_f4a8 fx = *reinterpret_cast<const tk_f4a8*>(far_dx + at + 2 * h);
+        const tk_f4a8 fy = *reinterpret_cast<const tk_f4a8*>(far_dy + at + 2 * h);
         pd_mode(I[2 * h], a[2 * h], b[2 * h], f0.x, f0.y, fx.x, fx.y, fy.x, fy.y);
         pd_mode(I[2 * h + 1], a[2 * h + 1], b[2 * h + 1], f0.z, f0.w, fx.z, fx.w, fy.z, fy.w);
       }
@@ -99,7 +88,7 @@ __global__ __launch_bounds__(256) void position_pd_sums_kernel(
 #pragma unroll
       for (int j = 0; j < PX; ++j) d[j] = (float)c[j];
     } else {
-      const pd_d4 c = *reinterpret_cast<const pd_d4*>(d32 + p);
+      const tk_f4a4 c = *reinterpret_cast<const tk_f4a4*>(d32 + p);
 #pragma unroll
       for (int j = 0; j < PX; ++j) d[j] = c[j];
     }
@@ -119,7 +108,7 @@ __global__ __launch_bounds__(256) void position_pd_sums_kernel(
   // wave64 shuffles, then the four waves through LDS in a fixed order
   double w[6] = {k.aa, k.ab, k.bb, k.ar, k.br, k.cost};
 #pragma unroll
-  for (int i = 0; i < 6; ++i) w[i] = pd_wave_sum(w[i]);
+  for (int i = 0; i < 6; ++i) w[i] = tk_wave_sum(w[i]);
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
     for (int i = 0; i < 6; ++i) red[threadIdx.x >> 6][i] = w[i];
