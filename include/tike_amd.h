@@ -1475,6 +1475,56 @@ int tike_cost_curvature(const void* farplane, const void* dfarplane, const void*
                         float* costs, float* dcosts, float* table, long nframe, int P,
                         long npix, int model, float floor, long num_measured, void* stream);
 
+/* ==== the difference map (tike_amd/ptycho/solvers/dm.py; Thibault et al.
+ * 2008 / 2009; no reference counterpart): the two ends of its exit-wave step.
+ * The solver keeps one exit wave per position and mode, waves (nscan,S,pw,pw)
+ * c64.  With O_n = patch_n(psi) (taps and weights as tike_conv_fwd has them; a
+ * tap outside the object counts as zero), P_s = probe[s] (S,pw,pw) c64 shared
+ * by every position, psi (H,W) c64, scan (nscan,2) f32 and a = relaxation: */
+
+/* The reflected estimate, padded for the transform:
+ *   nearplane[n][s] = pad( (1 + a) P_s O_n - a waves[n][s] )
+ * nearplane (nscan,S,det,det) c64, overwritten: the centred pw window as
+ * tike_conv_fwd places it (offset (det - pw) / 2), exactly 0.0 around it --
+ * every element is written once by its one owner, so no memset is needed and
+ * two calls give the same bits.  waves == NULL means that the waves ARE P O
+ * (the state a reconstruction starts from): the plane is pad(P_s O_n), no wave
+ * is read, and the bits are those of a call with waves holding those very
+ * products.  One gather of the four taps per pixel serves all S modes.  Any
+ * S >= 1, any det >= pw; float32 products; 16-byte accesses along rows;
+ * 64-bit offsets.  Nothing outside the arrays is touched, whatever the
+ * positions.  No allocation.  Per position S det^2 8 bytes are written,
+ * S pw^2 8 bytes of waves read (none with NULL), (pw + 1)^2 8 bytes of object
+ * taps and S pw^2 8 bytes of probe (mostly from cache), 8 bytes of scan.
+ * TIKE_ERR_ARG for a NULL psi, scan, probe or nearplane, pw > det, S < 1,
+ * pw < 1, H < 1, W < 2, a non-finite relaxation, nscan < 0, nscan > 2^31 - 1
+ * or a plane of more items than one launch holds; nscan == 0 returns 0
+ * without a launch. */
+int tike_dm_reflect(const void* psi, const float* scan, const void* probe, const void* waves,
+                    void* nearplane, float relaxation, long nscan, int S, int pw, int det, int H,
+                    int W, void* stream);
+
+/* The difference-map update of the waves, in place:
+ *   waves[n][s] <- (1 - a) waves[n][s] + a P_s O_n + crop(chi[n][s])
+ * chi (nscan,S,det,det) c64: the padded inverse transform of the projected far
+ * plane (tike_farplane_gradient, model 0, apply_gradient 1) BEFORE the crop,
+ * with the inverse's scale already applied; only its centred pw window is
+ * read, and it is not written.  P O is gathered again, not stored.  The step
+ * is formed as a (P_s O_n - waves) + crop(chi) and added to the wave.
+ * change (nscan) f64, if not NULL, receives sum_{s,pixels} |new - old|^2 of
+ * every position: float32 products summed in float64 in a fixed order by ONE
+ * workgroup per position (without it the (pw,pw) plane of a position is spread
+ * over several) -- no atomics, so it needs no deterministic-mode variant and
+ * two calls give the same bits.  chi must not overlap waves.  Any S >= 1, any
+ * det >= pw; 16-byte accesses along rows; 64-bit offsets.  Nothing outside the
+ * arrays is touched, whatever the positions.  No allocation.  Per position
+ * S pw^2 8 bytes of waves are read and as many written, the window's rows of
+ * chi read, object taps, probe and scan as above.  TIKE_ERR_ARG for a NULL
+ * waves, chi, psi, scan or probe, and as above. */
+int tike_dm_update(void* waves, const void* chi, const void* psi, const float* scan,
+                   const void* probe, float relaxation, double* change, long nscan, int S,
+                   int pw, int det, int H, int W, void* stream);
+
 /* ---- collectives: the per-minibatch gradient all-reduce over RCCL / xGMI,
  * one process (or thread) per GPU.  Replaces the serial peer-copy reduction of
  * communicators/pool.py:300-395 (reduce_gpu / allreduce) as composed by

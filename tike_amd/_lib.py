@@ -208,6 +208,8 @@ _PROTOTYPES = {
     "tike_cost_factor": [_p, _p, _i, _p, _p, _p, _p, _l, _i, _l, _i, _l, _p],
     "tike_cost_curvature": [_p, _p, _p, _i, _p, _p, _p, _p, _p, _l, _i, _l, _i,
                             _f, _l, _p],
+    "tike_dm_reflect": [_p, _p, _p, _p, _p, _f, _l, _i, _i, _i, _i, _i, _p],
+    "tike_dm_update": [_p, _p, _p, _p, _p, _f, _p, _l, _i, _i, _i, _i, _i, _p],
     "tike_comm_unique_id": [_p],
     "tike_comm_create": [_p, _i, _i, ctypes.POINTER(_p)],
     "tike_comm_destroy": [_p],

@@ -25,6 +25,8 @@ the tests that compare two routes.
                             multislice cgrad: the general operators slice by
                             slice / the step back through a slice as the three
                             launches `tike_slice_step_back` replaces
+  TIKE_DM_FUSED=0           dm, 256^2 / 512^2: the exit-wave step with a stored
+                            far plane instead of the far-plane-free route
   TIKE_CGRAD_GRAPHS=1       cgrad: replay captured HIP graphs (slower on ROCm 7.2)
   TIKE_FWD_SUB_MIB=n        Ptycho.fwd / adj: far-plane MiB per sub-batch
 """
@@ -52,6 +54,7 @@ multislice_first_stored = _flag("TIKE_MS_FIRST_STORED", True)
 multislice_step_back = _flag("TIKE_MS_STEP_BACK", True)
 cgrad_multislice_fused = _flag("TIKE_CGRAD_MS_FUSED", True)
 cgrad_multislice_step_back = _flag("TIKE_CGRAD_MS_STEP_BACK", True)
+dm_fused = _flag("TIKE_DM_FUSED", True)
 cgrad_graphs = _flag("TIKE_CGRAD_GRAPHS", False)
 fwd_sub_mib = (float(os.environ["TIKE_FWD_SUB_MIB"])
                if os.environ.get("TIKE_FWD_SUB_MIB") else None)

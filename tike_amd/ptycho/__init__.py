@@ -15,16 +15,17 @@ from .probe import (ProbeOptions, add_modes_cartesian_hermite,
                     orthogonalize_eig, simulate_varying_weights)
 from .ptycho import (Reconstruction, reconstruct, reconstruct_multigrid,
                      simulate)
-from .solvers import (CgradOptions, LstsqOptions, PtychoParameters,
-                      RpieOptions, cgrad, lstsq_grad, rpie,
-                      update_preconditioners)
+from .solvers import (CgradOptions, DmOptions, LstsqOptions,
+                      PtychoParameters, RpieOptions, cgrad, dm, lstsq_grad,
+                      rpie, update_preconditioners)
 from . import probe, object, position, exitwave, solvers, io, learn, fresnel  # noqa: F401,A004
 
 __all__ = [
-    "CgradOptions", "ExitWaveOptions", "LstsqOptions", "ObjectOptions",
+    "CgradOptions", "DmOptions", "ExitWaveOptions", "LstsqOptions",
+    "ObjectOptions",
     "AffineTransform", "PositionOptions", "affine_position_regularization",
     "ProbeOptions", "PtychoParameters", "Reconstruction",
-    "RpieOptions", "cgrad", "check_allowed_positions", "lstsq_grad",
+    "RpieOptions", "cgrad", "check_allowed_positions", "dm", "lstsq_grad",
     "position_pd_shifts", "update_positions_pd",
     "reconstruct", "reconstruct_multigrid", "rpie", "simulate",
     "update_preconditioners",

@@ -50,6 +50,27 @@ class RpieOptions(IterativeOptions):
 
 
 @dataclasses.dataclass
+class DmOptions(IterativeOptions):
+    """Options of the difference-map solver (`solvers.dm`; Thibault et al.
+    2008 / 2009; the reference snapshot has none).
+
+    ``relaxation`` (> 0) is the `a` of the exit-wave step
+    ``waves <- waves + P_F((1 + a) P O - a waves) - P O`` written out in
+    `solvers.dm`; 1 is the classic difference map.  ``overlap_iter`` (>= 1)
+    alternations of the object and the probe update follow it every epoch.
+    ``object_inertia`` / ``probe_inertia`` (>= 0), times the largest
+    denominator, keep the previous object / probe where nothing illuminates
+    them.  The minibatches only partition the work of an epoch."""
+    name: str = dataclasses.field(default="dm", init=False)
+    num_batch: int = 1
+    batch_method: str = "compact"
+    relaxation: float = 1.0
+    overlap_iter: int = 2
+    object_inertia: float = 1e-4
+    probe_inertia: float = 1e-9
+
+
+@dataclasses.dataclass
 class CgradOptions(IterativeOptions):
     """Conjugate-gradient solver composed from tike.opt.conjugate_gradient
     (the reference snapshot has no ptychography cgrad).
