@@ -1475,6 +1475,66 @@ int tike_cost_curvature(const void* farplane, const void* dfarplane, const void*
                         float* costs, float* dcosts, float* table, long nframe, int P,
                         long npix, int model, float floor, long num_measured, void* stream);
 
+/* ---- detector binning (no reference counterpart: `binned_pix` in the
+ * reference's readers bins the data, never the model): the far plane is
+ * modelled on a grid `binning` = B times finer than the measured pixels, and a
+ * measured pixel is the incoherent sum over its B x B far-plane pixels.  It
+ * generalises tike_fly_farplane_gradient (ptycho/ptycho.py:95-125 with
+ * operators/cupy/objective.py:11-15, 31-44 and :72-74, 90-104) along the
+ * detector axes.  det is the far-plane width, det % B == 0, w = det / B the
+ * data width.  farplane (nframe*fly,S,det,det) c64; data (nframe,w,w) f32, or
+ * uint16 when data_u16 != 0; measured (w,w) uint8 mask at data resolution or
+ * NULL, num_measured its non-zero (data) pixels.  In the stored (FFT-shifted)
+ * layout
+ *   I[f][U][V] = sum_{u<B} sum_{v<B} sum_{j<fly} sum_{m<S}
+ *                |farplane[f*fly+j][m][U*B+u][V*B+v]|^2
+ * intensity (nframe,w,w) = I and costs (nframe) = mean over the measured data
+ * pixels of the term of objective.py:11-15 (model 0) or :72-74 (model 1) are
+ * optional outputs (NULL to skip).  With apply_gradient every far-plane pixel
+ * of bin (U,V), in every plane of the frame, is multiplied by
+ *   -(1 - sqrt(d)/(sqrt(I)+1e-9)) or -(1 - d/(I+1e-9))   on measured bins,
+ *   unmeasured_scaling - 1                                elsewhere;
+ * without it the far plane is read once and never written.  Unmeasured counts
+ * (possibly NaN) are selected away by the mask.  One workgroup per frame; a
+ * pixel's planes are summed first, then the pixels of a bin's row, then its
+ * rows, in float32; the cost in float64 in a fixed order, no atomics: two
+ * calls give the same bits.  B in {2,4,8} with det % 4 == 0: 16-byte far-plane
+ * accesses, and with apply_gradient and B*fly*S <= 32 the bin's row-planes
+ * stay in registers (one read, one write of the far plane; four pixels per
+ * lane up to 16 row-planes, two above); beyond 32 they are read a second
+ * time.  Any other B dividing det, and any det: one bin per
+ * lane, pixel by pixel.  binning == 1 forwards to tike_fly_farplane_gradient:
+ * the same launch, the same bits.  No allocation.  TIKE_ERR_ARG for
+ * binning < 1, det % binning != 0 and whatever tike_fly_farplane_gradient
+ * refuses; nframe == 0 returns 0 without a launch. */
+int tike_binned_farplane_gradient(void* farplane, const void* data, int data_u16,
+                                  const unsigned char* measured, float* intensity,
+                                  float* costs, int nframe, int fly, int S, int det,
+                                  int binning, int model, int apply_gradient,
+                                  float unmeasured_scaling, long num_measured, void* stream);
+
+/* tike_cost_factor under detector binning (no reference counterpart;
+ * tike_amd.autograd.cost(binning=B); the objective lines above).  farplane
+ * (nframe,P,det,det) c64, P = fly * S, npix = det * det; data (nframe,w,w) and
+ * measured (w,w) at data resolution, w = det / binning; upstream (nframe) or
+ * NULL (ones).  costs (nframe) carries the bits of
+ * tike_binned_farplane_gradient's costs on the same far plane (one kernel
+ * body, the formulas of noise_model.h).  table (nframe,det,det) f32 is at
+ * FAR-PLANE resolution:
+ *   table[f][U*B+u][V*B+v] = upstream[f] l'(I[f][U][V], d[f][U][V]) / num_measured
+ * on measured bins and 0 exactly elsewhere, a bin's value replicated over its
+ * B x B pixels, so that tike_ifft2_crop_scaled, tike_ifft2_pass1_scaled and
+ * tike_farplane_scale take it unchanged.  table may be NULL (costs only).  The
+ * far plane is not written.  binning == 1 forwards to tike_cost_factor.  No
+ * atomics: two calls give the same bits.  No allocation.  TIKE_ERR_ARG for
+ * binning < 1, det % binning != 0, npix != det * det and whatever
+ * tike_cost_factor refuses; nframe == 0 returns 0 without a launch. */
+int tike_binned_cost_factor(const void* farplane, const void* data, int data_u16,
+                            const unsigned char* measured, const float* upstream,
+                            float* costs, float* table, long nframe, int P, long npix,
+                            int model, long num_measured, int det, int binning,
+                            void* stream);
+
 /* ==== the difference map (tike_amd/ptycho/solvers/dm.py; Thibault et al.
  * 2008 / 2009; no reference counterpart): the two ends of its exit-wave step.
  * The solver keeps one exit wave per position and mode, waves (nscan,S,pw,pw)

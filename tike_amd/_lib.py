@@ -208,6 +208,10 @@ _PROTOTYPES = {
     "tike_cost_factor": [_p, _p, _i, _p, _p, _p, _p, _l, _i, _l, _i, _l, _p],
     "tike_cost_curvature": [_p, _p, _p, _i, _p, _p, _p, _p, _p, _l, _i, _l, _i,
                             _f, _l, _p],
+    "tike_binned_farplane_gradient": [_p, _p, _i, _p, _p, _p, _i, _i, _i, _i,
+                                      _i, _i, _i, _f, _l, _p],
+    "tike_binned_cost_factor": [_p, _p, _i, _p, _p, _p, _p, _l, _i, _l, _i, _l,
+                                _i, _i, _p],
     "tike_dm_reflect": [_p, _p, _p, _p, _p, _f, _l, _i, _i, _i, _i, _i, _p],
     "tike_dm_update": [_p, _p, _p, _p, _p, _f, _p, _l, _i, _i, _i, _i, _i, _p],
     "tike_comm_unique_id": [_p],

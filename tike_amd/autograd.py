@@ -213,7 +213,12 @@ loop with the far plane resident --
 -- and for several slices the forward-mode chunks (the table over all frames)
 followed by the backward of `multislice_intensity`.  No tensor of
 N // fly * det * det elements exists in `cost`, `cost_jvp` or the one-slice
-product.
+product.  ``cost(..., binning=B)`` is the same cost with the far plane B times
+finer than the counts (a measured pixel the sum over its B x B far-plane
+pixels): tike_binned_cost_factor in the place of tike_cost_factor, its table
+at far-plane resolution with a bin's value on each of its pixels, the chain
+behind it unchanged; `cost_jvp` and `cost_gauss_newton_product` refuse
+binning > 1 by name.
 
 The entries share their bodies: the three `*_jvp` functions are `_jvp`, the
 three `*_gauss_newton_product` functions `_gauss_newton`, over `_checked_jvp`
@@ -1450,11 +1455,21 @@ COST_FLOOR = 1e-9
 
 def _checked_cost(name, operator, data, measured_pixels, model, psi, probe,
                   scan, eigen_probe, eigen_weights, fly, check_positions,
-                  checked):
+                  checked, binning=1):
     """Every refusal of the cost functions, none of which needs a device until
     the last: (fly, whatever `checked` returns besides, counts, mask or None,
     num_measured, the model's number).  checked(slices): the form's own
-    `_checked*` call, which returns fly or (fly, tangents)."""
+    `_checked*` call, which returns fly or (fly, tangents).  binning = B: the
+    counts and the mask are (det // B, det // B), num_measured counts data
+    pixels."""
+    if (isinstance(binning, bool) or not isinstance(binning, int)
+            or binning < 1):
+        raise ValueError(
+            f"{name}: binning={binning!r}: expected an integer >= 1")
+    if operator.detector_shape % binning:
+        raise ValueError(
+            f"{name}: binning={binning} does not divide the far-plane width "
+            f"{operator.detector_shape}")
     if not isinstance(data, torch.Tensor):
         raise TypeError(
             f"{name}: data must be a torch device tensor, not "
@@ -1463,14 +1478,15 @@ def _checked_cost(name, operator, data, measured_pixels, model, psi, probe,
         raise TypeError(
             f"{name}: data must be torch.float32 or torch.uint16, not "
             f"{data.dtype}")
-    det = operator.detector_shape
+    det = operator.detector_shape // binning  # (the data width)
     frames = _frames(scan, fly)
     if data.ndim != 3 or tuple(data.shape[1:]) != (det, det) or (
             frames is not None and data.shape[0] != frames):
         raise ValueError(
             f"{name}: data must be (N // fly, det, det) = "
             f"({'?' if frames is None else frames}, {det}, {det}), not "
-            f"{tuple(data.shape)}")
+            f"{tuple(data.shape)}"
+            + ("" if binning == 1 else f" (binning={binning})"))
     mask, num_measured = None, det * det
     if measured_pixels is not None:
         mask = measured_pixels
@@ -1515,15 +1531,29 @@ class _Counts:
     """The counts, the mask and the noise model of one call, and the two
     entries on a chunk's far plane."""
 
-    def __init__(self, data, mask, num_measured, model, fly):
+    def __init__(self, data, mask, num_measured, model, fly, binning=1):
         self.data, self.mask, self.nm = data, mask, num_measured
-        self.model, self.fly = model, fly
+        self.model, self.fly, self.binning = model, fly, binning
         self.u16 = int(data.dtype == torch.uint16)
 
     def factor(self, lo, hi, far, upstream, costs, table):
-        """tike_cost_factor on the frames of the positions lo ... hi - 1."""
+        """tike_cost_factor on the frames of the positions lo ... hi - 1;
+        with binning > 1 tike_binned_cost_factor: counts and mask at data
+        resolution, the table at the far plane's."""
         fly = self.fly
         flo, nf = lo // fly, (hi - lo) // fly
+        if self.binning > 1:
+            check(
+                lib.tike_binned_cost_factor(
+                    A.ptr(far), A.ptr(self.data[flo:]), self.u16,
+                    A.ptr(self.mask),
+                    None if upstream is None else A.ptr(upstream[flo:]),
+                    None if costs is None else A.ptr(costs[flo:]),
+                    A.ptr(table), nf, far.shape[-3] * fly,
+                    far.shape[-1] * far.shape[-2], self.model, self.nm,
+                    far.shape[-1], self.binning, A.stream_ptr()),
+                "cost (tike_binned_cost_factor)")
+            return
         check(
             lib.tike_cost_factor(
                 A.ptr(far), A.ptr(self.data[flo:]), self.u16,
@@ -1634,7 +1664,7 @@ class _Cost(torch.autograd.Function):
 
 def cost(operator, data, psi, probe, scan, *, model="gaussian",
          measured_pixels=None, eigen_probe=None, eigen_weights=None, fly=1,
-         check_positions=True):
+         binning=1, check_positions=True):
     """The per-frame cost (N // fly,) float32 of the model's intensity against
     the counts `data` (N // fly, det, det) float32 or uint16 under the
     project's noise models -- "gaussian": mean of (sqrt(I) - sqrt(d))^2,
@@ -1655,7 +1685,17 @@ def cost(operator, data, psi, probe, scan, *, model="gaussian",
     and the form's backward chain from the point where it reads the table.  No
     tensor of N // fly * det * det elements exists at any time.
 
-    Raises what the form's intensity raises, TypeError / ValueError for data
+    binning = B > 1 (B divides det): the far plane is B times finer than the
+    counts -- data (N // fly, det // B, det // B), measured_pixels
+    (det // B, det // B), a measured pixel the sum of the model's intensity
+    over its B x B far-plane pixels -- for every form; ``cost(...).mean()`` is
+    ``Ptycho.cost(..., binning=B)``.  tike_binned_cost_factor stands in the
+    place of tike_cost_factor and writes the chunk's table at far-plane
+    resolution, a bin's value replicated over its pixels, so the backward
+    chain is unchanged; no binned or unbinned intensity of all frames exists.
+
+    Raises what the form's intensity raises, ValueError for a binning that is
+    no integer >= 1 or does not divide the far-plane width, TypeError / ValueError for data
     or measured_pixels of another type, dtype or shape, ValueError for a mask
     that measures nothing or an unknown model, NotImplementedError for several
     slices with eigen probes.  measured_pixels costs a read-back per call.
@@ -1669,9 +1709,18 @@ def cost(operator, data, psi, probe, scan, *, model="gaussian",
 
     fly, data, mask, nm, model = _checked_cost(
         name, operator, data, measured_pixels, model, psi, probe, scan,
-        eigen_probe, eigen_weights, fly, check_positions, checked)
+        eigen_probe, eigen_weights, fly, check_positions, checked, binning)
     return _Cost.apply(psi, probe, scan, eigen_probe, eigen_weights, operator,
-                       _Counts(data, mask, nm, model, fly))
+                       _Counts(data, mask, nm, model, fly, binning))
+
+
+def _refuse_binned_curvature(name, binning):
+    """`cost_jvp` and `cost_gauss_newton_product` on a binned far plane."""
+    if binning != 1:
+        raise NotImplementedError(
+            f"{name} with binning={binning!r}: the forward-mode derivative "
+            "and the Gauss-Newton product of the cost are not implemented "
+            "for a binned far plane; `cost` is")
 
 
 def _cost_tangents(name, operator, data, measured_pixels, model, psi, probe,
@@ -1701,7 +1750,7 @@ def _cost_tangents(name, operator, data, measured_pixels, model, psi, probe,
 def cost_jvp(operator, data, psi, probe, scan, *, model="gaussian",
              measured_pixels=None, eigen_probe=None, eigen_weights=None,
              d_psi=None, d_probe=None, d_scan=None, d_eigen_probe=None,
-             d_eigen_weights=None, fly=1, check_positions=True):
+             d_eigen_weights=None, fly=1, binning=1, check_positions=True):
     """(costs, dcosts), both (N // fly,) float32 outside any autograd graph:
     the costs of `cost` -- the same bits -- and their directional derivative
     along the tangents of the form's `*_jvp` function (each None or of its
@@ -1710,8 +1759,11 @@ def cost_jvp(operator, data, psi, probe, scan, *, model="gaussian",
     tike_intensity_tangent: neither I nor dI is stored.  With no tangent
     dcosts is zeros and only the primal launches.
 
-    Raises what `cost` and the form's `*_jvp` function raise.
+    Raises what `cost` and the form's `*_jvp` function raise, and
+    NotImplementedError for binning > 1 (there is no curvature entry for a
+    binned far plane).
     """
+    _refuse_binned_curvature("cost_jvp", binning)
     counts, primals, tangents = _cost_tangents(
         "cost_jvp", operator, data, measured_pixels, model, psi, probe, scan,
         eigen_probe, eigen_weights, d_psi, d_probe, d_scan, d_eigen_probe,
@@ -1735,7 +1787,7 @@ def cost_gauss_newton_product(operator, data, psi, probe, scan, *,
                               eigen_probe=None, eigen_weights=None, d_psi=None,
                               d_probe=None, d_scan=None, d_eigen_probe=None,
                               d_eigen_weights=None, upstream=None,
-                              floor=COST_FLOOR, fly=1, wrt=None,
+                              floor=COST_FLOOR, fly=1, wrt=None, binning=1,
                               check_positions=True):
     """J^T diag(upstream_f c / (num_measured (I + floor))) J v on the measured
     pixels: the Gauss-Newton matrix of sum_f upstream_f cost_f applied to the
@@ -1760,9 +1812,10 @@ def cost_gauss_newton_product(operator, data, psi, probe, scan, *,
     Raises what `cost_jvp` raises, ValueError for names in `wrt` the form does
     not have (or none, or one twice), for a negative or non-finite floor,
     TypeError / ValueError for an upstream of another type, dtype, shape or
-    device.
+    device, NotImplementedError for binning > 1.
     """
     name = "cost_gauss_newton_product"
+    _refuse_binned_curvature(name, binning)
     names = _EIGEN_WRT if eigen_weights is not None else _WRT
     wrt = _checked_product(
         name, operator, (psi, probe, scan, eigen_probe, eigen_weights), None,

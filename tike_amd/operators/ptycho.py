@@ -271,25 +271,74 @@ class Ptycho(Operator):
                 A.stream_ptr()), "Ptycho.fly_farplane_gradient")
         return farplane
 
-    def _compute_intensity(self, data, psi, scan, probe, fly=1):
+    def binned_farplane_gradient(self, farplane, data, fly, binning, *,
+                                 model=0, measured=None, num_measured=None,
+                                 intensity=None, costs=None,
+                                 apply_gradient=False, unmeasured_scaling=1.0):
+        """`tike_binned_farplane_gradient` on device tensors: the far plane
+        (FRAME * fly, 1, SHARED, det, det) is `binning` = B times finer than
+        the measured pixels, w = det // B.  data (FRAME, w, w) float32 or
+        uint16; measured a (w, w) uint8 mask or None; intensity (FRAME, w, w)
+        and costs (FRAME) float32 outputs or None.  In the stored layout
+        (FFT-shifted, the peak at the corners) a measured pixel (U, V) is the
+        sum of |farplane|^2 over the rows U * B ... U * B + B - 1, the columns
+        V * B ... V * B + B - 1, the frame's positions and the modes.  When w
+        is even this block sum equals the block sum on the centred detector:
+        fftshift(I) == blocksum(fftshift(fine)), because the shift by det / 2
+        = (w / 2) * B moves whole blocks.  With apply_gradient every far-plane
+        pixel of a bin is scaled by the bin's factor (-gradient factor on
+        measured bins).  binning == 1 is `fly_farplane_gradient`."""
+        det = self.detector_shape
+        B = int(binning)
+        if B < 1 or det % B:
+            raise ValueError(
+                f"binning={binning!r} does not divide the far-plane width "
+                f"{det}")
+        w = det // B
+        S = farplane.shape[-3]
+        nframe = data.shape[0]
+        assert farplane.shape[0] == nframe * fly, (farplane.shape, nframe, fly)
+        assert tuple(farplane.shape[-2:]) == (det, det), farplane.shape
+        assert tuple(data.shape[1:]) == (w, w), data.shape
+        assert data.dtype in (torch.float32, torch.uint16), data.dtype
+        assert measured is None or tuple(measured.shape) == (w, w)
+        assert intensity is None or tuple(intensity.shape) == (nframe, w, w)
+        check(
+            lib.tike_binned_farplane_gradient(
+                A.ptr(farplane), A.ptr(data), int(data.dtype == torch.uint16),
+                A.ptr(measured), A.ptr(intensity), A.ptr(costs), nframe,
+                int(fly), S, det, B, int(model), int(bool(apply_gradient)),
+                float(unmeasured_scaling),
+                w * w if num_measured is None else int(num_measured),
+                A.stream_ptr()), "Ptycho.binned_farplane_gradient")
+        return farplane
+
+    def _compute_intensity(self, data, psi, scan, probe, fly=1, binning=1):
         """(intensity (FRAME,det,det), farplane) -- ptycho.py:178-191; with
         fly > 1 a frame is the sum over `fly` consecutive positions
-        (ptycho.py:104-125)."""
+        (ptycho.py:104-125); with binning = B > 1 the intensity is
+        (FRAME, det // B, det // B), a pixel the sum over its B x B far-plane
+        pixels (`binned_farplane_gradient`)."""
         kind = psi
         far = self.fwd_device(A.to_device(probe, np.complex64),
                               A.to_device(scan, np.float32),
                               A.to_device(psi, np.complex64))
         N, _, S, det, _ = far.shape
-        if fly > 1:
+        if fly > 1 or binning > 1:
             if N % fly:
                 raise ValueError(
                     f"{N} scan positions are not a multiple of fly={fly}")
-            intensity = torch.empty((N // fly, det, det), dtype=torch.float32,
+            if binning < 1 or det % binning:
+                raise ValueError(
+                    f"binning={binning!r} does not divide the far-plane "
+                    f"width {det}")
+            w = det // binning
+            intensity = torch.empty((N // fly, w, w), dtype=torch.float32,
                                     device=far.device)
             # (the counts are read by the cost and the gradient only: any
             # array of the frames' shape serves)
-            self.fly_farplane_gradient(far, torch.zeros_like(intensity), fly,
-                                       intensity=intensity)
+            self.binned_farplane_gradient(far, torch.zeros_like(intensity),
+                                          fly, binning, intensity=intensity)
             return A.like_input(intensity, kind), A.like_input(far, kind)
         intensity = torch.empty((N, det, det), dtype=torch.float32,
                                 device=far.device)
@@ -298,10 +347,10 @@ class Ptycho(Operator):
                                A.stream_ptr()), "Ptycho._compute_intensity")
         return A.like_input(intensity, kind), A.like_input(far, kind)
 
-    def cost(self, data, psi, scan, probe, *, model, fly=1):
-        """ptycho.py:193-204; with fly > 1 the mean over frames of the cost
-        of each frame's summed intensity."""
-        if fly > 1:
+    def cost(self, data, psi, scan, probe, *, model, fly=1, binning=1):
+        """ptycho.py:193-204; with fly > 1 or binning > 1 the mean over frames
+        of the cost of each frame's summed (and binned) intensity."""
+        if fly > 1 or binning > 1:
             if model not in objective._MODELS:
                 raise ValueError(f"unknown noise model {model!r}")
             kind = psi
@@ -317,9 +366,10 @@ class Ptycho(Operator):
                     f"{far.shape[0]} scan positions")
             costs = torch.empty(counts.shape[0], dtype=torch.float32,
                                 device=far.device)
-            self.fly_farplane_gradient(far, counts.contiguous(), fly,
-                                       model=objective._MODELS[model],
-                                       costs=costs)
+            self.binned_farplane_gradient(far, counts.contiguous(), fly,
+                                          binning,
+                                          model=objective._MODELS[model],
+                                          costs=costs)
             return A.like_input(costs.mean(), kind)
         intensity, _ = self._compute_intensity(data, psi, scan, probe)
         return getattr(objective, model)(data, intensity)

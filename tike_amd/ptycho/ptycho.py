@@ -42,7 +42,7 @@ from .probe import (apply_median_filter_abs_probe, constrain_center_peak,
                     finite_probe_support, get_varying_probe, orthogonalize_eig,
                     power as probe_power,
                     rescale_probe_using_fixed_intensity_photons)
-from .solvers.cgrad import _refuse_fly, _refuse_multislice
+from .solvers.cgrad import _refuse_binning, _refuse_fly, _refuse_multislice
 from .solvers.dm import refuse as _refuse_dm
 from .solvers.lstsq import chunk_positions, mask_info
 from .._lib import check, lib
@@ -51,9 +51,11 @@ logger = logging.getLogger(__name__)
 
 
 def _intensity_chunks(operator, psi, scan, probe, eigen_probe=None,
-                      eigen_weights=None, fly=1):
+                      eigen_weights=None, fly=1, binning=1):
     """Yield (lo, hi, intensity (n, det, det)) over chunks of frames; frame f
-    is the sum over the positions f * fly ... f * fly + fly - 1."""
+    is the sum over the positions f * fly ... f * fly + fly - 1.  With
+    binning = B > 1 the intensity is (n, det // B, det // B), a pixel the sum
+    over its B x B far-plane pixels."""
     N = scan.shape[0]
     S = probe.shape[-3]
     det = operator.detector_shape
@@ -71,9 +73,13 @@ def _intensity_chunks(operator, psi, scan, probe, eigen_probe=None,
                                scan=scan[lo:hi], psi=psi).contiguous()
         else:
             far = operator.fwd_device(probe, scan[lo:hi], psi, eigen_probe, w)
-        inten = torch.empty(((hi - lo) // fly, det, det), dtype=torch.float32,
+        w = det // binning
+        inten = torch.empty(((hi - lo) // fly, w, w), dtype=torch.float32,
                             device=psi.device)
-        if fly > 1:
+        if binning > 1:
+            operator.binned_farplane_gradient(far, torch.zeros_like(inten),
+                                              fly, binning, intensity=inten)
+        elif fly > 1:
             # (the counts are read by the cost and the gradient only)
             operator.fly_farplane_gradient(far, torch.zeros_like(inten), fly,
                                            intensity=inten)
@@ -85,9 +91,13 @@ def _intensity_chunks(operator, psi, scan, probe, eigen_probe=None,
 
 
 def simulate(detector_shape, probe, scan, psi, fly=1, eigen_probe=None,
-             eigen_weights=None, **kwargs):
+             eigen_weights=None, binning=1, **kwargs):
     """Real-valued detector counts of simulated ptychography data
-    (ptycho.py:128-179).  Returns (FRAME, det, det) float32 on the host."""
+    (ptycho.py:128-179).  Returns (FRAME, det, det) float32 on the host.
+    binning = B > 1: `detector_shape` stays the far-plane width, a measured
+    pixel is the sum over its B x B far-plane pixels, and the result is
+    (FRAME, det // B, det // B)."""
+    binning = _checked_binning(binning, int(detector_shape))
     check_allowed_positions(scan, psi, probe.shape)
     real, cplx = precision.floating, precision.cfloating
     wanted = ((psi, cplx), (scan, real), (probe, cplx), (eigen_probe, cplx),
@@ -98,13 +108,13 @@ def simulate(detector_shape, probe, scan, psi, fly=1, eigen_probe=None,
                     for a, t in wanted]
         # (`fly` consecutive positions expose one frame: summed by the kernel)
         frames = torch.cat([
-            inten for _, _, inten in _intensity_chunks(operator, *resident,
-                                                       fly=int(fly))])
+            inten for _, _, inten in _intensity_chunks(
+                operator, *resident, fly=int(fly), binning=binning)])
         return operator.asnumpy(frames)
 
 
 def reconstruct(data, parameters, num_gpu=None, use_mpi=False, *, fly=1,
-                **kwargs):
+                binning=1, **kwargs):
     """Solve the ptychography problem (ptycho.py:182-262).
 
     data (FRAME, WIDE, HIGH): measured intensities, FFT-shifted so that the
@@ -123,13 +133,27 @@ def reconstruct(data, parameters, num_gpu=None, use_mpi=False, *, fly=1,
     `data` holds one frame per `fly` consecutive rows of `parameters.scan`
     (what `simulate(..., fly=fly)` produces); cgrad alone reconstructs such
     data (see `Reconstruction`).
+
+    binning (keyword only): far-plane pixels per measured pixel along each
+    detector axis.  With binning = B > 1 the far field is modelled at
+    `data.shape[-1] * B` pixels and a measured pixel is the sum over its B x B
+    model pixels (what `simulate(..., binning=B)` produces): the probe window
+    may then be up to B times as wide as the data.  cgrad alone reconstructs
+    such data.
     """
     if use_mpi:
         raise NotImplementedError(
             "multi-node MPI is out of scope; launch one process per GPU "
             "with torchrun instead")
     fly = _checked_fly(fly)
+    binning = _checked_binning(binning)
     requested = _spawn.requested_devices(num_gpu)
+    if (binning > 1 and requested is not None and len(requested) > 1
+            and _spawn.world_size() == 1):
+        raise NotImplementedError(
+            f"binning={binning} with reconstruct(num_gpu={num_gpu!r}) from a "
+            "plain process: the ranks this call would start do not take "
+            "binned data")
     if (fly > 1 and requested is not None and len(requested) > 1
             and _spawn.world_size() == 1):
         raise NotImplementedError(
@@ -141,19 +165,24 @@ def reconstruct(data, parameters, num_gpu=None, use_mpi=False, *, fly=1,
         return _spawn.reconstruct_spawned(data, parameters, where, **kwargs)
     with Reconstruction(data, parameters,
                         num_gpu if where is None else (where,),
-                        use_mpi, fly=fly, **kwargs) as context:
+                        use_mpi, fly=fly, binning=binning,
+                        **kwargs) as context:
         context.iterate(parameters.algorithm_options.num_iter)
         result = context.get_result()
     return result
 
 
 def reconstruct_multigrid(data, parameters, num_gpu=None, use_mpi=False,
-                          num_levels=3, interp=None):
+                          num_levels=3, interp=None, *, binning=1):
     """Coarse-to-fine reconstruction (ptycho.py:975-1047): the real-space
     parameters are downsampled by 2^(num_levels-1) and the diffraction
     patterns cropped in Fourier space, every level runs
     `algorithm_options.num_iter` epochs and hands its upsampled result to the
     next."""
+    if _checked_binning(binning) > 1:
+        raise NotImplementedError(
+            f"binning={binning} with reconstruct_multigrid: cropping binned "
+            "diffraction patterns in Fourier space is not implemented")
     data = A.to_host(data)
     coarsest = 2**(num_levels - 1)
     if data.shape[-1] / coarsest < 64:
@@ -207,6 +236,33 @@ def _checked_fly(fly):
         raise ValueError(f"fly={fly!r}: expected an integer >= 1, the number "
                          "of scan positions per diffraction pattern")
     return int(fly)
+
+
+def _checked_binning(binning, det=None):
+    """`binning` as an int >= 1 that divides the far-plane width `det`."""
+    if (isinstance(binning, bool) or not isinstance(
+            binning, (int, float, np.integer, np.floating))
+            or int(binning) != binning or int(binning) < 1):
+        raise ValueError(
+            f"binning={binning!r}: expected an integer >= 1, the number of "
+            "far-plane pixels per measured pixel along each detector axis")
+    if det is not None and det % int(binning):
+        raise ValueError(
+            f"binning={binning!r} does not divide the far-plane width {det}")
+    return int(binning)
+
+
+def _check_binning_supported(parameters, binning):
+    """A reconstruction of binned data is cgrad's, with a shared probe, one
+    slice and fixed positions: everything else is refused by name."""
+    if binning <= 1:
+        return
+    name = parameters.algorithm_options.name
+    if name != "cgrad":
+        raise NotImplementedError(
+            f"binning={binning} with {name}: binned data (a far plane finer "
+            "than the measured pixels) is reconstructed by cgrad only")
+    _refuse_binning(parameters, binning)
 
 
 def _check_fly_supported(parameters, fly):
@@ -269,10 +325,12 @@ def collapse_to_frames(order, batches, fly):
     return rows[:, 0] // fly, frame_batches
 
 
-def _check_data_shape(data, parameters, fly=1):
+def _check_data_shape(data, parameters, fly=1, binning=1):
     """The diffraction patterns against the forward model's shapes
     (reference ptycho.py:303-331: same conditions, same messages; with
-    fly > 1 a pattern per `fly` scan positions)."""
+    fly > 1 a pattern per `fly` scan positions; with binning > 1 the probe
+    window is held against the far-plane width, data width * binning, and
+    the mask against the data width)."""
     frames = tuple(int(n) for n in data.shape)
     window = tuple(int(n) for n in parameters.probe.shape[-2:])
     measured = parameters.exitwave_options.measured_pixels
@@ -294,10 +352,14 @@ def _check_data_shape(data, parameters, fly=1):
          f"data shape {data.shape}, scan shape {parameters.scan.shape} and "
          f"fly={fly} are incompatible. The scan should hold fly positions "
          "for every diffraction pattern."),
-        (all(w <= d for w, d in zip(window, frames[-2:])),
+        (all(w <= d * binning for w, d in zip(window, frames[-2:])),
          f"probe shape {parameters.probe.shape} "
          f"and data shape {data.shape} are incompatible. "
-         "The probe width/height must be <= the data width/height ."),
+         "The probe width/height must be <= the data width/height ."
+         if binning == 1 else
+         f"probe shape {parameters.probe.shape} and data shape {data.shape} "
+         f"with binning={binning} are incompatible. The probe width/height "
+         "must be <= the data width/height times binning."),
         (not masked or mask == frames[-2:],
          f"exitwave_options.measured_pixels shape {mask} "
          f"does not match the diffraction patterns {frames[-2:]}"),
@@ -362,14 +424,21 @@ class Reconstruction():
         positions with every frame's positions consecutive and ascending, and
         the solver must be cgrad with a shared probe, one slice and no
         position correction.
+      binning: far-plane pixels per measured pixel along each detector axis
+        (default 1).  With binning = B > 1 the operator's far plane is
+        `data.shape[-1] * B` wide, a measured pixel is the sum over its B x B
+        model pixels (`simulate(..., binning=B)`), `measured_pixels` stays at
+        data resolution, and the solver must be cgrad with a shared probe,
+        one slice and no position correction, in one process.
     """
 
     fly = 1  # scan positions per diffraction pattern
+    binning = 1  # far-plane pixels per measured pixel, per axis
 
     def __init__(self, data, parameters, num_gpu=None, use_mpi=False, *,
                  presharded=False, order=None, batches=None,
                  spatial_sort=True, data_on_host=False, local_data=None,
-                 fly=1):
+                 fly=1, binning=1):
         # a context lives in ONE process with ONE GPU: `num_gpu` must agree
         # with the process group it runs in (`reconstruct` is the entry that
         # starts ranks by itself)
@@ -385,8 +454,18 @@ class Reconstruction():
         if device is not None:
             torch.cuda.set_device(device)  # ptycho.py:344-345
         fly = self.fly = _checked_fly(fly)
-        _check_data_shape(data, parameters, fly)
+        binning = self.binning = _checked_binning(binning)
+        _check_data_shape(data, parameters, fly, binning)
         _check_fly_supported(parameters, fly)
+        _check_binning_supported(parameters, binning)
+        if binning > 1 and local_data is not None:
+            raise NotImplementedError(
+                f"binning={binning} with local_data (the ranks started by "
+                "reconstruct(num_gpu=N)) is not implemented")
+        if binning > 1 and _spawn.world_size() > 1:
+            raise NotImplementedError(
+                f"binning={binning} with the ranks of a torch.distributed "
+                "job: binned data is reconstructed in one process")
         if fly > 1 and local_data is not None:
             raise NotImplementedError(
                 f"fly={fly} with local_data (the ranks started by "
@@ -426,7 +505,7 @@ class Reconstruction():
         self._spatial_sort = spatial_sort
         self.operator = Ptycho(
             probe_shape=parameters.probe.shape[-1],
-            detector_shape=data.shape[-1],
+            detector_shape=data.shape[-1] * binning,
             nz=parameters.psi.shape[-2],
             n=parameters.psi.shape[-1],
             norm=parameters.exitwave_options.propagation_normalization,
@@ -440,6 +519,7 @@ class Reconstruction():
                 1e-9),
         )
         self.operator.fly = fly  # (a rank without a frame reads it: cgrad)
+        self.operator.binning = binning  # (cgrad reads it)
         self.comm = Comm()
         self._pending_fits = []  # futures of deferred affine position fits
         self._free_snaps = []  # pinned host buffers of finished fits
@@ -544,7 +624,8 @@ class Reconstruction():
                 self.parameters.probe_options.init_rescale_from_measurements):
             self.parameters = _rescale_probe(self.operator, self.comm,
                                              self.data, self.parameters,
-                                             fly=self.fly)
+                                             fly=self.fly,
+                                             binning=self.binning)
         return self
 
     def _enter_with_local_data(self):
@@ -629,6 +710,10 @@ class Reconstruction():
             raise NotImplementedError(
                 f"fly={self.fly} with update_positions_pd: position "
                 "refinement of fly-scan data is not implemented")
+        if self.binning > 1:
+            raise NotImplementedError(
+                f"binning={self.binning} with update_positions_pd: position "
+                "refinement of binned data is not implemented")
         p, comm = self.parameters, self.comm
         sums, _ = _pd_sums_device(self.operator, self.data, p.psi, p.probe,
                                   p.scan, float(dx), p.eigen_probe,
@@ -891,16 +976,17 @@ def _apply_object_constraints(parameters):
     return parameters
 
 
-def _rescale_probe(operator, comm, data, parameters, fly=1):
+def _rescale_probe(operator, comm, data, parameters, fly=1, binning=1):
     """probe *= sqrt(sum(data) / sum(intensity)) over measured pixels and all
     ranks (ptycho.py:873-972); with fly > 1 the intensity of a frame is the
-    sum over its positions and `data` is read by frame range."""
+    sum over its positions and `data` is read by frame range; with
+    binning > 1 the intensity and the mask are at data resolution."""
     nmeasured, mask_u8 = mask_info(parameters.exitwave_options,
-                                   operator.detector_shape)
+                                   operator.detector_shape // binning)
     sums = torch.zeros(2, dtype=torch.float64, device=parameters.psi.device)
     for lo, hi, inten in _intensity_chunks(operator, parameters.psi,
                                            parameters.scan, parameters.probe,
-                                           fly=fly):
+                                           fly=fly, binning=binning):
         d = A.data_f32(data, lo, hi)
         if mask_u8 is not None:
             m = mask_u8.bool()

@@ -38,6 +38,11 @@ no variable is recovered, one cost-only evaluation.
   ``tike_fly_farplane_gradient``, adjoint, chunk by chunk over whole frames).
   The device searches form the intensity per position: every line search is
   decided on the host.
+* binned data (the operator's ``binning`` = B > 1: a far plane B times finer
+  than the patterns, a measured pixel the sum over its B x B far-plane
+  pixels; no reference counterpart): the fly-scan route at any ``fly``, also
+  1, with ``tike_binned_farplane_gradient`` in that kernel's place; the mask
+  and the pixel count are at data resolution.
 * objects of several slices (``psi.shape[0] > 1``, probe window = detector):
   the same cost on the far field behind the last slice, e_d = patch(O_d) x
   beam_d, beam_{d+1} = Fresnel(e_d), and its EXACT gradient -- the adjoint
@@ -703,6 +708,13 @@ def _fly_of(op, data, scan):
 _REFUSALS = (
     # (the kind of minibatch, what it cannot be combined with, message), the
     # most specific wording first
+    ("binning", "positions", "binning={binning} with position_options: "
+     "position correction of binned data is not implemented"),
+    ("binning", "eigen", "binning={binning} with eigen probes: a varying "
+     "probe per position of binned data is not implemented"),
+    ("binning", "slices", "binning={binning} with several slices "
+     "(psi.shape[0] = {D}): multislice reconstruction of binned data is not "
+     "implemented"),
     ("fly", "positions", "fly={fly} with position_options: position "
      "correction of fly-scan data is not implemented"),
     ("fly", "eigen", "fly={fly} with eigen probes: a varying probe per "
@@ -719,21 +731,28 @@ _REFUSALS = (
 )
 
 
-def _refuse(parameters, fly, kinds=("fly", "slices", "any")):
+def _refuse(parameters, fly, kinds=("binning", "fly", "slices", "any"),
+            binning=1):
     """NotImplementedError for the first row of `_REFUSALS` that applies."""
     D = parameters.psi.shape[0]
-    has = dict(any=True, fly=fly > 1, slices=D > 1,
+    has = dict(any=True, fly=fly > 1, binning=binning > 1, slices=D > 1,
                positions=parameters.position_options is not None,
                eigen=(parameters.eigen_probe is not None
                       or parameters.eigen_weights is not None))
     for kind, other, message in _REFUSALS:
         if kind in kinds and has[kind] and has[other]:
-            raise NotImplementedError(message.format(fly=fly, D=D))
+            raise NotImplementedError(
+                message.format(fly=fly, binning=binning, D=D))
 
 
 def _refuse_fly(parameters, fly):
     """What a fly-scan reconstruction cannot be combined with."""
     _refuse(parameters, fly, ("fly",))
+
+
+def _refuse_binning(parameters, binning):
+    """What a reconstruction of binned data cannot be combined with."""
+    _refuse(parameters, 1, ("binning",), binning)
 
 
 def _refuse_multislice(parameters):
@@ -779,14 +798,16 @@ def _fly_adjoint(op, far, probe, scan, psi, want_psi, want_probe):
 
 
 def _fly_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, fly, *,
-                       want_psi, want_probe, want_grad, cm):
+                       want_psi, want_probe, want_grad, cm, binning=1):
     """(sum of this rank's per-frame costs, a device scalar; d cost / d psi or
     None; d cost / d probe or None -- unnormalised adjoints summed over the
     ranks) of the positions [lo, hi), whole frames: the data rows
     [lo / fly, hi / fly).  Per chunk of whole frames: the forward operator,
     `tike_fly_farplane_gradient` (costs only for a line-search probe: the far
     plane is read once and not written) and, for a gradient, the adjoint of
-    the far plane it left."""
+    the far plane it left.  binning > 1 (any fly): the data rows and the mask
+    are `binning` times coarser than the far plane and
+    `tike_binned_farplane_gradient` stands in that kernel's place."""
     assert lo % fly == 0 and hi % fly == 0, (lo, hi, fly)
     dev = psi.device
     S, det = probe.shape[-3], op.detector_shape
@@ -806,11 +827,14 @@ def _fly_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, fly, *,
         d = data[clo // fly:chi // fly]
         if d.dtype not in (torch.float32, torch.uint16):
             d = d.to(torch.float32)
-        op.fly_farplane_gradient(
-            far, d, fly, model=cm.model, measured=cm.mask,
-            num_measured=cm.nmeasured,
-            costs=costs[(clo - lo) // fly:(chi - lo) // fly],
-            apply_gradient=want_grad)
+        how = dict(model=cm.model, measured=cm.mask,
+                   num_measured=cm.nmeasured,
+                   costs=costs[(clo - lo) // fly:(chi - lo) // fly],
+                   apply_gradient=want_grad)
+        if binning > 1:
+            op.binned_farplane_gradient(far, d, fly, binning, **how)
+        else:
+            op.fly_farplane_gradient(far, d, fly, **how)
         if want_grad:
             # the far plane now holds MINUS the gradient
             a, b = _fly_adjoint(op, far, probe, sc, psi, want_psi, want_probe)
@@ -971,19 +995,23 @@ class _Minibatch:
 
     on_device = False
 
-    def __init__(self, op, comm, data, psi, scan, probe, lo, hi, cm, fly):
+    def __init__(self, op, comm, data, psi, scan, probe, lo, hi, cm, fly,
+                 binning=1):
         self.where = (op, comm, data), scan, (lo, hi)
         self.finish = lambda total: _finish_cost(total, comm, op, lo, hi, fly)
         if psi.shape[0] > 1:  # (every evaluation splits into the same chunks)
             self.run = _multislice_cost_and_grad
             self.how = dict(cm=cm, chunk=_multislice_chunk(op, psi, probe))
-        elif fly > 1:
+        elif fly > 1 or binning > 1:
             if lo % fly or hi % fly:
                 raise ValueError(
                     f"minibatch [{lo}, {hi}) does not hold whole frames of "
                     f"fly={fly} positions")
             global_count(comm, op, lo, hi)  # (all-reduced ahead of the passes)
-            self.run, self.how = _fly_cost_and_grad, dict(cm=cm, fly=fly)
+            self.run = _fly_cost_and_grad
+            self.how = dict(cm=cm, fly=fly)
+            if binning > 1:
+                self.how["binning"] = binning
         else:
             self.plan = _CostPlan(op, data, psi, scan, probe, lo, hi, cm)
             self.run = _cost_and_grad
@@ -1051,12 +1079,15 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
     saw the old positions, as in lstsq_grad and rpie)."""
     o = parameters.algorithm_options
     fly = _fly_of(op, data, parameters.scan)
-    _refuse(parameters, fly)
+    binning = int(getattr(op, "binning", 1))
+    _refuse(parameters, fly, binning=binning)
     recover = (parameters.object_options is not None,
                parameters.probe_options is not None
                and epoch >= parameters.probe_options.update_start)
     psi, probe, scan = parameters.psi, parameters.probe, parameters.scan
-    cm = _cost_model(parameters.exitwave_options, op.detector_shape)
+    # (the mask and the pixel count are at data resolution)
+    cm = _cost_model(parameters.exitwave_options,
+                     op.detector_shape // binning)
     position_options = parameters.position_options  # (plain minibatches only)
     positions = None
     if position_options is not None:
@@ -1073,7 +1104,8 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
         lo = int(b[0]) if len(b) else 0
         hi = lo + len(b)
         comm.minibatch = batch_index
-        mb = _Minibatch(op, comm, data, psi, scan, probe, lo, hi, cm, fly)
+        mb = _Minibatch(op, comm, data, psi, scan, probe, lo, hi, cm, fly,
+                        binning)
         if positions is not None:
             positions.pending = True
             # the object's first gradient pass writes the projection the sums
