@@ -1535,6 +1535,87 @@ int tike_binned_cost_factor(const void* farplane, const void* data, int data_u16
                             int model, long num_measured, int det, int binning,
                             void* stream);
 
+/* ---- a fitted incoherent background per detector pixel (no reference
+ * counterpart; tike_amd.ptycho.BackgroundOptions, tike_amd.autograd.cost(
+ * background=)): air scatter, fluorescence and dark current add a count
+ * b[p] >= 0 to every frame that does not move with the scan,
+ *   I_model[f][p] = sum_{j<fly*S} |farplane[f][j][p]|^2 + b[p].
+ * background (det,det) f32 in the stored (FFT-shifted) layout of the data.
+ * The three entries below use the terms and factors of
+ * tike_fly_farplane_gradient at Ib = I + b[p]: I the float32 running sum over
+ * the planes in ascending order (the bits of tike_intensity), then ONE float32
+ * add.  A background value at an unmeasured pixel may be NaN, like a count
+ * there: it is selected away, never multiplied. */
+
+/* tike_fly_farplane_gradient with the background added (the same kernel
+ * body): costs and the factor the far plane is multiplied by are taken at Ib,
+ *   -(1 - sqrt(d)/(sqrt(Ib)+1e-9)) or -(1 - d/(Ib+1e-9))   on measured pixels,
+ *   unmeasured_scaling - 1                                  elsewhere;
+ * intensity, if not NULL, receives I WITHOUT b (what tike_background_sums
+ * takes), the bits tike_fly_farplane_gradient writes.  Every other argument,
+ * the one workgroup per frame, the 16-byte far-plane accesses, the planes in
+ * registers up to fly*S = 16 and the second read beyond, the last npix % 4
+ * pixels one per lane and the fixed order of the float64 cost sum are those of
+ * tike_fly_farplane_gradient; det^2 4 bytes of background more are read per
+ * frame (from cache after the first).  background == NULL forwards to
+ * tike_fly_farplane_gradient: the same launch, the same bits.  No atomics: two
+ * calls give the same bits.  No allocation.  TIKE_ERR_ARG for whatever
+ * tike_fly_farplane_gradient refuses; nframe == 0 returns 0 without a launch. */
+int tike_background_farplane_gradient(void* farplane, const void* data, int data_u16,
+                                      const unsigned char* measured, const float* background,
+                                      float* intensity, float* costs, int nframe, int fly,
+                                      int S, int det, int model, int apply_gradient,
+                                      float unmeasured_scaling, long num_measured,
+                                      void* stream);
+
+/* tike_cost_factor at Ib (the same kernel body; background (npix) f32):
+ *   costs[f]    the bits of tike_background_farplane_gradient's costs on the
+ *               same far plane                                   (unless NULL)
+ *   table[f][p] = upstream[f] l'(Ib, d) / num_measured  p measured (unless NULL)
+ *               = 0 exactly                              p unmeasured
+ * d cost / d I = d cost / d b, so the table serves tike_ifft2_crop_scaled,
+ * tike_ifft2_pass1_scaled and tike_farplane_scale unchanged, and its sum over
+ * the frames is the gradient with respect to b.  background == NULL forwards
+ * to tike_cost_factor.  No atomics: two calls give the same bits.  No
+ * allocation.  TIKE_ERR_ARG for whatever tike_cost_factor refuses;
+ * nframe == 0 returns 0 without a launch. */
+int tike_background_cost_factor(const void* farplane, const void* data, int data_u16,
+                                const unsigned char* measured, const float* background,
+                                const float* upstream, float* costs, float* table,
+                                long nframe, int P, long npix, int model, long num_measured,
+                                void* stream);
+
+/* The length of tike_background_sums' `partials` for npix pixels (host only:
+ * no device, no allocation); 0 for npix < 1. */
+int tike_background_sums_partials(long npix);
+
+/* Cost and gradient with respect to the background on STORED intensities: I
+ * does not depend on b, so an optimiser of b needs no forward operator.
+ * intensity (nframe,npix) f32 as tike_background_farplane_gradient writes it;
+ * data (nframe,npix) f32, or u16 with data_u16; measured (npix) u8 or NULL;
+ * background (npix) f32; upstream (nframe) f32 or NULL (ones).
+ *   bgrad[p]  = sum_f upstream[f] l'(I[f][p] + b[p], d[f][p]) / num_measured
+ *               on measured pixels, 0 exactly elsewhere       (npix f32, unless NULL)
+ *   partials  float64, tike_background_sums_partials(npix) of them: their sum
+ *               (the caller adds them in order) is
+ *               sum_f upstream[f] sum_{p measured} term(Ib, d) / num_measured
+ *                                                             (unless NULL)
+ * The products of bgrad are float32 -- upstream[f] / num_measured rounded
+ * once, times l': the table of tike_background_cost_factor -- and their sum
+ * over the frames is float64 in ascending f, rounded once.  A lane owns four
+ * consecutive pixels (16-byte loads; the last npix % 4 pixels one per lane)
+ * and walks the frames, one wave per workgroup, so no sum crosses lanes but
+ * the cost: one partial per workgroup, summed over its lanes in a fixed order.
+ * No atomics: two calls give the same bits.  No allocation.  It reads
+ * nframe npix (4 + 4 or 2) bytes once, the mask and b once per workgroup.
+ * TIKE_ERR_ARG for a NULL intensity, data or background, npix < 1,
+ * num_measured < 1, a model other than 0 or 1 or nframe < 0; nframe == 0
+ * returns 0 without a launch (the outputs are left as they are). */
+int tike_background_sums(const float* intensity, const void* data, int data_u16,
+                         const unsigned char* measured, const float* background,
+                         const float* upstream, double* partials, float* bgrad, long nframe,
+                         long npix, int model, long num_measured, void* stream);
+
 /* ==== the difference map (tike_amd/ptycho/solvers/dm.py; Thibault et al.
  * 2008 / 2009; no reference counterpart): the two ends of its exit-wave step.
  * The solver keeps one exit wave per position and mode, waves (nscan,S,pw,pw)

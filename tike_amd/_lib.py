@@ -212,6 +212,13 @@ _PROTOTYPES = {
                                       _i, _i, _i, _f, _l, _p],
     "tike_binned_cost_factor": [_p, _p, _i, _p, _p, _p, _p, _l, _i, _l, _i, _l,
                                 _i, _i, _p],
+    "tike_background_farplane_gradient": [_p, _p, _i, _p, _p, _p, _p, _i, _i,
+                                          _i, _i, _i, _i, _f, _l, _p],
+    "tike_background_cost_factor": [_p, _p, _i, _p, _p, _p, _p, _p, _l, _i, _l,
+                                    _i, _l, _p],
+    "tike_background_sums_partials": [_l],
+    "tike_background_sums": [_p, _p, _i, _p, _p, _p, _p, _p, _l, _l, _i, _l,
+                             _p],
     "tike_dm_reflect": [_p, _p, _p, _p, _p, _f, _l, _i, _i, _i, _i, _i, _p],
     "tike_dm_update": [_p, _p, _p, _p, _p, _f, _p, _l, _i, _i, _i, _i, _i, _p],
     "tike_comm_unique_id": [_p],

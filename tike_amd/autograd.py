@@ -1531,17 +1531,33 @@ class _Counts:
     """The counts, the mask and the noise model of one call, and the two
     entries on a chunk's far plane."""
 
-    def __init__(self, data, mask, num_measured, model, fly, binning=1):
+    def __init__(self, data, mask, num_measured, model, fly, binning=1,
+                 background=None):
         self.data, self.mask, self.nm = data, mask, num_measured
         self.model, self.fly, self.binning = model, fly, binning
+        # (det, det) float32, detached: the factors are taken at I + background
+        self.background = background
         self.u16 = int(data.dtype == torch.uint16)
 
     def factor(self, lo, hi, far, upstream, costs, table):
         """tike_cost_factor on the frames of the positions lo ... hi - 1;
         with binning > 1 tike_binned_cost_factor: counts and mask at data
-        resolution, the table at the far plane's."""
+        resolution, the table at the far plane's; with a background
+        tike_background_cost_factor."""
         fly = self.fly
         flo, nf = lo // fly, (hi - lo) // fly
+        if self.background is not None:
+            check(
+                lib.tike_background_cost_factor(
+                    A.ptr(far), A.ptr(self.data[flo:]), self.u16,
+                    A.ptr(self.mask), A.ptr(self.background),
+                    None if upstream is None else A.ptr(upstream[flo:]),
+                    None if costs is None else A.ptr(costs[flo:]),
+                    A.ptr(table), nf, far.shape[-3] * fly,
+                    far.shape[-1] * far.shape[-2], self.model, self.nm,
+                    A.stream_ptr()),
+                "cost (tike_background_cost_factor)")
+            return
         if self.binning > 1:
             check(
                 lib.tike_binned_cost_factor(
@@ -1584,26 +1600,34 @@ class _Counts:
             "cost (tike_cost_curvature)")
 
 
-def _cost_forward(op, counts, psi, probe, scan, eigen, weights):
-    """(frames,) costs: per chunk the form's forward and tike_cost_factor."""
-    fly = counts.fly
+def _cost_far_chunks(op, fly, psi, probe, scan, eigen, weights):
+    """(lo, hi, far plane of the positions lo ... hi - 1) per chunk of whole
+    frames, by the form's forward."""
     N, S, det = scan.shape[0], probe.shape[2], op.detector_shape
-    A.current_device()  # (hands the library its deterministic-mode scratch)
-    costs = torch.empty(N // fly, dtype=torch.float32, device=psi.device)
     if N == 0:
-        return costs
+        return
     if psi.shape[0] > 1:
         for lo, hi, far, beams in _SlicesForward(op, fly, psi, probe, scan):
             del beams  # (general route: only the far plane is kept)
-            counts.factor(lo, hi, far, None, costs, None)
-        return costs
+            yield lo, hi, far
+        return
     chunk = _chunk_rows(op, probe, fly)
     far_all = torch.empty((min(chunk, N), 1, S, det, det),
                           dtype=torch.complex64, device=psi.device)
     for lo in range(0, N, chunk):
         hi = min(N, lo + chunk)
-        far = _one_slice_far(op, psi, probe, scan, eigen, weights, lo, hi,
-                             far_all)
+        yield lo, hi, _one_slice_far(op, psi, probe, scan, eigen, weights, lo,
+                                     hi, far_all)
+
+
+def _cost_forward(op, counts, psi, probe, scan, eigen, weights):
+    """(frames,) costs: per chunk the form's forward and tike_cost_factor."""
+    fly = counts.fly
+    A.current_device()  # (hands the library its deterministic-mode scratch)
+    costs = torch.empty(scan.shape[0] // fly, dtype=torch.float32,
+                        device=psi.device)
+    for lo, hi, far in _cost_far_chunks(op, fly, psi, probe, scan, eigen,
+                                        weights):
         counts.factor(lo, hi, far, None, costs, None)
     return costs
 
@@ -1615,7 +1639,8 @@ class _Cost(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, psi, probe, scan, eigen_probe, eigen_weights, operator,
-                counts):
+                counts, background):
+        # (background: `counts` holds it detached; here for its gradient)
         psi, probe, scan = (x.detach().contiguous() for x in (psi, probe, scan))
         eigen = (None if eigen_probe is None else
                  eigen_probe.detach().contiguous())
@@ -1640,6 +1665,11 @@ class _Cost(torch.autograd.Function):
         g = g.to(torch.float32).contiguous()
         A.current_device()  # (hands the library its deterministic-mode scratch)
         tables = {}
+        want_b = counts.background is not None and ctx.needs_input_grad[7]
+        # d cost_f / d b = d cost_f / d I: the sum of the table over the
+        # frames, chunk by chunk in float64, rounded once
+        bsum = (torch.zeros((det, det), dtype=torch.float64,
+                            device=psi.device) if want_b else None)
 
         def table_of(lo, hi, far):
             # one chunk of table, reused: the chain reads it before the next
@@ -1650,21 +1680,32 @@ class _Cost(torch.autograd.Function):
                                           device=psi.device)
             table = tables["t"][:nf]
             counts.factor(lo, hi, far, g, None, table)
+            if want_b:
+                bsum.add_(table.sum(dim=0, dtype=torch.float64))
             return table
 
+        def gb():
+            return bsum.to(torch.float32) if want_b else None
+
         want = tuple(ctx.needs_input_grad[:5])
+        if want_b and not any(want):
+            # the background alone: the tables, no chain behind them
+            for lo, hi, far in _cost_far_chunks(op, fly, psi, probe, scan,
+                                                eigen, weights):
+                table_of(lo, hi, far)
+            return (None,) * 7 + (gb(),)
         if psi.shape[0] > 1:
             grads = _multislice_backward_chunks(op, fly, psi, probe, scan,
                                                 want[:3], table_of)
-            return grads + (None, None, None, None)
+            return grads + (None, None, None, None, gb())
         grads = _backward_chunks(op, fly, psi, probe, scan, want, table_of,
                                  eigen, weights)
-        return grads + (None, None)
+        return grads + (None, None, gb())
 
 
 def cost(operator, data, psi, probe, scan, *, model="gaussian",
          measured_pixels=None, eigen_probe=None, eigen_weights=None, fly=1,
-         binning=1, check_positions=True):
+         binning=1, check_positions=True, background=None):
     """The per-frame cost (N // fly,) float32 of the model's intensity against
     the counts `data` (N // fly, det, det) float32 or uint16 under the
     project's noise models -- "gaussian": mean of (sqrt(I) - sqrt(d))^2,
@@ -1694,6 +1735,15 @@ def cost(operator, data, psi, probe, scan, *, model="gaussian",
     resolution, a bin's value replicated over its pixels, so the backward
     chain is unchanged; no binned or unbinned intensity of all frames exists.
 
+    background: a (det, det) float32 device tensor b, the incoherent
+    background of ptycho.BackgroundOptions in the stored layout of the
+    counts: the costs and every gradient above are taken at I + b
+    (tike_background_cost_factor in the place of tike_cost_factor), and b may
+    require a gradient itself: d cost_f / d b = d cost_f / d I, so b.grad is
+    the sum of the chunks' tables over their frames (float64, rounded once);
+    no tensor of N // fly * det * det elements exists for it either.  A value
+    under the mask may be NaN.  NotImplementedError with binning > 1.
+
     Raises what the form's intensity raises, ValueError for a binning that is
     no integer >= 1 or does not divide the far-plane width, TypeError / ValueError for data
     or measured_pixels of another type, dtype or shape, ValueError for a mask
@@ -1710,8 +1760,37 @@ def cost(operator, data, psi, probe, scan, *, model="gaussian",
     fly, data, mask, nm, model = _checked_cost(
         name, operator, data, measured_pixels, model, psi, probe, scan,
         eigen_probe, eigen_weights, fly, check_positions, checked, binning)
+    b = (None if background is None else
+         _checked_background(name, operator, background, binning))
     return _Cost.apply(psi, probe, scan, eigen_probe, eigen_weights, operator,
-                       _Counts(data, mask, nm, model, fly, binning))
+                       _Counts(data, mask, nm, model, fly, binning, b),
+                       background)
+
+
+def _checked_background(name, operator, background, binning):
+    """The background of `cost`, detached and contiguous, after its
+    refusals."""
+    if binning != 1:
+        raise NotImplementedError(
+            f"{name}: background with binning={binning} is not implemented")
+    det = operator.detector_shape
+    if not isinstance(background, torch.Tensor):
+        raise TypeError(
+            f"{name}: background must be a torch device tensor, not "
+            f"{type(background).__name__}")
+    if background.dtype != torch.float32:
+        raise TypeError(
+            f"{name}: background must be torch.float32, not "
+            f"{background.dtype}")
+    if tuple(background.shape) != (det, det):
+        raise ValueError(
+            f"{name}: background must be ({det}, {det}), not "
+            f"{tuple(background.shape)}")
+    if background.device.type != "cuda":
+        raise TypeError(
+            f"{name}: background lives on {background.device}; tike_amd runs "
+            "on the GPU only and there is no CPU fallback")
+    return background.detach().contiguous()
 
 
 def _refuse_binned_curvature(name, binning):

@@ -21,91 +21,14 @@
 // counts, npix bytes of mask when there is one, npix * 4 bytes of table
 // written; 4 or 8 bytes of costs.  Nothing is read twice.
 #include "../../include/tike_amd.h"
-#include "frame_lanes.h"
-#include "noise_model.h"
+#include "cost_factor_kernel.h"
 
 #include <cmath>
 
 namespace {
 
-constexpr int CT_PX = 4;  // pixels of a lane per sweep: two 16-byte far-plane loads
-
-// The layout of fly_farplane_gradient_kernel without its scaling: one
-// workgroup per frame, a lane owns CT_PX consecutive pixels per sweep and walks
-// the P planes (any P; nothing is kept), the last npix % CT_PX pixels one per
-// lane.  The frame's cost is summed as that kernel sums it -- lane, wave
-// shuffles, the four waves through LDS, float64 -- so costs carry its bits.
-// The intensity is the float32 running sum of tike_intensity (planes
-// ascending, each product and each sum rounded): contraction is off in the
-// kernel body so that those bits do not hang on what the compiler fuses (see
-// intensity_tangent_kernel); the noise-model formulas are compiled in
-// noise_model.h exactly as fly.hip compiles them.
-template <int MODEL, bool U16>
-__global__ __launch_bounds__(256) void cost_factor_kernel(
-    const cf* __restrict__ farplane, const void* __restrict__ data_,
-    const unsigned char* __restrict__ mask, const float* __restrict__ upstream,
-    float* __restrict__ costs, float* __restrict__ table, int P, long npix,
-    double inv_nmeasured) {
-#pragma clang fp contract(off)
-  constexpr int PX = CT_PX;
-  __shared__ double red[4];
-  const long n = blockIdx.x;
-  const cf* __restrict__ F = farplane + n * P * npix;
-  const void* __restrict__ data =
-      U16 ? (const void*)((const unsigned short*)data_ + n * npix)
-          : (const void*)((const float*)data_ + n * npix);
-  // upstream / num_measured, rounded once
-  const float up = (float)((upstream != nullptr ? (double)upstream[n] : 1.0) * inv_nmeasured);
-  float* __restrict__ T = table != nullptr ? table + n * npix : nullptr;
-  double cost = 0.;
-  const long nvec = npix / PX;
-  for (long v = threadIdx.x; v < nvec; v += blockDim.x) {
-    const long p = v * PX;
-    // the counts and the mask are requested with the planes, not behind them
-    float d[PX];
-    tk_counts4<U16>(data, p, d);
-    bool measured[PX] = {true, true, true, true};
-    if (mask != nullptr) tk_mask4(mask, p, measured);
-    float I[PX] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-    for (int j = 0; j < P; ++j) {
-      const cf* at = F + j * npix + p;
-      const tk_f4a8 a = *reinterpret_cast<const tk_f4a8*>(at);
-      const tk_f4a8 b = *reinterpret_cast<const tk_f4a8*>(at + 2);
-      I[0] += a.x * a.x + a.y * a.y;
-      I[1] += a.z * a.z + a.w * a.w;
-      I[2] += b.x * b.x + b.y * b.y;
-      I[3] += b.z * b.z + b.w * b.w;
-    }
-    tk_f4a4 o;
-#pragma unroll
-    for (int k = 0; k < PX; ++k) {
-      float term;
-      const float lp = tk_noise_pixel<MODEL>(I[k], d[k], term);
-      cost += measured[k] ? (double)term : 0.0;
-      o[k] = measured[k] ? up * lp : 0.0f;
-    }
-    if (T != nullptr) *reinterpret_cast<tk_f4a4*>(T + p) = o;
-  }
-  // scalar tail: fewer than CT_PX pixels, one per lane
-  for (long p = nvec * PX + threadIdx.x; p < npix; p += blockDim.x) {
-    const float dv = U16 ? (float)((const unsigned short*)data)[p] : ((const float*)data)[p];
-    const bool measured = mask != nullptr ? mask[p] != 0 : true;
-    float I = 0.f;
-    for (int j = 0; j < P; ++j) {
-      const cf a = F[j * npix + p];
-      I += a.x * a.x + a.y * a.y;
-    }
-    float term;
-    const float lp = tk_noise_pixel<MODEL>(I, dv, term);
-    cost += measured ? (double)term : 0.0;
-    if (T != nullptr) T[p] = measured ? up * lp : 0.0f;
-  }
-  if (costs != nullptr) {
-    cost = tk_frame_sum_f64(cost, red);
-    if (threadIdx.x == 0) costs[n] = (float)(cost * inv_nmeasured);
-  }
-}
+// cost_factor_kernel and CT_PX are in cost_factor_kernel.h (shared with
+// background.hip).
 
 // The same layout over a far plane and its tangent.  dI is the float32 running
 // sum of tike_intensity_tangent, doubled; without counts (data NULL: neither
@@ -219,9 +142,10 @@ extern "C" int tike_cost_factor(const void* farplane, const void* data, int data
   TK_CHECK_ARG(nframe <= 0x7fffffffL);  // one workgroup per frame: grid.x
   const double inv = 1.0 / (double)num_measured;
   const dim3 grid((unsigned)nframe), block(256);
-#define TK_COST(M, U)                                                                    \
-  hipLaunchKernelGGL((cost_factor_kernel<M, U>), grid, block, 0, stream, (const cf*)farplane, \
-                     data, measured, upstream, costs, table, P, npix, inv)
+#define TK_COST(M, U)                                                                      \
+  hipLaunchKernelGGL((cost_factor_kernel<M, U, false>), grid, block, 0, stream,           \
+                     (const cf*)farplane, data, measured, upstream, costs, table, P, npix, \
+                     inv, (const float*)nullptr)
   if (model == 0 && data_u16)
     TK_COST(0, true);
   else if (model == 0)

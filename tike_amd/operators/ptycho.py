@@ -271,6 +271,37 @@ class Ptycho(Operator):
                 A.stream_ptr()), "Ptycho.fly_farplane_gradient")
         return farplane
 
+    def background_farplane_gradient(self, farplane, data, fly, background, *,
+                                     model=0, measured=None,
+                                     num_measured=None, intensity=None,
+                                     costs=None, apply_gradient=False,
+                                     unmeasured_scaling=1.0):
+        """`tike_background_farplane_gradient` on device tensors:
+        `fly_farplane_gradient` with an incoherent background (det, det)
+        float32 added to every frame's intensity, in the stored (FFT-shifted)
+        layout of the data.  Costs and the gradient factor are taken at
+        I + background; `intensity` receives I without it.  background None
+        is `fly_farplane_gradient`."""
+        det = self.detector_shape
+        S = farplane.shape[-3]
+        nframe = data.shape[0]
+        assert farplane.shape[0] == nframe * fly, (farplane.shape, nframe, fly)
+        assert tuple(data.shape[1:]) == (det, det), data.shape
+        assert data.dtype in (torch.float32, torch.uint16), data.dtype
+        if background is not None:
+            assert tuple(background.shape) == (det, det), background.shape
+            assert background.dtype == torch.float32, background.dtype
+            assert background.is_contiguous()
+        check(
+            lib.tike_background_farplane_gradient(
+                A.ptr(farplane), A.ptr(data), int(data.dtype == torch.uint16),
+                A.ptr(measured), A.ptr(background), A.ptr(intensity),
+                A.ptr(costs), nframe, int(fly), S, det, int(model),
+                int(bool(apply_gradient)), float(unmeasured_scaling),
+                det * det if num_measured is None else int(num_measured),
+                A.stream_ptr()), "Ptycho.background_farplane_gradient")
+        return farplane
+
     def binned_farplane_gradient(self, farplane, data, fly, binning, *,
                                  model=0, measured=None, num_measured=None,
                                  intensity=None, costs=None,
@@ -313,12 +344,38 @@ class Ptycho(Operator):
                 A.stream_ptr()), "Ptycho.binned_farplane_gradient")
         return farplane
 
-    def _compute_intensity(self, data, psi, scan, probe, fly=1, binning=1):
+    def _device_background(self, background, binning, psi):
+        """The background of `_compute_intensity` and `cost` on the device,
+        after their refusals."""
+        if binning > 1:
+            raise ValueError(
+                "background together with binning > 1 is not supported")
+        if psi.shape[0] > 1:
+            raise ValueError(
+                "background together with several object slices is not "
+                "supported")
+        det = self.detector_shape
+        b = A.to_device(background, np.float32).contiguous()
+        if tuple(b.shape) != (det, det):
+            raise ValueError(
+                f"background must have the detector's shape ({det}, {det}), "
+                f"not {tuple(b.shape)}")
+        return b
+
+    def _compute_intensity(self, data, psi, scan, probe, fly=1, binning=1,
+                           background=None):
         """(intensity (FRAME,det,det), farplane) -- ptycho.py:178-191; with
         fly > 1 a frame is the sum over `fly` consecutive positions
         (ptycho.py:104-125); with binning = B > 1 the intensity is
         (FRAME, det // B, det // B), a pixel the sum over its B x B far-plane
-        pixels (`binned_farplane_gradient`)."""
+        pixels (`binned_farplane_gradient`); with a background (det, det) the
+        intensity includes it."""
+        if background is not None:
+            b = self._device_background(background, binning,
+                                        A.to_device(psi, np.complex64))
+            intensity, far = self._compute_intensity(data, psi, scan, probe,
+                                                     fly=fly)
+            return (A.like_input(A.to_device(intensity) + b, psi), far)
         kind = psi
         far = self.fwd_device(A.to_device(probe, np.complex64),
                               A.to_device(scan, np.float32),
@@ -347,10 +404,16 @@ class Ptycho(Operator):
                                A.stream_ptr()), "Ptycho._compute_intensity")
         return A.like_input(intensity, kind), A.like_input(far, kind)
 
-    def cost(self, data, psi, scan, probe, *, model, fly=1, binning=1):
+    def cost(self, data, psi, scan, probe, *, model, fly=1, binning=1,
+             background=None):
         """ptycho.py:193-204; with fly > 1 or binning > 1 the mean over frames
-        of the cost of each frame's summed (and binned) intensity."""
-        if fly > 1 or binning > 1:
+        of the cost of each frame's summed (and binned) intensity; with a
+        background (det, det) the cost of intensity + background
+        (`background_farplane_gradient`)."""
+        if background is not None:
+            background = self._device_background(
+                background, binning, A.to_device(psi, np.complex64))
+        if fly > 1 or binning > 1 or background is not None:
             if model not in objective._MODELS:
                 raise ValueError(f"unknown noise model {model!r}")
             kind = psi
@@ -366,10 +429,15 @@ class Ptycho(Operator):
                     f"{far.shape[0]} scan positions")
             costs = torch.empty(counts.shape[0], dtype=torch.float32,
                                 device=far.device)
-            self.binned_farplane_gradient(far, counts.contiguous(), fly,
-                                          binning,
-                                          model=objective._MODELS[model],
-                                          costs=costs)
+            if background is not None:
+                self.background_farplane_gradient(
+                    far, counts.contiguous(), fly, background,
+                    model=objective._MODELS[model], costs=costs)
+            else:
+                self.binned_farplane_gradient(far, counts.contiguous(), fly,
+                                              binning,
+                                              model=objective._MODELS[model],
+                                              costs=costs)
             return A.like_input(costs.mean(), kind)
         intensity, _ = self._compute_intensity(data, psi, scan, probe)
         return getattr(objective, model)(data, intensity)

@@ -42,6 +42,7 @@ from .probe import (apply_median_filter_abs_probe, constrain_center_peak,
                     finite_probe_support, get_varying_probe, orthogonalize_eig,
                     power as probe_power,
                     rescale_probe_using_fixed_intensity_photons)
+from . import background as _background
 from .solvers.cgrad import _refuse_binning, _refuse_fly, _refuse_multislice
 from .solvers.dm import refuse as _refuse_dm
 from .solvers.lstsq import chunk_positions, mask_info
@@ -51,11 +52,12 @@ logger = logging.getLogger(__name__)
 
 
 def _intensity_chunks(operator, psi, scan, probe, eigen_probe=None,
-                      eigen_weights=None, fly=1, binning=1):
+                      eigen_weights=None, fly=1, binning=1, background=None):
     """Yield (lo, hi, intensity (n, det, det)) over chunks of frames; frame f
     is the sum over the positions f * fly ... f * fly + fly - 1.  With
     binning = B > 1 the intensity is (n, det // B, det // B), a pixel the sum
-    over its B x B far-plane pixels."""
+    over its B x B far-plane pixels.  background (det, det) float32 or None
+    is added to every frame."""
     N = scan.shape[0]
     S = probe.shape[-3]
     det = operator.detector_shape
@@ -87,17 +89,25 @@ def _intensity_chunks(operator, psi, scan, probe, eigen_probe=None,
             check(
                 lib.tike_intensity(A.ptr(far), A.ptr(inten), hi - lo, S,
                                    det * det, A.stream_ptr()), "intensity")
+        if background is not None:
+            inten += background
         yield lo // fly, hi // fly, inten
 
 
 def simulate(detector_shape, probe, scan, psi, fly=1, eigen_probe=None,
-             eigen_weights=None, binning=1, **kwargs):
+             eigen_weights=None, binning=1, background=None, **kwargs):
     """Real-valued detector counts of simulated ptychography data
     (ptycho.py:128-179).  Returns (FRAME, det, det) float32 on the host.
     binning = B > 1: `detector_shape` stays the far-plane width, a measured
     pixel is the sum over its B x B far-plane pixels, and the result is
-    (FRAME, det // B, det // B)."""
+    (FRAME, det // B, det // B).  background: a (det, det) float32
+    incoherent background >= 0, in the stored layout of the frames, added to
+    every frame."""
     binning = _checked_binning(binning, int(detector_shape))
+    if background is not None:
+        background = _checked_simulated_background(
+            background, int(detector_shape), binning, psi, eigen_probe,
+            eigen_weights)
     check_allowed_positions(scan, psi, probe.shape)
     real, cplx = precision.floating, precision.cfloating
     wanted = ((psi, cplx), (scan, real), (probe, cplx), (eigen_probe, cplx),
@@ -109,12 +119,37 @@ def simulate(detector_shape, probe, scan, psi, fly=1, eigen_probe=None,
         # (`fly` consecutive positions expose one frame: summed by the kernel)
         frames = torch.cat([
             inten for _, _, inten in _intensity_chunks(
-                operator, *resident, fly=int(fly), binning=binning)])
+                operator, *resident, fly=int(fly), binning=binning,
+                background=None if background is None else operator.asarray(
+                    background, dtype=real))])
         return operator.asnumpy(frames)
 
 
+def _checked_simulated_background(background, det, binning, psi, eigen_probe,
+                                  eigen_weights):
+    """The background of `simulate` as a host array, after its refusals."""
+    if binning > 1:
+        raise NotImplementedError(
+            f"background with binning={binning} is not implemented")
+    if psi.shape[0] > 1:
+        raise NotImplementedError(
+            f"background with several slices (psi.shape[0] = {psi.shape[0]}) "
+            "is not implemented")
+    if eigen_probe is not None or eigen_weights is not None:
+        raise NotImplementedError(
+            "background with eigen probes is not implemented")
+    b = np.asarray(A.to_host(background), dtype=np.float32)
+    if b.shape != (det, det):
+        raise ValueError(
+            f"background has shape {b.shape}; expected the detector's "
+            f"({det}, {det})")
+    if not np.all(np.isfinite(b)) or np.any(b < 0):
+        raise ValueError("background must be finite and >= 0")
+    return b
+
+
 def reconstruct(data, parameters, num_gpu=None, use_mpi=False, *, fly=1,
-                binning=1, **kwargs):
+                binning=1, background_options=None, **kwargs):
     """Solve the ptychography problem (ptycho.py:182-262).
 
     data (FRAME, WIDE, HIGH): measured intensities, FFT-shifted so that the
@@ -140,6 +175,11 @@ def reconstruct(data, parameters, num_gpu=None, use_mpi=False, *, fly=1,
     model pixels (what `simulate(..., binning=B)` produces): the probe window
     may then be up to B times as wide as the data.  cgrad alone reconstructs
     such data.
+
+    background_options (keyword only): a `BackgroundOptions`; cgrad then
+    models every pattern as the coherent intensity plus a non-negative
+    background per detector pixel and, unless told otherwise, fits it.  The
+    fitted background is left in `background_options.background`.
     """
     if use_mpi:
         raise NotImplementedError(
@@ -160,12 +200,19 @@ def reconstruct(data, parameters, num_gpu=None, use_mpi=False, *, fly=1,
             f"fly={fly} with reconstruct(num_gpu={num_gpu!r}) from a plain "
             "process: the ranks this call would start do not take fly-scan "
             "data; launch one process per GPU with torchrun instead")
+    if (background_options is not None and requested is not None
+            and len(requested) > 1 and _spawn.world_size() == 1):
+        raise NotImplementedError(
+            f"background_options with reconstruct(num_gpu={num_gpu!r}) from "
+            "a plain process: the ranks this call would start do not fit a "
+            "background")
     how, where = _spawn.resolve(num_gpu)
     if how == "spawn":
         return _spawn.reconstruct_spawned(data, parameters, where, **kwargs)
     with Reconstruction(data, parameters,
                         num_gpu if where is None else (where,),
                         use_mpi, fly=fly, binning=binning,
+                        background_options=background_options,
                         **kwargs) as context:
         context.iterate(parameters.algorithm_options.num_iter)
         result = context.get_result()
@@ -430,6 +477,13 @@ class Reconstruction():
         model pixels (`simulate(..., binning=B)`), `measured_pixels` stays at
         data resolution, and the solver must be cgrad with a shared probe,
         one slice and no position correction, in one process.
+      background_options: a `BackgroundOptions` (default None).  Every
+        pattern is then modelled as the coherent intensity plus a
+        non-negative background per detector pixel, which cgrad fits in a
+        third conjugate-gradient block per minibatch; the solver must be
+        cgrad with a shared probe, one slice, no binning, no position
+        correction and HBM-resident data, in one process.  `get_result()`
+        leaves the fitted background in `background_options.background`.
     """
 
     fly = 1  # scan positions per diffraction pattern
@@ -438,7 +492,7 @@ class Reconstruction():
     def __init__(self, data, parameters, num_gpu=None, use_mpi=False, *,
                  presharded=False, order=None, batches=None,
                  spatial_sort=True, data_on_host=False, local_data=None,
-                 fly=1, binning=1):
+                 fly=1, binning=1, background_options=None):
         # a context lives in ONE process with ONE GPU: `num_gpu` must agree
         # with the process group it runs in (`reconstruct` is the entry that
         # starts ranks by itself)
@@ -470,6 +524,12 @@ class Reconstruction():
             raise NotImplementedError(
                 f"fly={fly} with local_data (the ranks started by "
                 "reconstruct(num_gpu=N)) is not implemented")
+        background = None
+        if background_options is not None:
+            background = _background.refuse(
+                background_options, parameters, data.shape[-1], fly=fly,
+                binning=binning, data_on_host=data_on_host,
+                local_data=local_data, world_size=_spawn.world_size())
         name = parameters.algorithm_options.name
         if not hasattr(solvers, name):
             raise NotImplementedError(
@@ -520,6 +580,10 @@ class Reconstruction():
         )
         self.operator.fly = fly  # (a rank without a frame reads it: cgrad)
         self.operator.binning = binning  # (cgrad reads it)
+        # (cgrad reads it; on the device from the first epoch on)
+        self._background = (None if background is None else
+                            (background_options, background))
+        self.operator.background = None
         self.comm = Comm()
         self._pending_fits = []  # futures of deferred affine position fits
         self._free_snaps = []  # pinned host buffers of finished fits
@@ -615,6 +679,8 @@ class Reconstruction():
         return self._finish_enter()
 
     def _finish_enter(self):
+        if self._background is not None:
+            self.operator.background = _background.State(*self._background)
         self.parameters = solvers.PtychoParameters.split(
             self.local_order,
             x=self._host_parameters()).copy_to_device()
@@ -849,6 +915,8 @@ class Reconstruction():
             g = self._gather_positions
             p.position_options = po._like(g(po.initial_scan),
                                           g(po.confidence), g(po._momentum))
+        if self.operator.background is not None:
+            self.operator.background.write_back()
         return p
 
     def get_convergence(self):

@@ -43,6 +43,15 @@ no variable is recovered, one cost-only evaluation.
   pixels; no reference counterpart): the fly-scan route at any ``fly``, also
   1, with ``tike_binned_farplane_gradient`` in that kernel's place; the mask
   and the pixel count are at data resolution.
+* a fitted background (the operator's ``background`` state, set by
+  ``background_options``; no reference counterpart): every pattern is the
+  coherent intensity plus b = a * a per detector pixel.  The fly-scan route
+  at any ``fly``, also 1, with ``tike_background_farplane_gradient`` in that
+  kernel's place, and a THIRD conjugate-gradient call per minibatch, on a
+  (real), after the object's and the probe's.  The intensity does not depend
+  on b: that call forms the minibatch's intensities once (``_Intensities``)
+  and every gradient and line-search trial is then one
+  ``tike_background_sums`` launch -- no forward operator, no transform.
 * objects of several slices (``psi.shape[0] > 1``, probe window = detector):
   the same cost on the far field behind the last slice, e_d = patch(O_d) x
   beam_d, beam_{d+1} = Fresnel(e_d), and its EXACT gradient -- the adjoint
@@ -797,8 +806,43 @@ def _fly_adjoint(op, far, probe, scan, psi, want_psi, want_probe):
     return psi_adj, probe_adj
 
 
+class _Intensities:
+    """The intensities (frames, det, det) float32, WITHOUT the background, of
+    a minibatch at the current object and probe: formed once, by the first
+    evaluation of the background block, in a workspace that the other two
+    blocks do not touch."""
+
+    def __init__(self):
+        self.values = None
+
+
+def _background_cost_and_grad(op, data, lo, hi, fly, a, *, want_grad, cm,
+                              stored):
+    """(sum of the per-frame costs at b = a * a, a device scalar; d / d a of
+    that sum = 2 a bgrad, or None) of the frames [lo / fly, hi / fly) from
+    their stored intensities: one `tike_background_sums` launch."""
+    det = op.detector_shape
+    npix = det * det
+    dev = a.device
+    d = data[lo // fly:hi // fly]
+    if d.dtype not in (torch.float32, torch.uint16):
+        d = d.to(torch.float32)
+    b = (a * a).contiguous()
+    partials = torch.zeros(lib.tike_background_sums_partials(npix),
+                           dtype=torch.float64, device=dev)
+    bgrad = torch.empty_like(b) if want_grad else None
+    check(
+        lib.tike_background_sums(
+            A.ptr(stored.values), A.ptr(d), int(d.dtype == torch.uint16),
+            A.ptr(cm.mask), A.ptr(b), None, A.ptr(partials), A.ptr(bgrad),
+            d.shape[0], npix, cm.model, cm.nmeasured, A.stream_ptr()),
+        "cgrad background sums")
+    return partials.sum(), (2 * a * bgrad if want_grad else None)
+
+
 def _fly_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, fly, *,
-                       want_psi, want_probe, want_grad, cm, binning=1):
+                       want_psi, want_probe, want_grad, cm, binning=1,
+                       background=None, stored=None):
     """(sum of this rank's per-frame costs, a device scalar; d cost / d psi or
     None; d cost / d probe or None -- unnormalised adjoints summed over the
     ranks) of the positions [lo, hi), whole frames: the data rows
@@ -807,7 +851,11 @@ def _fly_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, fly, *,
     plane is read once and not written) and, for a gradient, the adjoint of
     the far plane it left.  binning > 1 (any fly): the data rows and the mask
     are `binning` times coarser than the far plane and
-    `tike_binned_farplane_gradient` stands in that kernel's place."""
+    `tike_binned_farplane_gradient` stands in that kernel's place.
+    background (det, det) float32: costs and gradients at intensity +
+    background, `tike_background_farplane_gradient` in that kernel's place.
+    stored (with background, cost only): the `_Intensities` that receive the
+    frames' intensities without the background."""
     assert lo % fly == 0 and hi % fly == 0, (lo, hi, fly)
     dev = psi.device
     S, det = probe.shape[-3], op.detector_shape
@@ -819,6 +867,10 @@ def _fly_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, fly, *,
     costs = ws.get("costs", (max(N // fly, 1),), torch.float32, dev)[:N // fly]
     grads, gpsi, gprobe = _gradient_buffer(
         psi, probe, want_grad and want_psi, want_grad and want_probe)
+    if stored is not None:
+        stored.values = ws.get("background_intensity",
+                               (max(N // fly, 1), det, det), torch.float32,
+                               dev)[:N // fly]
     for clo in range(lo, hi, chunk):
         chi = min(hi, clo + chunk)
         sc = scan[clo:chi]
@@ -831,7 +883,12 @@ def _fly_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, fly, *,
                    num_measured=cm.nmeasured,
                    costs=costs[(clo - lo) // fly:(chi - lo) // fly],
                    apply_gradient=want_grad)
-        if binning > 1:
+        if background is not None:
+            if stored is not None:
+                how["intensity"] = stored.values[(clo - lo) // fly:
+                                                 (chi - lo) // fly]
+            op.background_farplane_gradient(far, d, fly, background, **how)
+        elif binning > 1:
             op.binned_farplane_gradient(far, d, fly, binning, **how)
         else:
             op.fly_farplane_gradient(far, d, fly, **how)
@@ -977,13 +1034,16 @@ def _multislice_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, *,
 
 class _Minibatch:
     """The cost of the positions [lo, hi) of this rank -- all that the epoch
-    loop and `_host_cg` know of a minibatch, whichever of the three kinds
-    (module docstring) it is.
+    loop and `_host_cg` know of a minibatch, whichever of the kinds (module
+    docstring) it is.
 
-    evaluate(psi, probe, variable, want_grad, position_terms=None) ->
+    evaluate(psi, probe, variable, want_grad, position_terms=None, a=None) ->
         (this rank's cost sum, a device float64 scalar; with want_grad MINUS
         d cost / d variable -- the unnormalised adjoint, summed over the ranks
-        -- else None).  variable: 0 the object, 1 the probe, None cost only.
+        -- else None).  variable: 0 the object, 1 the probe, 2 the root a of
+        the background (minibatches with a background only; `a` is then the
+        point of evaluation, psi and probe those of the block's start), None
+        cost only.
         position_terms: plain minibatches only, see `_cost_and_grad`.
     finish(total) -> the mean cost over all ranks, a host float: the one
         read-back of an evaluation.
@@ -996,13 +1056,15 @@ class _Minibatch:
     on_device = False
 
     def __init__(self, op, comm, data, psi, scan, probe, lo, hi, cm, fly,
-                 binning=1):
+                 binning=1, background=None):
         self.where = (op, comm, data), scan, (lo, hi)
+        self.background = background  # the `State` of ptycho/background.py
+        self.stored = None  # `_Intensities` of the background block
         self.finish = lambda total: _finish_cost(total, comm, op, lo, hi, fly)
         if psi.shape[0] > 1:  # (every evaluation splits into the same chunks)
             self.run = _multislice_cost_and_grad
             self.how = dict(cm=cm, chunk=_multislice_chunk(op, psi, probe))
-        elif fly > 1 or binning > 1:
+        elif fly > 1 or binning > 1 or background is not None:
             if lo % fly or hi % fly:
                 raise ValueError(
                     f"minibatch [{lo}, {hi}) does not hold whole frames of "
@@ -1030,18 +1092,34 @@ class _Minibatch:
                                                   self.on_device))
             self.count = global_count(comm, op, lo, hi)
 
-    def evaluate(self, psi, probe, variable, want_grad, position_terms=None):
+    def evaluate(self, psi, probe, variable, want_grad, position_terms=None,
+                 a=None):
         args, scan, span = self.where
         how = self.how if position_terms is None else dict(
             self.how, position_terms=position_terms)
+        if variable == 2:
+            if self.stored is None:
+                # the intensities at the block's object and probe, once
+                self.stored = _Intensities()
+                self.run(*args, psi, scan, probe, *span, want_psi=False,
+                         want_probe=False, want_grad=False,
+                         background=self.background.b, stored=self.stored,
+                         **how)
+            return _background_cost_and_grad(
+                args[0], args[2], *span, how["fly"], a, want_grad=want_grad,
+                cm=how["cm"], stored=self.stored)
+        if self.background is not None:
+            how = dict(how, background=self.background.b)
         r = self.run(*args, psi, scan, probe, *span, want_psi=variable == 0,
                      want_probe=variable == 1, want_grad=want_grad, **how)
         return r[0], None if variable is None else r[1 + variable]
 
 
 def _host_cg(minibatch, psi, probe, variable, o, positions=None):
-    """`opt.conjugate_gradient` on the object (variable 0) or the probe (1)
-    of one minibatch, every line search decided on the host: (x, mean cost).
+    """`opt.conjugate_gradient` on the object (variable 0), the probe (1) or
+    the root of the background (2: real float32, the minibatch's
+    `background.a`) of one minibatch, every line search decided on the host:
+    (x, mean cost).
     positions: the `_PositionTerms` of the epoch; the first gradient pass
     takes the minibatch's sums if they are still owed.
 
@@ -1054,9 +1132,10 @@ def _host_cg(minibatch, psi, probe, variable, o, positions=None):
 
     def run(x, want_grad):
         return minibatch.evaluate(
-            x if variable == 0 else psi, probe if variable == 0 else x,
+            x if variable == 0 else psi, x if variable == 1 else probe,
             variable, want_grad,
-            positions.take() if want_grad and positions is not None else None)
+            positions.take() if want_grad and positions is not None else None,
+            **(dict(a=x) if variable == 2 else {}))
 
     def cost(x):
         return minibatch.finish(last[1] if x is last[0] else run(x, False)[0])
@@ -1067,23 +1146,29 @@ def _host_cg(minibatch, psi, probe, variable, o, positions=None):
         return [g]
 
     return opt.conjugate_gradient(
-        torch, x=(psi, probe)[variable], cost_function=cost, grad=grad,
+        torch, x=(psi, probe, getattr(minibatch.background, "a",
+                                      None))[variable],
+        cost_function=cost, grad=grad,
         dir_multi=lambda x: x[0], num_iter=o.cg_iter,
         step_length=o.step_length)
 
 
 def cgrad(parameters, data, batches, comm, *, op, epoch):
-    """One epoch: for every minibatch, `cg_iter` CG iterations on psi and
-    then (when probe recovery is on) on the probe; with position_options, one
+    """One epoch: for every minibatch, `cg_iter` CG iterations on psi, then
+    (when probe recovery is on) on the probe and then (with a background that
+    is fitted) on the root of the background; with position_options, one
     position update after the last minibatch (every minibatch of the epoch
     saw the old positions, as in lstsq_grad and rpie)."""
     o = parameters.algorithm_options
     fly = _fly_of(op, data, parameters.scan)
     binning = int(getattr(op, "binning", 1))
     _refuse(parameters, fly, binning=binning)
+    background = getattr(op, "background", None)
     recover = (parameters.object_options is not None,
                parameters.probe_options is not None
-               and epoch >= parameters.probe_options.update_start)
+               and epoch >= parameters.probe_options.update_start,
+               background is not None and bool(background.options.update)
+               and epoch >= background.options.update_start)
     psi, probe, scan = parameters.psi, parameters.probe, parameters.scan
     # (the mask and the pixel count are at data resolution)
     cm = _cost_model(parameters.exitwave_options,
@@ -1105,7 +1190,7 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
         hi = lo + len(b)
         comm.minibatch = batch_index
         mb = _Minibatch(op, comm, data, psi, scan, probe, lo, hi, cm, fly,
-                        binning)
+                        binning, background)
         if positions is not None:
             positions.pending = True
             # the object's first gradient pass writes the projection the sums
@@ -1116,7 +1201,8 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
                     and not (mb.on_device and USE_GRAPHS)):
                 mb.evaluate(psi, probe, None, True, positions.take())
         cost = None
-        for variable in (0, 1):  # CG on the object, then on the probe
+        # CG on the object, then on the probe, then on the background's root
+        for variable in (0, 1, 2):
             if not recover[variable]:
                 continue
             owed = positions if variable == 0 else None
@@ -1128,6 +1214,9 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
             if r is None:
                 r = _host_cg(mb, psi, probe, variable, o, owed)
             x, cost = r
+            if variable == 2:
+                background.set(x)
+                continue
             psi, probe = (x, probe) if variable == 0 else (psi, x)
         if cost is None:  # no variable recovered: the cost alone
             cost = mb.finish(mb.evaluate(psi, probe, None, False)[0])
