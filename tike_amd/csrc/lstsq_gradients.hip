@@ -96,7 +96,10 @@ __global__ __launch_bounds__(256) void probe_grad_kernel(
           if (out) acc[s] = acc[s] + oc * xs[s];
           if (objproj) {
             cf ps;
-            if (hoist && !(probe.weights != nullptr && probe.eigen != nullptr && s < probe.Sm)) {
+            // (the first Sm modes vary by more than a weight: eigen probes, or
+            // a unique probe passed in their place)
+            if (hoist && !(probe.weights != nullptr && s < probe.Sm &&
+                           (probe.eigen != nullptr || probe.unique != nullptr))) {
               const float w0 =
                   probe.weights ? probe.weights[b * (long)(probe.C + 1) * probe.S + s] : 1.0f;
               ps = pr[s] * w0;
