@@ -1616,6 +1616,92 @@ int tike_background_sums(const float* intensity, const void* data, int data_u16,
                          const float* upstream, double* partials, float* bgrad, long nframe,
                          long npix, int model, long num_measured, void* stream);
 
+/* ---- far-field blur (no reference counterpart; tike_amd.autograd.cost(
+ * blur=), Ptycho.cost / _compute_intensity / simulate(blur=)): a source of
+ * finite size (partial spatial coherence in the Gaussian-Schell approximation)
+ * and the detector's point-spread function both convolve the recorded
+ * intensity with a small non-negative kernel,
+ *   I_model[f] = K (*) I[f],   I[f][p] = sum_{j<fly*S} |farplane[f][j][p]|^2,
+ *   I_model[y][x] = sum_{u,v} K[u][v] I[(y - u + r) mod det][(x - v + r) mod det].
+ * kernel (k,k) f32, k in {3,5,7}, r = k / 2, the centre at [r][r]; the entries
+ * use it as given (the callers keep it non-negative with sum 1).  The
+ * convolution is CYCLIC over the (det,det) plane in the stored (FFT-shifted)
+ * layout of the data; the shift between the stored and the physical layout is
+ * itself cyclic, so this is the physical convolution with the detector's
+ * opposite edges joined.  Both entries work on STORED intensities
+ * (nframe,det,det) f32 -- what tike_fly_farplane_gradient(intensity=,
+ * costs=NULL, apply_gradient=0) or tike_intensity write from one read of the
+ * far plane -- and never touch the far plane.  The terms and factors are those
+ * of tike_fly_farplane_gradient taken at I_model, which is a float32 sum of
+ * the k*k products with the taps in ascending u, then v.  A count at an
+ * unmeasured pixel may be NaN: it is selected away, never multiplied; the
+ * model intensity under the mask still feeds its measured neighbours. */
+
+/* Costs, the table of the backward and the blurred intensity:
+ *   costs[f]      = sum_{p measured} term(I_model, d) / num_measured  (unless NULL)
+ *   table[f][p]   = sum_{u,v} K[u][v] g[f][p + (u - r, v - r) mod det] (unless NULL)
+ *                   g = upstream[f] l'(I_model, d) / num_measured on measured
+ *                   pixels, 0 exactly elsewhere: the cyclic CORRELATION, the
+ *                   adjoint of the blur, so that farplane[f][j][p] table[f][p]
+ *                   is the gradient with respect to the far plane
+ *   blurred[f][p] = I_model                                            (unless NULL)
+ * data (nframe,det,det) f32, or u16 with data_u16 (may be NULL when costs and
+ * table both are); measured (det,det) u8 or NULL (every pixel measured);
+ * upstream (nframe) f32 or NULL (ones); costs (nframe) f32, table and blurred
+ * (nframe,det,det) f32, overwritten.  g is float32: upstream[f] / num_measured
+ * rounded once, times l'; the table is the float32 sum of its k*k products,
+ * taps ascending u then v, and exactly 0 where no measured pixel lies within
+ * r.  The cost of a frame is summed in float64 in a fixed order: per lane over
+ * the tiles, wave shuffles, the four waves.  The table is what
+ * tike_ifft2_crop_scaled, tike_ifft2_pass1_scaled and tike_farplane_scale
+ * take.  One launch, one workgroup per frame walking 32 x 32 tiles (det need
+ * not be a multiple): the tile plus a halo of 2r (r without a table) is staged
+ * into LDS with every index reduced modulo det, I_model and g are formed on
+ * tile + r, the correlation on the tile.  No atomics: two calls give the same
+ * bits.  No allocation.  Per pixel and frame 4 bytes of intensity, 4 (or 2) of
+ * counts and 1 of mask are read and 4 per output written; the halo comes from
+ * cache.  TIKE_ERR_ARG for a NULL intensity or kernel, k not in {3,5,7},
+ * det < k, num_measured < 1, a model other than 0 or 1, data NULL with costs
+ * or table, nframe < 0 or nframe > 2^31 - 1 (one workgroup per frame);
+ * nframe == 0 returns 0 without a launch. */
+int tike_blur_cost_factor(const float* intensity, const float* kernel, int k,
+                          const void* data, int data_u16, const unsigned char* measured,
+                          const float* upstream, float* costs, float* table, float* blurred,
+                          long nframe, int det, int model, long num_measured, void* stream);
+
+/* The length of tike_blur_kernel_sums' `partials` for a (det,det) plane and a
+ * (k,k) kernel (host only: no device, no allocation): n = w (1 + k*k) for w
+ * workgroups; 0 for k not in {3,5,7}, det < k or more than one launch holds. */
+int tike_blur_kernel_sums_partials(int det, int k);
+
+/* Cost and gradient with respect to the kernel on STORED intensities: I does
+ * not depend on K, so an optimiser of K needs no forward operator and no
+ * transform -- one call is a whole gradient or line-search trial.  Arguments
+ * as above; data is required.
+ *   partials  float64, n = tike_blur_kernel_sums_partials(det, k) of them: the
+ *             sum of the FIRST n / (1 + k*k) (the caller adds them in order) is
+ *               sum_f upstream[f] sum_{p measured} term(I_model, d) / num_measured;
+ *             the rest is the workspace of kgrad
+ *   kgrad[u][v] = sum_f sum_{p measured} upstream[f] l'(I_model, d) / num_measured
+ *                 I[f][p - (u - r, v - r) mod det]      (k,k) float64, unless NULL
+ * The products of kgrad are float32 -- g as above, times the stored intensity
+ * -- and every sum is float64 in a fixed order: a workgroup owns a 16 x 16
+ * tile, one pixel per lane, through one of four contiguous ranges of frames in
+ * ascending order (the tile plus a halo of r staged into LDS, every index
+ * reduced modulo det), sums its lanes by wave shuffles and the four waves, and
+ * a second launch of k*k lanes adds the workgroups' sums tile by tile, then
+ * range by range.  Without kgrad it is one launch and no products are formed.
+ * No atomics: two calls give the same bits.  No allocation.  It reads
+ * nframe det^2 (4 + 4 or 2) bytes once, the halo from cache.  TIKE_ERR_ARG for
+ * a NULL intensity, kernel, data or partials, k not in {3,5,7}, det < k,
+ * num_measured < 1, a model other than 0 or 1, nframe < 0 or more workgroups
+ * than one launch holds; nframe == 0 returns 0 without a launch (the outputs
+ * are left as they are). */
+int tike_blur_kernel_sums(const float* intensity, const float* kernel, int k, const void* data,
+                          int data_u16, const unsigned char* measured, const float* upstream,
+                          double* partials, double* kgrad, long nframe, int det, int model,
+                          long num_measured, void* stream);
+
 /* ==== the difference map (tike_amd/ptycho/solvers/dm.py; Thibault et al.
  * 2008 / 2009; no reference counterpart): the two ends of its exit-wave step.
  * The solver keeps one exit wave per position and mode, waves (nscan,S,pw,pw)

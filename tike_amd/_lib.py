@@ -219,6 +219,11 @@ _PROTOTYPES = {
     "tike_background_sums_partials": [_l],
     "tike_background_sums": [_p, _p, _i, _p, _p, _p, _p, _p, _l, _l, _i, _l,
                              _p],
+    "tike_blur_cost_factor": [_p, _p, _i, _p, _i, _p, _p, _p, _p, _p, _l, _i, _i,
+                              _l, _p],
+    "tike_blur_kernel_sums_partials": [_i, _i],
+    "tike_blur_kernel_sums": [_p, _p, _i, _p, _i, _p, _p, _p, _p, _l, _i, _i, _l,
+                              _p],
     "tike_dm_reflect": [_p, _p, _p, _p, _p, _f, _l, _i, _i, _i, _i, _i, _p],
     "tike_dm_update": [_p, _p, _p, _p, _p, _f, _p, _l, _i, _i, _i, _i, _i, _p],
     "tike_comm_unique_id": [_p],

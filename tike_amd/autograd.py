@@ -218,7 +218,13 @@ finer than the counts (a measured pixel the sum over its B x B far-plane
 pixels): tike_binned_cost_factor in the place of tike_cost_factor, its table
 at far-plane resolution with a bin's value on each of its pixels, the chain
 behind it unchanged; `cost_jvp` and `cost_gauss_newton_product` refuse
-binning > 1 by name.
+binning > 1 by name.  ``cost(..., blur=K)`` is the same cost at K (*) I, the
+cyclic convolution of each frame's intensity with a (k, k) kernel (partial
+coherence, a detector's point-spread function): per chunk tike_intensity stores
+the intensities and tike_blur_cost_factor, in the place of tike_cost_factor,
+writes costs or the table K (star) (g mask l' / num_measured), the chain behind
+it unchanged; K.grad is the sum of the chunks' tike_blur_kernel_sums; `cost_jvp`
+and `cost_gauss_newton_product` take no blur.
 
 The entries share their bodies: the three `*_jvp` functions are `_jvp`, the
 three `*_gauss_newton_product` functions `_gauss_newton`, over `_checked_jvp`
@@ -1532,20 +1538,70 @@ class _Counts:
     entries on a chunk's far plane."""
 
     def __init__(self, data, mask, num_measured, model, fly, binning=1,
-                 background=None):
+                 background=None, blur=None):
         self.data, self.mask, self.nm = data, mask, num_measured
         self.model, self.fly, self.binning = model, fly, binning
         # (det, det) float32, detached: the factors are taken at I + background
         self.background = background
+        # (k, k) float32, detached: the factors are taken at blur (*) I
+        self.blur = blur
+        self._stored = None  # the stored intensities of the chunk in hand
         self.u16 = int(data.dtype == torch.uint16)
+
+    def _intensity(self, far, nf):
+        """The stored intensities (nf, det, det) of a chunk's far plane
+        (tike_intensity: one read of the far plane), in a buffer that is
+        reused from chunk to chunk (one stream)."""
+        det = far.shape[-1]
+        if self._stored is None or self._stored.shape[0] < nf:
+            self._stored = torch.empty((nf, det, det), dtype=torch.float32,
+                                       device=far.device)
+        inten = self._stored[:nf]
+        check(
+            lib.tike_intensity(A.ptr(far), A.ptr(inten), nf,
+                               far.shape[-3] * self.fly, det * det,
+                               A.stream_ptr()), "cost (tike_intensity)")
+        return inten
+
+    def kernel_sums(self, lo, hi, upstream, ksum):
+        """Adds d (sum_f upstream_f cost_f) / d blur of the frames of the
+        positions lo ... hi - 1 to ksum (k, k) float64: tike_blur_kernel_sums
+        on the intensities `factor` has just stored for this chunk."""
+        fly = self.fly
+        flo, nf = lo // fly, (hi - lo) // fly
+        k, det = self.blur.shape[-1], self._stored.shape[-1]
+        n = lib.tike_blur_kernel_sums_partials(det, k)
+        partials = torch.empty(n, dtype=torch.float64, device=ksum.device)
+        kgrad = torch.empty((k, k), dtype=torch.float64, device=ksum.device)
+        check(
+            lib.tike_blur_kernel_sums(
+                A.ptr(self._stored[:nf]), A.ptr(self.blur), k,
+                A.ptr(self.data[flo:]), self.u16, A.ptr(self.mask),
+                None if upstream is None else A.ptr(upstream[flo:]),
+                A.ptr(partials), A.ptr(kgrad), nf, det, self.model, self.nm,
+                A.stream_ptr()), "cost (tike_blur_kernel_sums)")
+        ksum.add_(kgrad)
 
     def factor(self, lo, hi, far, upstream, costs, table):
         """tike_cost_factor on the frames of the positions lo ... hi - 1;
         with binning > 1 tike_binned_cost_factor: counts and mask at data
         resolution, the table at the far plane's; with a background
-        tike_background_cost_factor."""
+        tike_background_cost_factor; with a blur the chunk's stored
+        intensities (tike_intensity), then tike_blur_cost_factor on them."""
         fly = self.fly
         flo, nf = lo // fly, (hi - lo) // fly
+        if self.blur is not None:
+            inten = self._intensity(far, nf)
+            check(
+                lib.tike_blur_cost_factor(
+                    A.ptr(inten), A.ptr(self.blur), self.blur.shape[-1],
+                    A.ptr(self.data[flo:]), self.u16, A.ptr(self.mask),
+                    None if upstream is None else A.ptr(upstream[flo:]),
+                    None if costs is None else A.ptr(costs[flo:]),
+                    A.ptr(table), None, nf, far.shape[-1], self.model,
+                    self.nm, A.stream_ptr()),
+                "cost (tike_blur_cost_factor)")
+            return
         if self.background is not None:
             check(
                 lib.tike_background_cost_factor(
@@ -1639,8 +1695,9 @@ class _Cost(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, psi, probe, scan, eigen_probe, eigen_weights, operator,
-                counts, background):
-        # (background: `counts` holds it detached; here for its gradient)
+                counts, background, blur):
+        # (background, blur: `counts` holds them detached; here for their
+        # gradients)
         psi, probe, scan = (x.detach().contiguous() for x in (psi, probe, scan))
         eigen = (None if eigen_probe is None else
                  eigen_probe.detach().contiguous())
@@ -1670,6 +1727,10 @@ class _Cost(torch.autograd.Function):
         # frames, chunk by chunk in float64, rounded once
         bsum = (torch.zeros((det, det), dtype=torch.float64,
                             device=psi.device) if want_b else None)
+        # d (sum_f g_f cost_f) / d K: the chunks' kgrad, float64, rounded once
+        want_k = counts.blur is not None and ctx.needs_input_grad[8]
+        ksum = (torch.zeros(tuple(counts.blur.shape), dtype=torch.float64,
+                            device=psi.device) if want_k else None)
 
         def table_of(lo, hi, far):
             # one chunk of table, reused: the chain reads it before the next
@@ -1682,30 +1743,37 @@ class _Cost(torch.autograd.Function):
             counts.factor(lo, hi, far, g, None, table)
             if want_b:
                 bsum.add_(table.sum(dim=0, dtype=torch.float64))
+            if want_k:
+                counts.kernel_sums(lo, hi, g, ksum)
             return table
 
         def gb():
-            return bsum.to(torch.float32) if want_b else None
+            return (bsum.to(torch.float32) if want_b else None,
+                    ksum.to(torch.float32) if want_k else None)
 
         want = tuple(ctx.needs_input_grad[:5])
-        if want_b and not any(want):
-            # the background alone: the tables, no chain behind them
+        if (want_b or want_k) and not any(want):
+            # the background or the kernel alone: no chain behind the tables
             for lo, hi, far in _cost_far_chunks(op, fly, psi, probe, scan,
                                                 eigen, weights):
-                table_of(lo, hi, far)
-            return (None,) * 7 + (gb(),)
+                if want_b:
+                    table_of(lo, hi, far)
+                else:  # (the kernel's sums need the intensities, no table)
+                    counts._intensity(far, (hi - lo) // fly)
+                    counts.kernel_sums(lo, hi, g, ksum)
+            return (None,) * 7 + gb()
         if psi.shape[0] > 1:
             grads = _multislice_backward_chunks(op, fly, psi, probe, scan,
                                                 want[:3], table_of)
-            return grads + (None, None, None, None, gb())
+            return grads + (None, None, None, None) + gb()
         grads = _backward_chunks(op, fly, psi, probe, scan, want, table_of,
                                  eigen, weights)
-        return grads + (None, None, gb())
+        return grads + (None, None) + gb()
 
 
 def cost(operator, data, psi, probe, scan, *, model="gaussian",
          measured_pixels=None, eigen_probe=None, eigen_weights=None, fly=1,
-         binning=1, check_positions=True, background=None):
+         binning=1, check_positions=True, background=None, blur=None):
     """The per-frame cost (N // fly,) float32 of the model's intensity against
     the counts `data` (N // fly, det, det) float32 or uint16 under the
     project's noise models -- "gaussian": mean of (sqrt(I) - sqrt(d))^2,
@@ -1744,6 +1812,19 @@ def cost(operator, data, psi, probe, scan, *, model="gaussian",
     no tensor of N // fly * det * det elements exists for it either.  A value
     under the mask may be NaN.  NotImplementedError with binning > 1.
 
+    blur: a (k, k) float32 device tensor K, k in {3, 5, 7}, used as given (the
+    caller keeps it non-negative with sum 1): the costs and every gradient
+    above are taken at K (*) I, the convolution of each frame's intensity with
+    K, cyclic over the (det, det) plane in the stored layout of the counts
+    (the physical convolution with the detector's opposite edges joined) --
+    partial spatial coherence, a detector's point-spread function.  Per chunk
+    the intensities are stored once (tike_intensity) and
+    tike_blur_cost_factor, in the place of tike_cost_factor, writes the costs
+    or the table K (star) (g mask l' / num_measured); the backward chain is
+    unchanged, so this holds for every form of the model.  K may require a
+    gradient: the sum of the chunks' tike_blur_kernel_sums, float64, rounded
+    once.  NotImplementedError with binning > 1 or with a background.
+
     Raises what the form's intensity raises, ValueError for a binning that is
     no integer >= 1 or does not divide the far-plane width, TypeError / ValueError for data
     or measured_pixels of another type, dtype or shape, ValueError for a mask
@@ -1762,9 +1843,11 @@ def cost(operator, data, psi, probe, scan, *, model="gaussian",
         eigen_probe, eigen_weights, fly, check_positions, checked, binning)
     b = (None if background is None else
          _checked_background(name, operator, background, binning))
+    K = (None if blur is None else
+         _checked_blur(name, operator, blur, binning, background))
     return _Cost.apply(psi, probe, scan, eigen_probe, eigen_weights, operator,
-                       _Counts(data, mask, nm, model, fly, binning, b),
-                       background)
+                       _Counts(data, mask, nm, model, fly, binning, b, K),
+                       background, blur)
 
 
 def _checked_background(name, operator, background, binning):
@@ -1791,6 +1874,39 @@ def _checked_background(name, operator, background, binning):
             f"{name}: background lives on {background.device}; tike_amd runs "
             "on the GPU only and there is no CPU fallback")
     return background.detach().contiguous()
+
+
+def _checked_blur(name, operator, blur, binning, background):
+    """The blur kernel of `cost`, detached and contiguous, after its
+    refusals."""
+    if binning != 1:
+        raise NotImplementedError(
+            f"{name}: blur with binning={binning} is not implemented")
+    if background is not None:
+        raise NotImplementedError(
+            f"{name}: blur with a background is not implemented")
+    det = operator.detector_shape
+    if not isinstance(blur, torch.Tensor):
+        raise TypeError(
+            f"{name}: blur must be a torch device tensor, not "
+            f"{type(blur).__name__}")
+    if blur.dtype != torch.float32:
+        raise TypeError(
+            f"{name}: blur must be torch.float32, not {blur.dtype}")
+    k = blur.shape[-1] if blur.ndim else 0
+    if blur.ndim != 2 or tuple(blur.shape) != (k, k) or k not in (3, 5, 7):
+        raise ValueError(
+            f"{name}: blur must be (k, k) with k in (3, 5, 7), not "
+            f"{tuple(blur.shape)}")
+    if k > det:
+        raise ValueError(
+            f"{name}: blur {tuple(blur.shape)} is wider than the detector "
+            f"({det}, {det})")
+    if blur.device.type != "cuda":
+        raise TypeError(
+            f"{name}: blur lives on {blur.device}; tike_amd runs on the GPU "
+            "only and there is no CPU fallback")
+    return blur.detach().contiguous()
 
 
 def _refuse_binned_curvature(name, binning):

@@ -344,6 +344,98 @@ class Ptycho(Operator):
                 A.stream_ptr()), "Ptycho.binned_farplane_gradient")
         return farplane
 
+    def blur_cost_factor(self, intensity, kernel, data=None, *, model=0,
+                         measured=None, num_measured=None, upstream=None,
+                         costs=None, table=None, blurred=None):
+        """`tike_blur_cost_factor` on device tensors: the model
+        I_model = kernel (*) intensity, cyclic over the (det, det) plane in
+        the stored (FFT-shifted) layout, on STORED intensities (FRAME, det,
+        det) float32 -- what `fly_farplane_gradient(intensity=)` or
+        `_compute_intensity` write.  kernel (k, k) float32, k in (3, 5, 7),
+        used as given; data (FRAME, det, det) float32 or uint16 (None when only
+        `blurred` is asked for); measured a (det, det) uint8 mask or None;
+        upstream (FRAME) float32 or None.  Outputs, each float32 or None:
+        costs (FRAME), table (FRAME, det, det) = kernel (star) (upstream mask
+        l' / num_measured), the factor the far plane is multiplied by for the
+        gradient, and blurred (FRAME, det, det) = I_model."""
+        det = self.detector_shape
+        nframe = intensity.shape[0]
+        assert tuple(intensity.shape[1:]) == (det, det), intensity.shape
+        assert intensity.dtype == torch.float32 and intensity.is_contiguous()
+        assert kernel.dtype == torch.float32 and kernel.is_contiguous()
+        assert kernel.ndim == 2 and kernel.shape[0] == kernel.shape[1]
+        if data is not None:
+            assert tuple(data.shape) == (nframe, det, det), data.shape
+            assert data.dtype in (torch.float32, torch.uint16), data.dtype
+        check(
+            lib.tike_blur_cost_factor(
+                A.ptr(intensity), A.ptr(kernel), int(kernel.shape[0]),
+                A.ptr(data),
+                int(data is not None and data.dtype == torch.uint16),
+                A.ptr(measured), A.ptr(upstream), A.ptr(costs), A.ptr(table),
+                A.ptr(blurred), nframe, det, int(model),
+                det * det if num_measured is None else int(num_measured),
+                A.stream_ptr()), "Ptycho.blur_cost_factor")
+
+    def blur_kernel_sums(self, intensity, kernel, data, *, model=0,
+                         measured=None, num_measured=None, upstream=None,
+                         want_gradient=True):
+        """`tike_blur_kernel_sums` on device tensors (arguments as
+        `blur_cost_factor`): (cost partials float64, kgrad (k, k) float64 or
+        None).  The sum of the partials is sum_f upstream_f cost_f (upstream
+        None: ones), kgrad its gradient with respect to the kernel.  One
+        launch without the gradient, a second of k * k lanes with it; no
+        forward operator, no transform."""
+        det = self.detector_shape
+        nframe, k = intensity.shape[0], int(kernel.shape[0])
+        assert tuple(intensity.shape[1:]) == (det, det), intensity.shape
+        assert intensity.dtype == torch.float32 and intensity.is_contiguous()
+        assert kernel.dtype == torch.float32 and kernel.is_contiguous()
+        assert tuple(data.shape) == (nframe, det, det), data.shape
+        assert data.dtype in (torch.float32, torch.uint16), data.dtype
+        n = lib.tike_blur_kernel_sums_partials(det, k)
+        if n <= 0:
+            raise ValueError(
+                f"blur kernel {tuple(kernel.shape)} on a ({det}, {det}) "
+                "detector: incompatible shapes / arguments")
+        buf = torch.empty(n, dtype=torch.float64, device=intensity.device)
+        kgrad = (torch.empty((k, k), dtype=torch.float64,
+                             device=intensity.device)
+                 if want_gradient else None)
+        check(
+            lib.tike_blur_kernel_sums(
+                A.ptr(intensity), A.ptr(kernel), k, A.ptr(data),
+                int(data.dtype == torch.uint16), A.ptr(measured),
+                A.ptr(upstream), A.ptr(buf), A.ptr(kgrad), nframe, det,
+                int(model),
+                det * det if num_measured is None else int(num_measured),
+                A.stream_ptr()), "Ptycho.blur_kernel_sums")
+        return buf[:n // (1 + k * k)], kgrad
+
+    def _device_blur(self, blur, binning, psi, background):
+        """The blur kernel of `_compute_intensity` and `cost` on the device,
+        after their refusals."""
+        if binning > 1:
+            raise ValueError("blur together with binning > 1 is not supported")
+        if background is not None:
+            raise ValueError(
+                "blur together with a background is not supported")
+        if psi.shape[0] > 1:
+            raise ValueError(
+                "blur together with several object slices is not supported")
+        det = self.detector_shape
+        K = A.to_device(blur, np.float32).contiguous()
+        k = K.shape[-1] if K.ndim else 0
+        if K.ndim != 2 or tuple(K.shape) != (k, k) or k not in (3, 5, 7):
+            raise ValueError(
+                f"blur must be (k, k) with k in (3, 5, 7), not "
+                f"{tuple(K.shape)}")
+        if k > det:
+            raise ValueError(
+                f"blur {tuple(K.shape)} is wider than the detector "
+                f"({det}, {det})")
+        return K
+
     def _device_background(self, background, binning, psi):
         """The background of `_compute_intensity` and `cost` on the device,
         after their refusals."""
@@ -363,13 +455,23 @@ class Ptycho(Operator):
         return b
 
     def _compute_intensity(self, data, psi, scan, probe, fly=1, binning=1,
-                           background=None):
+                           background=None, blur=None):
         """(intensity (FRAME,det,det), farplane) -- ptycho.py:178-191; with
         fly > 1 a frame is the sum over `fly` consecutive positions
         (ptycho.py:104-125); with binning = B > 1 the intensity is
         (FRAME, det // B, det // B), a pixel the sum over its B x B far-plane
         pixels (`binned_farplane_gradient`); with a background (det, det) the
-        intensity includes it."""
+        intensity includes it; with a blur (k, k) the intensity is convolved
+        with it, cyclically over the plane (`blur_cost_factor`)."""
+        if blur is not None:
+            K = self._device_blur(blur, binning,
+                                  A.to_device(psi, np.complex64), background)
+            intensity, far = self._compute_intensity(data, psi, scan, probe,
+                                                     fly=fly)
+            stored = A.to_device(intensity).contiguous()
+            blurred = torch.empty_like(stored)
+            self.blur_cost_factor(stored, K, blurred=blurred)
+            return A.like_input(blurred, psi), far
         if background is not None:
             b = self._device_background(background, binning,
                                         A.to_device(psi, np.complex64))
@@ -405,11 +507,32 @@ class Ptycho(Operator):
         return A.like_input(intensity, kind), A.like_input(far, kind)
 
     def cost(self, data, psi, scan, probe, *, model, fly=1, binning=1,
-             background=None):
+             background=None, blur=None):
         """ptycho.py:193-204; with fly > 1 or binning > 1 the mean over frames
         of the cost of each frame's summed (and binned) intensity; with a
         background (det, det) the cost of intensity + background
-        (`background_farplane_gradient`)."""
+        (`background_farplane_gradient`); with a blur (k, k) the cost of
+        blur (*) intensity (`blur_cost_factor` on the stored intensities)."""
+        if blur is not None:
+            if model not in objective._MODELS:
+                raise ValueError(f"unknown noise model {model!r}")
+            K = self._device_blur(blur, binning,
+                                  A.to_device(psi, np.complex64), background)
+            intensity, _ = self._compute_intensity(None, psi, scan, probe,
+                                                   fly=fly)
+            stored = A.to_device(intensity).contiguous()
+            counts = A.to_device(data)
+            if counts.dtype not in (torch.float32, torch.uint16):
+                counts = counts.to(torch.float32)
+            if counts.shape[0] != stored.shape[0]:
+                raise ValueError(
+                    f"{counts.shape[0]} frames of fly={fly} do not match "
+                    f"{stored.shape[0] * fly} scan positions")
+            costs = torch.empty(counts.shape[0], dtype=torch.float32,
+                                device=stored.device)
+            self.blur_cost_factor(stored, K, counts.contiguous(),
+                                  model=objective._MODELS[model], costs=costs)
+            return A.like_input(costs.mean(), psi)
         if background is not None:
             background = self._device_background(
                 background, binning, A.to_device(psi, np.complex64))

@@ -1,5 +1,6 @@
 """Ptychography solvers and helpers (mirror of ``tike.ptycho``)."""
 from .background import BackgroundOptions
+from .blur import BlurOptions
 from .exitwave import ExitWaveOptions
 from .fresnel import MW_probe, single_probe
 from .object import (ObjectOptions, get_absorbtion_image, get_padded_object,
@@ -22,7 +23,7 @@ from .solvers import (CgradOptions, DmOptions, LstsqOptions,
 from . import probe, object, position, exitwave, solvers, io, learn, fresnel  # noqa: F401,A004
 
 __all__ = [
-    "BackgroundOptions", "CgradOptions", "DmOptions", "ExitWaveOptions", "LstsqOptions",
+    "BackgroundOptions", "BlurOptions", "CgradOptions", "DmOptions", "ExitWaveOptions", "LstsqOptions",
     "ObjectOptions",
     "AffineTransform", "PositionOptions", "affine_position_regularization",
     "ProbeOptions", "PtychoParameters", "Reconstruction",

@@ -43,6 +43,7 @@ from .probe import (apply_median_filter_abs_probe, constrain_center_peak,
                     power as probe_power,
                     rescale_probe_using_fixed_intensity_photons)
 from . import background as _background
+from . import blur as _blur
 from .solvers.cgrad import _refuse_binning, _refuse_fly, _refuse_multislice
 from .solvers.dm import refuse as _refuse_dm
 from .solvers.lstsq import chunk_positions, mask_info
@@ -52,12 +53,14 @@ logger = logging.getLogger(__name__)
 
 
 def _intensity_chunks(operator, psi, scan, probe, eigen_probe=None,
-                      eigen_weights=None, fly=1, binning=1, background=None):
+                      eigen_weights=None, fly=1, binning=1, background=None,
+                      blur=None):
     """Yield (lo, hi, intensity (n, det, det)) over chunks of frames; frame f
     is the sum over the positions f * fly ... f * fly + fly - 1.  With
     binning = B > 1 the intensity is (n, det // B, det // B), a pixel the sum
     over its B x B far-plane pixels.  background (det, det) float32 or None
-    is added to every frame."""
+    is added to every frame; blur (k, k) float32 or None is the kernel every
+    frame is convolved with, cyclically (`Ptycho.blur_cost_factor`)."""
     N = scan.shape[0]
     S = probe.shape[-3]
     det = operator.detector_shape
@@ -91,19 +94,31 @@ def _intensity_chunks(operator, psi, scan, probe, eigen_probe=None,
                                    det * det, A.stream_ptr()), "intensity")
         if background is not None:
             inten += background
+        if blur is not None:
+            blurred = torch.empty_like(inten)
+            operator.blur_cost_factor(inten, blur, blurred=blurred)
+            inten = blurred
         yield lo // fly, hi // fly, inten
 
 
 def simulate(detector_shape, probe, scan, psi, fly=1, eigen_probe=None,
-             eigen_weights=None, binning=1, background=None, **kwargs):
+             eigen_weights=None, binning=1, background=None, blur=None,
+             **kwargs):
     """Real-valued detector counts of simulated ptychography data
     (ptycho.py:128-179).  Returns (FRAME, det, det) float32 on the host.
     binning = B > 1: `detector_shape` stays the far-plane width, a measured
     pixel is the sum over its B x B far-plane pixels, and the result is
     (FRAME, det // B, det // B).  background: a (det, det) float32
     incoherent background >= 0, in the stored layout of the frames, added to
-    every frame."""
+    every frame.  blur: a (k, k) float32 kernel >= 0, k in (3, 5, 7), the
+    centre at [k // 2, k // 2]: normalised to sum 1, then every frame is
+    convolved with it, cyclically over the (det, det) plane in the stored
+    layout (the detector's opposite edges joined; `ptycho.blur`)."""
     binning = _checked_binning(binning, int(detector_shape))
+    if blur is not None:
+        blur = _checked_simulated_blur(blur, int(detector_shape), binning,
+                                       psi, eigen_probe, eigen_weights,
+                                       background)
     if background is not None:
         background = _checked_simulated_background(
             background, int(detector_shape), binning, psi, eigen_probe,
@@ -121,8 +136,30 @@ def simulate(detector_shape, probe, scan, psi, fly=1, eigen_probe=None,
             inten for _, _, inten in _intensity_chunks(
                 operator, *resident, fly=int(fly), binning=binning,
                 background=None if background is None else operator.asarray(
-                    background, dtype=real))])
+                    background, dtype=real),
+                blur=None if blur is None else operator.asarray(
+                    blur, dtype=real).contiguous())])
         return operator.asnumpy(frames)
+
+
+def _checked_simulated_blur(blur, det, binning, psi, eigen_probe,
+                            eigen_weights, background):
+    """The kernel of `simulate` as a normalised host array, after its
+    refusals."""
+    if binning > 1:
+        raise NotImplementedError(
+            f"blur with binning={binning} is not implemented")
+    if background is not None:
+        raise NotImplementedError(
+            "blur with a background is not implemented")
+    if psi.shape[0] > 1:
+        raise NotImplementedError(
+            f"blur with several slices (psi.shape[0] = {psi.shape[0]}) is not "
+            "implemented")
+    if eigen_probe is not None or eigen_weights is not None:
+        raise NotImplementedError("blur with eigen probes is not implemented")
+    return _blur.checked_kernel(
+        np.asarray(A.to_host(blur), dtype=np.float32), det)
 
 
 def _checked_simulated_background(background, det, binning, psi, eigen_probe,
@@ -149,7 +186,8 @@ def _checked_simulated_background(background, det, binning, psi, eigen_probe,
 
 
 def reconstruct(data, parameters, num_gpu=None, use_mpi=False, *, fly=1,
-                binning=1, background_options=None, **kwargs):
+                binning=1, background_options=None, blur_options=None,
+                **kwargs):
     """Solve the ptychography problem (ptycho.py:182-262).
 
     data (FRAME, WIDE, HIGH): measured intensities, FFT-shifted so that the
@@ -180,6 +218,12 @@ def reconstruct(data, parameters, num_gpu=None, use_mpi=False, *, fly=1,
     models every pattern as the coherent intensity plus a non-negative
     background per detector pixel and, unless told otherwise, fits it.  The
     fitted background is left in `background_options.background`.
+
+    blur_options (keyword only): a `BlurOptions`; cgrad then models every
+    pattern as the coherent intensity convolved with a small non-negative
+    kernel (partial spatial coherence, the detector's point-spread function;
+    cyclic over the detector plane) and, unless told otherwise, fits the
+    kernel.  The fitted kernel is left in `blur_options.kernel`.
     """
     if use_mpi:
         raise NotImplementedError(
@@ -206,6 +250,12 @@ def reconstruct(data, parameters, num_gpu=None, use_mpi=False, *, fly=1,
             f"background_options with reconstruct(num_gpu={num_gpu!r}) from "
             "a plain process: the ranks this call would start do not fit a "
             "background")
+    if (blur_options is not None and requested is not None
+            and len(requested) > 1 and _spawn.world_size() == 1):
+        raise NotImplementedError(
+            f"blur_options with reconstruct(num_gpu={num_gpu!r}) from a plain "
+            "process: the ranks this call would start do not fit a blur "
+            "kernel")
     how, where = _spawn.resolve(num_gpu)
     if how == "spawn":
         return _spawn.reconstruct_spawned(data, parameters, where, **kwargs)
@@ -213,6 +263,7 @@ def reconstruct(data, parameters, num_gpu=None, use_mpi=False, *, fly=1,
                         num_gpu if where is None else (where,),
                         use_mpi, fly=fly, binning=binning,
                         background_options=background_options,
+                        blur_options=blur_options,
                         **kwargs) as context:
         context.iterate(parameters.algorithm_options.num_iter)
         result = context.get_result()
@@ -220,7 +271,8 @@ def reconstruct(data, parameters, num_gpu=None, use_mpi=False, *, fly=1,
 
 
 def reconstruct_multigrid(data, parameters, num_gpu=None, use_mpi=False,
-                          num_levels=3, interp=None, *, binning=1):
+                          num_levels=3, interp=None, *, binning=1,
+                          blur_options=None):
     """Coarse-to-fine reconstruction (ptycho.py:975-1047): the real-space
     parameters are downsampled by 2^(num_levels-1) and the diffraction
     patterns cropped in Fourier space, every level runs
@@ -230,6 +282,10 @@ def reconstruct_multigrid(data, parameters, num_gpu=None, use_mpi=False,
         raise NotImplementedError(
             f"binning={binning} with reconstruct_multigrid: cropping binned "
             "diffraction patterns in Fourier space is not implemented")
+    if blur_options is not None:
+        raise NotImplementedError(
+            "blur_options with reconstruct_multigrid: a blur kernel of "
+            "diffraction patterns cropped in Fourier space is not implemented")
     data = A.to_host(data)
     coarsest = 2**(num_levels - 1)
     if data.shape[-1] / coarsest < 64:
@@ -484,15 +540,24 @@ class Reconstruction():
         cgrad with a shared probe, one slice, no binning, no position
         correction and HBM-resident data, in one process.  `get_result()`
         leaves the fitted background in `background_options.background`.
+      blur_options: a `BlurOptions` (default None).  Every pattern is then
+        modelled as the coherent intensity convolved with a (k, k) kernel,
+        cyclically over the detector plane (`ptycho.blur`), which cgrad fits
+        in a third conjugate-gradient block per minibatch; the solver must
+        be cgrad with a shared probe, one slice, no binning, no background,
+        no position correction and HBM-resident data, in one process.
+        `get_result()` leaves the fitted kernel in `blur_options.kernel`.
     """
 
     fly = 1  # scan positions per diffraction pattern
     binning = 1  # far-plane pixels per measured pixel, per axis
+    _blur = None  # (blur_options, its normalised kernel) or None
 
     def __init__(self, data, parameters, num_gpu=None, use_mpi=False, *,
                  presharded=False, order=None, batches=None,
                  spatial_sort=True, data_on_host=False, local_data=None,
-                 fly=1, binning=1, background_options=None):
+                 fly=1, binning=1, background_options=None,
+                 blur_options=None):
         # a context lives in ONE process with ONE GPU: `num_gpu` must agree
         # with the process group it runs in (`reconstruct` is the entry that
         # starts ranks by itself)
@@ -530,6 +595,13 @@ class Reconstruction():
                 background_options, parameters, data.shape[-1], fly=fly,
                 binning=binning, data_on_host=data_on_host,
                 local_data=local_data, world_size=_spawn.world_size())
+        blur = None
+        if blur_options is not None:
+            blur = _blur.refuse(
+                blur_options, parameters, data.shape[-1], fly=fly,
+                binning=binning, data_on_host=data_on_host,
+                local_data=local_data, world_size=_spawn.world_size(),
+                background_options=background_options)
         name = parameters.algorithm_options.name
         if not hasattr(solvers, name):
             raise NotImplementedError(
@@ -584,6 +656,8 @@ class Reconstruction():
         self._background = (None if background is None else
                             (background_options, background))
         self.operator.background = None
+        self._blur = None if blur is None else (blur_options, blur)
+        self.operator.blur = None
         self.comm = Comm()
         self._pending_fits = []  # futures of deferred affine position fits
         self._free_snaps = []  # pinned host buffers of finished fits
@@ -681,6 +755,8 @@ class Reconstruction():
     def _finish_enter(self):
         if self._background is not None:
             self.operator.background = _background.State(*self._background)
+        if self._blur is not None:
+            self.operator.blur = _blur.State(*self._blur)
         self.parameters = solvers.PtychoParameters.split(
             self.local_order,
             x=self._host_parameters()).copy_to_device()
@@ -772,6 +848,10 @@ class Reconstruction():
         returns the same cost.  `parameters.scan` is replaced only after the
         test has passed.  `position_options` is neither needed nor touched."""
         from .solvers.rpie import _positions_flag, _raise_unless_allowed
+        if self._blur is not None:
+            raise NotImplementedError(
+                "blur_options with update_positions_pd: position refinement "
+                "together with a blur is not implemented")
         if self.fly > 1:
             raise NotImplementedError(
                 f"fly={self.fly} with update_positions_pd: position "
@@ -917,6 +997,8 @@ class Reconstruction():
                                           g(po.confidence), g(po._momentum))
         if self.operator.background is not None:
             self.operator.background.write_back()
+        if self.operator.blur is not None:
+            self.operator.blur.write_back()
         return p
 
     def get_convergence(self):

@@ -52,6 +52,16 @@ no variable is recovered, one cost-only evaluation.
   on b: that call forms the minibatch's intensities once (``_Intensities``)
   and every gradient and line-search trial is then one
   ``tike_background_sums`` launch -- no forward operator, no transform.
+* a blurred far field (the operator's ``blur`` state, set by
+  ``blur_options``; no reference counterpart): every pattern is the coherent
+  intensity convolved with a (k, k) kernel K = a^2 / sum a^2, cyclically over
+  the detector plane.  The fly-scan route at any ``fly``, also 1: the kernel
+  of that route only stores the chunk's intensities, ``tike_blur_cost_factor``
+  forms costs and the table K (star) (mask l') from them, and
+  ``tike_farplane_scale`` applies the table to the far plane as MINUS the
+  gradient.  The third conjugate-gradient call is on a: the minibatch's
+  intensities are stored once and every gradient and line-search trial is one
+  ``tike_blur_kernel_sums`` launch and k * k numbers of chain in torch.
 * objects of several slices (``psi.shape[0] > 1``, probe window = detector):
   the same cost on the far field behind the last slice, e_d = patch(O_d) x
   beam_d, beam_{d+1} = Fresnel(e_d), and its EXACT gradient -- the adjoint
@@ -77,6 +87,7 @@ from ... import _arrays as A
 from ... import opt
 from ..._lib import check, lib
 from ...operators.propagation import fft_scales
+from .. import blur as _blur
 from ..exitwave import ExitWaveOptions
 from ..position import gaussian_derivative_taps
 from . import _multislice as M
@@ -840,9 +851,24 @@ def _background_cost_and_grad(op, data, lo, hi, fly, a, *, want_grad, cm,
     return partials.sum(), (2 * a * bgrad if want_grad else None)
 
 
+def _blur_cost_and_grad(op, data, lo, hi, fly, a, *, want_grad, cm, stored):
+    """(sum of the per-frame costs at K = a^2 / sum a^2, a device scalar;
+    d / d a of that sum, or None) of the frames [lo / fly, hi / fly) from
+    their stored intensities: one `tike_blur_kernel_sums` launch (with the
+    gradient, its k * k lanes of a second), then the chain of
+    ptycho/blur.py, k * k numbers in torch."""
+    d = data[lo // fly:hi // fly]
+    if d.dtype not in (torch.float32, torch.uint16):
+        d = d.to(torch.float32)
+    partials, kgrad = op.blur_kernel_sums(
+        stored.values, _blur.kernel_of(a), d, model=cm.model,
+        measured=cm.mask, num_measured=cm.nmeasured, want_gradient=want_grad)
+    return partials.sum(), (_blur.chain(a, kgrad) if want_grad else None)
+
+
 def _fly_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, fly, *,
                        want_psi, want_probe, want_grad, cm, binning=1,
-                       background=None, stored=None):
+                       background=None, stored=None, blur=None):
     """(sum of this rank's per-frame costs, a device scalar; d cost / d psi or
     None; d cost / d probe or None -- unnormalised adjoints summed over the
     ranks) of the positions [lo, hi), whole frames: the data rows
@@ -855,7 +881,19 @@ def _fly_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, fly, *,
     background (det, det) float32: costs and gradients at intensity +
     background, `tike_background_farplane_gradient` in that kernel's place.
     stored (with background, cost only): the `_Intensities` that receive the
-    frames' intensities without the background."""
+    frames' intensities without the background.
+    blur (k, k) float32: costs and gradients at blur (*) intensity, the
+    cyclic convolution of ptycho/blur.py.  `tike_fly_farplane_gradient` then
+    only stores the chunk's intensities (one read of the far plane, nothing
+    written to it), `tike_blur_cost_factor` forms the costs from them and, for
+    a gradient, the table blur (star) (mask l') -- upstream num_measured, so
+    that the factor is the unnormalised one of the other routes --, which
+    `tike_farplane_scale` applies to the far plane as MINUS the gradient: per
+    gradient evaluation the far plane crosses HBM five times (written by the
+    forward, read for the intensities, read and written by the scaling, read
+    by the adjoint), once more than without a blur.  stored (with blur, cost
+    only): receives the frames' intensities, which do not depend on the
+    kernel."""
     assert lo % fly == 0 and hi % fly == 0, (lo, hi, fly)
     dev = psi.device
     S, det = probe.shape[-3], op.detector_shape
@@ -871,6 +909,16 @@ def _fly_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, fly, *,
         stored.values = ws.get("background_intensity",
                                (max(N // fly, 1), det, det), torch.float32,
                                dev)[:N // fly]
+    if blur is not None:
+        nchunk = max(min(chunk, max(N, 1)) // fly, 1)
+        inten_all = ws.get("blur_intensity", (nchunk, det, det), torch.float32,
+                           dev)
+        table_all = ws.get("blur_table", (nchunk, det, det), torch.float32,
+                           dev)
+        # upstream = num_measured: (float)(n * (1 / n)) = 1, the table is the
+        # unnormalised blur (star) (mask l')
+        unit = ws.get("blur_upstream", (nchunk,), torch.float32, dev)
+        unit.fill_(float(cm.nmeasured))
     for clo in range(lo, hi, chunk):
         chi = min(hi, clo + chunk)
         sc = scan[clo:chi]
@@ -883,7 +931,23 @@ def _fly_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, fly, *,
                    num_measured=cm.nmeasured,
                    costs=costs[(clo - lo) // fly:(chi - lo) // fly],
                    apply_gradient=want_grad)
-        if background is not None:
+        if blur is not None:
+            nf = (chi - clo) // fly
+            inten = (inten_all[:nf] if stored is None else
+                     stored.values[(clo - lo) // fly:(chi - lo) // fly])
+            op.fly_farplane_gradient(far, d, fly, intensity=inten)
+            table = table_all[:nf] if want_grad else None
+            op.blur_cost_factor(inten, blur, d, model=cm.model,
+                                measured=cm.mask, num_measured=cm.nmeasured,
+                                upstream=unit[:nf], costs=how["costs"],
+                                table=table)
+            if want_grad:
+                check(
+                    lib.tike_farplane_scale(A.ptr(far), A.ptr(table), nf,
+                                            S * fly, det * det, -1.0,
+                                            A.stream_ptr()),
+                    "cgrad blur (table applied to the far plane)")
+        elif background is not None:
             if stored is not None:
                 how["intensity"] = stored.values[(clo - lo) // fly:
                                                  (chi - lo) // fly]
@@ -1058,13 +1122,19 @@ class _Minibatch:
     def __init__(self, op, comm, data, psi, scan, probe, lo, hi, cm, fly,
                  binning=1, background=None):
         self.where = (op, comm, data), scan, (lo, hi)
+        # `background`: the state of the third block, the `State` of
+        # ptycho/background.py or that of ptycho/blur.py (never both)
+        blur = background if isinstance(background, _blur.State) else None
+        background = None if blur is not None else background
         self.background = background  # the `State` of ptycho/background.py
-        self.stored = None  # `_Intensities` of the background block
+        self.blur = blur  # the `State` of ptycho/blur.py
+        self.stored = None  # `_Intensities` of the third block
         self.finish = lambda total: _finish_cost(total, comm, op, lo, hi, fly)
         if psi.shape[0] > 1:  # (every evaluation splits into the same chunks)
             self.run = _multislice_cost_and_grad
             self.how = dict(cm=cm, chunk=_multislice_chunk(op, psi, probe))
-        elif fly > 1 or binning > 1 or background is not None:
+        elif (fly > 1 or binning > 1 or background is not None
+              or blur is not None):
             if lo % fly or hi % fly:
                 raise ValueError(
                     f"minibatch [{lo}, {hi}) does not hold whole frames of "
@@ -1097,6 +1167,17 @@ class _Minibatch:
         args, scan, span = self.where
         how = self.how if position_terms is None else dict(
             self.how, position_terms=position_terms)
+        if variable == 2 and self.blur is not None:
+            if self.stored is None:
+                # the intensities at the block's object and probe, once: they
+                # do not depend on the kernel
+                self.stored = _Intensities()
+                self.run(*args, psi, scan, probe, *span, want_psi=False,
+                         want_probe=False, want_grad=False,
+                         blur=self.blur.kernel, stored=self.stored, **how)
+            return _blur_cost_and_grad(
+                args[0], args[2], *span, how["fly"], a, want_grad=want_grad,
+                cm=how["cm"], stored=self.stored)
         if variable == 2:
             if self.stored is None:
                 # the intensities at the block's object and probe, once
@@ -1110,6 +1191,8 @@ class _Minibatch:
                 cm=how["cm"], stored=self.stored)
         if self.background is not None:
             how = dict(how, background=self.background.b)
+        if self.blur is not None:
+            how = dict(how, blur=self.blur.kernel)
         r = self.run(*args, psi, scan, probe, *span, want_psi=variable == 0,
                      want_probe=variable == 1, want_grad=want_grad, **how)
         return r[0], None if variable is None else r[1 + variable]
@@ -1146,8 +1229,9 @@ def _host_cg(minibatch, psi, probe, variable, o, positions=None):
         return [g]
 
     return opt.conjugate_gradient(
-        torch, x=(psi, probe, getattr(minibatch.background, "a",
-                                      None))[variable],
+        torch, x=(psi, probe, getattr(
+            minibatch.background if minibatch.blur is None else
+            minibatch.blur, "a", None))[variable],
         cost_function=cost, grad=grad,
         dir_multi=lambda x: x[0], num_iter=o.cg_iter,
         step_length=o.step_length)
@@ -1164,11 +1248,13 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
     binning = int(getattr(op, "binning", 1))
     _refuse(parameters, fly, binning=binning)
     background = getattr(op, "background", None)
+    blur = getattr(op, "blur", None)
+    third = background if blur is None else blur  # (never both: refused)
     recover = (parameters.object_options is not None,
                parameters.probe_options is not None
                and epoch >= parameters.probe_options.update_start,
-               background is not None and bool(background.options.update)
-               and epoch >= background.options.update_start)
+               third is not None and bool(third.options.update)
+               and epoch >= third.options.update_start)
     psi, probe, scan = parameters.psi, parameters.probe, parameters.scan
     # (the mask and the pixel count are at data resolution)
     cm = _cost_model(parameters.exitwave_options,
@@ -1190,7 +1276,7 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
         hi = lo + len(b)
         comm.minibatch = batch_index
         mb = _Minibatch(op, comm, data, psi, scan, probe, lo, hi, cm, fly,
-                        binning, background)
+                        binning, third)
         if positions is not None:
             positions.pending = True
             # the object's first gradient pass writes the projection the sums
@@ -1215,7 +1301,7 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
                 r = _host_cg(mb, psi, probe, variable, o, owed)
             x, cost = r
             if variable == 2:
-                background.set(x)
+                third.set(x)
                 continue
             psi, probe = (x, probe) if variable == 0 else (psi, x)
         if cost is None:  # no variable recovered: the cost alone
