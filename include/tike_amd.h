@@ -1702,6 +1702,59 @@ int tike_blur_kernel_sums(const float* intensity, const float* kernel, int k, co
                           double* partials, double* kgrad, long nframe, int det, int model,
                           long num_measured, void* stream);
 
+/* ==== near-field (Fresnel, holographic) ptychography (tike_amd/ptycho/
+ * nearfield.py; no reference counterpart).  The detector sits a finite
+ * distance behind the sample, probe window = detector, and a frame is one
+ * Fresnel step of the exit waves that expose it:
+ *   w = IFFT2(H . FFT2(patch x probe)),   I = sum |w|^2.
+ * tike_fwd_pass1 -> tike_fresnel_colpass(H) run the step up to its last pass,
+ * tike_fresnel_colpass(conj H) -> tike_ifft2_pass2_products run the adjoint
+ * from its second pass on; this entry is everything in between, in one launch
+ * (plus a small one that finishes the costs).
+ *   work (nframe*fly,S,det,det) c64: the input of an inverse pass 2, i.e. the
+ *     output of tike_fresnel_colpass(adjoint = 0).  Frame f is exposed by
+ *     positions f*fly .. f*fly+fly-1; P = fly * S planes.  Never written.
+ *   data (nframe,det,det) f32, or u16 with data_u16; measured (det,det) u8 or
+ *     NULL (every pixel measured), num_measured its non-zero pixels; upstream
+ *     (nframe) f32 or NULL (ones); model 0 (gaussian) or 1 (poisson).
+ * With w = inv_scale * (pass 2 of work), which never goes to memory, and
+ * I[f][p] = sum_{j<P} |w[f][j][p]|^2 (a float32 running sum, planes ascending):
+ *   costs (nframe) f32, optional: the mean over the measured pixels of the
+ *     model's term (tike_cost_factor's formulas).  Summed in float64 in a fixed
+ *     order, no atomics: a partial per work item (lane, wave shuffles, waves
+ *     ascending) into cost_partials, float64,
+ *     tike_nearfield_cost_partials(nframe) of them (required with costs), then
+ *     the items of a frame in ascending order.  Two calls give the same bits.
+ *   intensity (nframe,det,det) f32, optional.
+ *   out (nframe*fly,S,det,det) c64, optional, != work: forward pass 1 of g . w,
+ *     the input of tike_fresnel_colpass(adjoint = 1), with
+ *       g[f][p] = scale * ((float)(upstream[f] / num_measured) * l'(I, d))
+ *     on measured pixels (tike_cost_factor's table times scale) and exactly 0
+ *     elsewhere.  A count under the mask may be NaN: selected away, never
+ *     multiplied.
+ * With out == NULL (a line-search probe) work is read once and nothing
+ * plane-sized is written.  data may be NULL only when costs and out both are.
+ * A work item = (frame, q < det / 16) as in tike_slice_step_back: the rows the
+ * inverse column stage finishes are the 16 rows of a forward pass-1 group.
+ * LIMITS: det in {128, 256}, S <= 8, any fly >= 1 (TIKE_ERR_UNSUPPORTED
+ * otherwise: tike_fft2_pass2_inplace + tike_fly_farplane_gradient or
+ * tike_cost_factor / tike_farplane_scale + tike_fft2_pass1).  With P <= 3 the
+ * planes of a work item stay in registers between the intensity sum and the
+ * product (work read once); above, a second sweep reads work again, newest
+ * plane first.  Per frame P det^2 8 bytes read (x 2 with P > 3), det^2 (4 or
+ * 2) of counts, det^2 of mask, P det^2 8 written with out.  No allocation.
+ * TIKE_ERR_ARG for a NULL work, a NULL data with costs or out, costs without
+ * cost_partials, out == work, a model other than 0 or 1, num_measured < 1,
+ * fly < 1, S < 1, nframe < 0 or more frames than
+ * tike_nearfield_cost_partials counts in an int; nframe == 0 returns 0 without
+ * a launch. */
+int tike_nearfield_cost_partials(long nframe);
+int tike_nearfield_plane_gradient(const void* work, const void* data, int data_u16,
+                                  const unsigned char* measured, const float* upstream,
+                                  float* costs, double* cost_partials, float* intensity,
+                                  void* out, long nframe, int fly, int S, int det, int model,
+                                  long num_measured, float inv_scale, float scale, void* stream);
+
 /* ==== the difference map (tike_amd/ptycho/solvers/dm.py; Thibault et al.
  * 2008 / 2009; no reference counterpart): the two ends of its exit-wave step.
  * The solver keeps one exit wave per position and mode, waves (nscan,S,pw,pw)

@@ -224,6 +224,9 @@ _PROTOTYPES = {
     "tike_blur_kernel_sums_partials": [_i, _i],
     "tike_blur_kernel_sums": [_p, _p, _i, _p, _i, _p, _p, _p, _p, _l, _i, _i, _l,
                               _p],
+    "tike_nearfield_cost_partials": [_l],
+    "tike_nearfield_plane_gradient": [_p, _p, _i, _p, _p, _p, _p, _p, _p, _l, _i,
+                                      _i, _i, _i, _l, _f, _f, _p],
     "tike_dm_reflect": [_p, _p, _p, _p, _p, _f, _l, _i, _i, _i, _i, _i, _p],
     "tike_dm_update": [_p, _p, _p, _p, _p, _f, _p, _l, _i, _i, _i, _i, _i, _p],
     "tike_comm_unique_id": [_p],

@@ -27,6 +27,9 @@ the tests that compare two routes.
                             launches `tike_slice_step_back` replaces
   TIKE_DM_FUSED=0           dm, 256^2 / 512^2: the exit-wave step with a stored
                             far plane instead of the far-plane-free route
+  TIKE_NEARFIELD_FUSED=0    near-field, 128^2 / 256^2: the middle of the chain as the
+                            three launches `tike_nearfield_plane_gradient`
+                            replaces (as 512^2 always takes it)
   TIKE_CGRAD_GRAPHS=1       cgrad: replay captured HIP graphs (slower on ROCm 7.2)
   TIKE_FWD_SUB_MIB=n        Ptycho.fwd / adj: far-plane MiB per sub-batch
 """
@@ -55,6 +58,7 @@ multislice_step_back = _flag("TIKE_MS_STEP_BACK", True)
 cgrad_multislice_fused = _flag("TIKE_CGRAD_MS_FUSED", True)
 cgrad_multislice_step_back = _flag("TIKE_CGRAD_MS_STEP_BACK", True)
 dm_fused = _flag("TIKE_DM_FUSED", True)
+nearfield_fused = _flag("TIKE_NEARFIELD_FUSED", True)
 cgrad_graphs = _flag("TIKE_CGRAD_GRAPHS", False)
 fwd_sub_mib = (float(os.environ["TIKE_FWD_SUB_MIB"])
                if os.environ.get("TIKE_FWD_SUB_MIB") else None)

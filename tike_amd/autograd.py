@@ -224,7 +224,15 @@ coherence, a detector's point-spread function): per chunk tike_intensity stores
 the intensities and tike_blur_cost_factor, in the place of tike_cost_factor,
 writes costs or the table K (star) (g mask l' / num_measured), the chain behind
 it unchanged; K.grad is the sum of the chunks' tike_blur_kernel_sums; `cost_jvp`
-and `cost_gauss_newton_product` take no blur.
+and `cost_gauss_newton_product` take no blur.  ``cost(..., nearfield=H)`` puts
+the detector in the near field, I = |IFFT2(H FFT2(patch x probe))|^2 with probe
+window = detector (one slice, the shared probe): a Function of its own,
+`_NearfieldCost`, over `operators.nearfield.wave_and_back` -- forward
+tike_fwd_pass1 -> tike_fresnel_colpass -> tike_nearfield_plane_gradient with
+out = NULL, backward the same chunk with grad_output for the upstream, the
+adjoint Fresnel step and the tail of `_Back` (tike_lstsq_gradients,
+tike_scatter_patches, tike_scan_gradient); H takes no gradient; `cost_jvp` and
+`cost_gauss_newton_product` take no nearfield.
 
 The entries share their bodies: the three `*_jvp` functions are `_jvp`, the
 three `*_gauss_newton_product` functions `_gauss_newton`, over `_checked_jvp`
@@ -1771,9 +1779,164 @@ class _Cost(torch.autograd.Function):
         return grads + (None, None) + gb()
 
 
+def _nearfield_chunks(op, counts, psi, probe, scan, H, visit):
+    """Per chunk of whole frames of the near-field form: visit(lo, hi, sc, d,
+    how, bufs), how / bufs those of `operators.nearfield.wave_and_back`."""
+    from .operators import nearfield as NF
+    from .ptycho.solvers.lstsq import _workspace
+    fly, N = counts.fly, scan.shape[0]
+    S, det = probe.shape[2], op.detector_shape
+    how = NF.route(op.probe_shape, det, S)
+    chunk = _chunk_rows(op, probe, fly)
+    bufs = NF.buffers(_workspace(op), psi.device, max(min(chunk, N), 1), S,
+                      det, fly, how)
+    for lo in range(0, N, chunk):
+        hi = min(N, lo + chunk)
+        visit(lo, hi, scan[lo:hi], counts.data[lo // fly:hi // fly], how, bufs)
+
+
+class _NearfieldCost(torch.autograd.Function):
+    """The per-frame cost with the detector in the near field
+    (`operators.nearfield`): one slice, the shared probe.  Forward: the chain
+    with out = NULL.  Backward: the chunk again with grad_output for the
+    upstream, the adjoint Fresnel step, its inverse finished to chi
+    (tike_fft2_pass2_inplace on the fused routes), then the tail of `_Back`:
+    tike_lstsq_gradients, tike_scatter_patches, tike_scan_gradient."""
+
+    @staticmethod
+    def forward(ctx, psi, probe, scan, operator, counts, H):
+        from .operators import nearfield as NF
+        psi, probe, scan = (x.detach().contiguous() for x in (psi, probe, scan))
+        ctx.operator, ctx.counts, ctx.H = operator, counts, H
+        ctx.save_for_backward(psi, probe, scan)
+        A.current_device()
+        costs = torch.empty(scan.shape[0] // counts.fly, dtype=torch.float32,
+                            device=psi.device)
+
+        def visit(lo, hi, sc, d, how, bufs):
+            fly = counts.fly
+            NF.wave_and_back(operator, psi, sc, probe, H, d, fly, how, bufs,
+                             model=counts.model, measured=counts.mask,
+                             num_measured=counts.nm,
+                             costs=costs[lo // fly:hi // fly])
+
+        _nearfield_chunks(operator, counts, psi, probe, scan, H, visit)
+        return costs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from .operators import nearfield as NF
+        psi, probe, scan = ctx.saved_tensors
+        op, counts, H = ctx.operator, ctx.counts, ctx.H
+        fly, det, S = counts.fly, op.detector_shape, probe.shape[2]
+        Hh, W = psi.shape[-2:]
+        g = g.to(torch.float32).contiguous()
+        A.current_device()
+        want_psi, want_probe, want_scan = ctx.needs_input_grad[:3]
+        dev = psi.device
+        acc = (torch.zeros((2, Hh, W), dtype=torch.float32, device=dev)
+               if want_psi else None)
+        gprobe = torch.zeros_like(probe) if want_probe else None
+        gscan = torch.empty_like(scan) if want_scan else None
+        need_proj = want_psi or want_scan
+        proj = {}
+        inv_scale = fft_scales(det, op.norm)[1]
+
+        def visit(lo, hi, sc, d, how, bufs):
+            n, st = hi - lo, A.stream_ptr()
+            # the 2 of torch's gradient of a real function of a complex leaf
+            chi, finished = NF.wave_and_back(
+                op, psi, sc, probe, H, d, fly, how, bufs, model=counts.model,
+                measured=counts.mask, num_measured=counts.nm,
+                upstream=g[lo // fly:hi // fly], scale=2.0, want_back=True)
+            if not finished:
+                check(
+                    lib.tike_fft2_pass2_inplace(A.ptr(chi), n * S, det, 1,
+                                                inv_scale, st),
+                    "nearfield cost backward (inverse pass 2)")
+            objproj = None
+            if need_proj:
+                if "p" not in proj or proj["p"].shape[0] < n:
+                    proj["p"] = torch.empty((n, det, det),
+                                            dtype=torch.complex64, device=dev)
+                objproj = proj["p"][:n]
+            check(
+                lib.tike_lstsq_gradients(A.ptr(chi), A.ptr(sc), A.ptr(psi),
+                                         A.ptr(probe), None, None, 0, 0, None,
+                                         None, A.ptr(gprobe), A.ptr(objproj),
+                                         n, S, det, Hh, W, st),
+                "nearfield cost backward (probe gradient + object projection)")
+            if want_psi:
+                check(
+                    lib.tike_scatter_patches(A.ptr(objproj), A.ptr(sc),
+                                             A.ptr(acc), n, det, Hh, W, st),
+                    "nearfield cost backward (object gradient)")
+            if want_scan:
+                check(
+                    lib.tike_scan_gradient(A.ptr(objproj), A.ptr(sc),
+                                           A.ptr(psi), A.ptr(gscan[lo:hi]), n,
+                                           det, Hh, W, st),
+                    "nearfield cost backward (scan gradient)")
+
+        _nearfield_chunks(op, counts, psi, probe, scan, H, visit)
+        gpsi = torch.complex(acc[0], acc[1])[None] if want_psi else None
+        return gpsi, gprobe, gscan, None, None, None
+
+
+def _checked_nearfield(name, operator, nearfield, psi, eigen_probe,
+                       eigen_weights, binning, background, blur):
+    """The propagator of `cost`, detached and contiguous on the device, after
+    its refusals."""
+    from .operators import nearfield as NF
+    if isinstance(nearfield, torch.Tensor) and nearfield.requires_grad:
+        raise NotImplementedError(
+            f"{name}: nearfield that requires a gradient is not implemented: "
+            "the propagator is used as given")
+    if eigen_probe is not None or eigen_weights is not None:
+        raise NotImplementedError(
+            f"{name}: nearfield with eigen probes is not implemented")
+    if isinstance(psi, torch.Tensor) and psi.ndim == 3 and psi.shape[0] > 1:
+        raise NotImplementedError(
+            f"{name}: nearfield with several slices (psi.shape[0] = "
+            f"{psi.shape[0]}) is not implemented")
+    if binning != 1:
+        raise NotImplementedError(
+            f"{name}: nearfield with binning={binning} is not implemented")
+    if background is not None:
+        raise NotImplementedError(
+            f"{name}: nearfield with a background is not implemented")
+    if blur is not None:
+        raise NotImplementedError(
+            f"{name}: nearfield with a blur is not implemented")
+    if not isinstance(nearfield, torch.Tensor):
+        raise TypeError(
+            f"{name}: nearfield must be a torch device tensor, not "
+            f"{type(nearfield).__name__}")
+    if nearfield.dtype != torch.complex64:
+        raise TypeError(
+            f"{name}: nearfield must be torch.complex64, not "
+            f"{nearfield.dtype}")
+    det = operator.detector_shape
+    if tuple(nearfield.shape) != (det, det):
+        raise ValueError(
+            f"{name}: nearfield must be ({det}, {det}), not "
+            f"{tuple(nearfield.shape)}")
+    if operator.probe_shape != det:
+        raise NotImplementedError(
+            f"{name}: nearfield with probe window {operator.probe_shape} != "
+            f"detector {det}: the probe fills the frame in this geometry")
+    if nearfield.device.type != "cuda":
+        raise TypeError(
+            f"{name}: nearfield lives on {nearfield.device}; tike_amd runs on "
+            "the GPU only and there is no CPU fallback")
+    return NF.device_propagator(nearfield.detach(), det)
+
+
 def cost(operator, data, psi, probe, scan, *, model="gaussian",
          measured_pixels=None, eigen_probe=None, eigen_weights=None, fly=1,
-         binning=1, check_positions=True, background=None, blur=None):
+         binning=1, check_positions=True, background=None, blur=None,
+         nearfield=None):
     """The per-frame cost (N // fly,) float32 of the model's intensity against
     the counts `data` (N // fly, det, det) float32 or uint16 under the
     project's noise models -- "gaussian": mean of (sqrt(I) - sqrt(d))^2,
@@ -1825,6 +1988,19 @@ def cost(operator, data, psi, probe, scan, *, model="gaussian",
     gradient: the sum of the chunks' tike_blur_kernel_sums, float64, rounded
     once.  NotImplementedError with binning > 1 or with a background.
 
+    nearfield: a (det, det) complex64 device tensor H in FFT order, used as
+    given (it takes no gradient): the detector sits in the near field, probe
+    window = detector, and the intensity is |IFFT2(H FFT2(patch x probe))|^2
+    summed over the modes and the `fly` positions of a frame
+    (ptycho.NearFieldOptions; data and measured_pixels in the natural layout of
+    the detector).  One slice, the shared probe; exact gradients with respect
+    to psi, probe and scan.  At 128^2 and 256^2 the forward is tike_fwd_pass1
+    -> tike_fresnel_colpass -> tike_nearfield_plane_gradient with out = NULL:
+    the detector-plane wave never exists in memory.  ``cost(...).mean()`` is
+    ``Ptycho.cost(..., nearfield=H)``.  NotImplementedError with eigen probes,
+    several slices, binning > 1, a background, a blur, or an H that requires a
+    gradient; `cost_jvp` and `cost_gauss_newton_product` take no nearfield.
+
     Raises what the form's intensity raises, ValueError for a binning that is
     no integer >= 1 or does not divide the far-plane width, TypeError / ValueError for data
     or measured_pixels of another type, dtype or shape, ValueError for a mask
@@ -1841,6 +2017,11 @@ def cost(operator, data, psi, probe, scan, *, model="gaussian",
     fly, data, mask, nm, model = _checked_cost(
         name, operator, data, measured_pixels, model, psi, probe, scan,
         eigen_probe, eigen_weights, fly, check_positions, checked, binning)
+    if nearfield is not None:
+        H = _checked_nearfield(name, operator, nearfield, psi, eigen_probe,
+                               eigen_weights, binning, background, blur)
+        return _NearfieldCost.apply(psi, probe, scan, operator,
+                                    _Counts(data, mask, nm, model, fly), H)
     b = (None if background is None else
          _checked_background(name, operator, background, binning))
     K = (None if blur is None else

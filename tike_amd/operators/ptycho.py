@@ -13,6 +13,7 @@ import torch
 from .. import _tuning
 from .. import _arrays as A
 from .._lib import check, lib
+from . import nearfield as NF
 from . import objective
 from .multislice import Multislice
 from .operator import Operator
@@ -454,15 +455,64 @@ class Ptycho(Operator):
                 f"not {tuple(b.shape)}")
         return b
 
+    def _device_nearfield(self, nearfield, binning, psi, probe, background,
+                          blur):
+        """The propagator of `_compute_intensity` and `cost` on the device,
+        after their refusals."""
+        if binning > 1:
+            raise ValueError(
+                "nearfield together with binning > 1 is not supported")
+        if background is not None:
+            raise ValueError(
+                "nearfield together with a background is not supported")
+        if blur is not None:
+            raise ValueError("nearfield together with a blur is not supported")
+        if psi.shape[0] > 1:
+            raise ValueError(
+                "nearfield together with several object slices is not "
+                "supported")
+        if probe.shape[-1] != self.detector_shape or (
+                self.probe_shape != self.detector_shape):
+            raise ValueError(
+                f"nearfield needs probe window = detector, not "
+                f"{probe.shape[-1]} and {self.detector_shape}")
+        return NF.device_propagator(nearfield, self.detector_shape)
+
+    def _nearfield_inputs(self, psi, scan, probe, fly):
+        psi = A.to_device(psi, np.complex64)
+        scan = A.to_device(scan, np.float32)
+        probe = A.to_device(probe, np.complex64)
+        if scan.shape[0] % fly:
+            raise ValueError(
+                f"{scan.shape[0]} scan positions are not a multiple of "
+                f"fly={fly}")
+        return psi, scan, probe
+
     def _compute_intensity(self, data, psi, scan, probe, fly=1, binning=1,
-                           background=None, blur=None):
+                           background=None, blur=None, nearfield=None):
         """(intensity (FRAME,det,det), farplane) -- ptycho.py:178-191; with
         fly > 1 a frame is the sum over `fly` consecutive positions
         (ptycho.py:104-125); with binning = B > 1 the intensity is
         (FRAME, det // B, det // B), a pixel the sum over its B x B far-plane
         pixels (`binned_farplane_gradient`); with a background (det, det) the
         intensity includes it; with a blur (k, k) the intensity is convolved
-        with it, cyclically over the plane (`blur_cost_factor`)."""
+        with it, cyclically over the plane (`blur_cost_factor`); with nearfield
+        (det, det) complex64 the detector sits in the near field: the
+        intensity is |IFFT2(nearfield FFT2(patch x probe))|^2 and the second
+        result is that detector-plane wave (`operators.nearfield`)."""
+        if nearfield is not None:
+            psi_d, scan_d, probe_d = self._nearfield_inputs(psi, scan, probe,
+                                                            fly)
+            H = self._device_nearfield(nearfield, binning, psi_d, probe_d,
+                                       background, blur)
+            w = NF.detector_wave(self, psi_d, scan_d, probe_d, H)
+            N, S, det, _ = w.shape
+            intensity = torch.empty((N // fly, det, det), dtype=torch.float32,
+                                    device=w.device)
+            self.fly_farplane_gradient(w, torch.zeros_like(intensity), fly,
+                                       intensity=intensity)
+            return (A.like_input(intensity, psi),
+                    A.like_input(w.view(N, 1, S, det, det), psi))
         if blur is not None:
             K = self._device_blur(blur, binning,
                                   A.to_device(psi, np.complex64), background)
@@ -507,12 +557,38 @@ class Ptycho(Operator):
         return A.like_input(intensity, kind), A.like_input(far, kind)
 
     def cost(self, data, psi, scan, probe, *, model, fly=1, binning=1,
-             background=None, blur=None):
+             background=None, blur=None, nearfield=None):
         """ptycho.py:193-204; with fly > 1 or binning > 1 the mean over frames
         of the cost of each frame's summed (and binned) intensity; with a
         background (det, det) the cost of intensity + background
         (`background_farplane_gradient`); with a blur (k, k) the cost of
-        blur (*) intensity (`blur_cost_factor` on the stored intensities)."""
+        blur (*) intensity (`blur_cost_factor` on the stored intensities); with
+        nearfield (det, det) complex64 the mean over frames of the cost of
+        |IFFT2(nearfield FFT2(patch x probe))|^2 (`operators.nearfield`, the
+        general route)."""
+        if nearfield is not None:
+            if model not in objective._MODELS:
+                raise ValueError(f"unknown noise model {model!r}")
+            psi_d, scan_d, probe_d = self._nearfield_inputs(psi, scan, probe,
+                                                            fly)
+            H = self._device_nearfield(nearfield, binning, psi_d, probe_d,
+                                       background, blur)
+            counts = A.to_device(data)
+            if counts.dtype not in (torch.float32, torch.uint16):
+                counts = counts.to(torch.float32)
+            if counts.shape[0] * fly != scan_d.shape[0]:
+                raise ValueError(
+                    f"{counts.shape[0]} frames of fly={fly} do not match "
+                    f"{scan_d.shape[0]} scan positions")
+            costs = torch.empty(counts.shape[0], dtype=torch.float32,
+                                device=psi_d.device)
+            S, det = probe_d.shape[-3], self.detector_shape
+            NF.wave_and_back(
+                self, psi_d, scan_d, probe_d, H, counts.contiguous(), fly,
+                "general", NF.buffers(None, psi_d.device, 0, S, det, fly,
+                                      "general", table=False),
+                model=objective._MODELS[model], costs=costs)
+            return A.like_input(costs.mean(), psi)
         if blur is not None:
             if model not in objective._MODELS:
                 raise ValueError(f"unknown noise model {model!r}")

@@ -1,6 +1,7 @@
 """Ptychography solvers and helpers (mirror of ``tike.ptycho``)."""
 from .background import BackgroundOptions
 from .blur import BlurOptions
+from .nearfield import NearFieldOptions
 from .exitwave import ExitWaveOptions
 from .fresnel import MW_probe, single_probe
 from .object import (ObjectOptions, get_absorbtion_image, get_padded_object,
@@ -24,7 +25,7 @@ from . import probe, object, position, exitwave, solvers, io, learn, fresnel  # 
 
 __all__ = [
     "BackgroundOptions", "BlurOptions", "CgradOptions", "DmOptions", "ExitWaveOptions", "LstsqOptions",
-    "ObjectOptions",
+    "NearFieldOptions", "ObjectOptions",
     "AffineTransform", "PositionOptions", "affine_position_regularization",
     "ProbeOptions", "PtychoParameters", "Reconstruction",
     "RpieOptions", "cgrad", "check_allowed_positions", "dm", "lstsq_grad",

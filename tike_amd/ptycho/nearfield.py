@@ -1,0 +1,142 @@
+"""Near-field (Fresnel, holographic) ptychography: the detector a finite
+distance behind the sample (no reference counterpart).
+
+In the far field every pattern is |FFT2(pad(patch x probe))|^2.  In the near
+field -- a diffuser structures the beam, the probe fills the whole frame, the
+detector sits a finite distance z behind the sample (Stockmar et al. 2013) --
+the wave on the detector is one Fresnel step of the exit wave:
+
+    w = IFFT2(H . FFT2(patch x probe)),   I[f] = sum_{j < fly * S} |w[f][j]|^2
+
+with probe window = detector.  H (det, det) complex64 is the propagator on the
+FFT's own frequency order, the one `operators.fresnelspectprop` builds for the
+step between two slices of a multislice object.  It is used as given: it is
+not fitted (refining the distance is out of scope).
+
+Nothing about the data is FFT-shifted in this geometry: the frames and
+`measured_pixels` are in the natural, unshifted layout of the detector, pixel
+(y, x) of a frame behind pixel (y, x) of the probe window.
+
+With a magnified (cone-beam) geometry, source-to-sample z1 and
+sample-to-detector z2, the Fresnel scaling theorem maps the measurement onto a
+parallel-beam one: pass the EFFECTIVE distance z1 z2 / (z1 + z2) and the
+EFFECTIVE pixel size (the detector's divided by the magnification
+(z1 + z2) / z1) to `from_geometry`.
+
+`NearFieldOptions` hands the propagator to `reconstruct(...,
+nearfield_options=)`; cgrad is the solver.
+"""
+from __future__ import annotations
+
+import dataclasses
+
+import numpy as np
+
+from .. import _arrays as A
+from ..operators.fresnelspectprop import fresnel_spectrum_propagator
+
+
+def checked_propagator(propagator, det, what="nearfield"):
+    """`propagator` as a host (det, det) complex64 array, after validation of
+    its shape, dtype and finiteness."""
+    H = propagator
+    if A.is_device(H):
+        if H.requires_grad:
+            raise ValueError(
+                f"{what} that requires a gradient is not supported: the "
+                "propagator is used as given")
+        H = A.to_host(H)
+    H = np.asarray(H)
+    if H.ndim != 2 or H.shape != (det, det):
+        raise ValueError(
+            f"{what} has shape {H.shape}; expected ({det}, {det}), the "
+            "detector's shape")
+    if H.dtype != np.complex64:
+        raise ValueError(f"{what} is {H.dtype}; expected complex64")
+    if not np.all(np.isfinite(H)):
+        raise ValueError(f"{what} must be finite")
+    return np.ascontiguousarray(H)
+
+
+@dataclasses.dataclass
+class NearFieldOptions:
+    """The detector-plane geometry of `reconstruct(..., nearfield_options=)`."""
+
+    propagator: np.ndarray
+    """(det, det) complex64, finite, on the FFT's own frequency order
+    (element [0, 0] is the zero frequency): the transfer function of free
+    space between the sample and the detector.  Used as given."""
+
+    @classmethod
+    def from_geometry(cls, det, pixel_size, distance, wavelength):
+        """The Fresnel spectrum propagator
+        (`operators.fresnelspectprop.fresnel_spectrum_propagator`) of a
+        (det, det) window of `pixel_size` pixels over `distance`, all lengths
+        in one unit.  Cone beam: the effective distance and the effective
+        pixel size of the Fresnel scaling theorem (module docstring)."""
+        det = int(det)
+        fov = det * float(pixel_size)
+        return cls(fresnel_spectrum_propagator((det, det), (fov, fov),
+                                               float(distance),
+                                               float(wavelength)))
+
+
+def refuse(options, parameters, det, *, binning=1, data_on_host=False,
+           local_data=None, world_size=1, background_options=None,
+           blur_options=None):
+    """Raise, by name, for everything a near-field reconstruction cannot be
+    combined with, before any device work; the checked propagator
+    otherwise."""
+    if not isinstance(options, NearFieldOptions):
+        raise TypeError(
+            "nearfield_options must be a tike_amd.ptycho.NearFieldOptions, "
+            f"not {type(options).__name__}")
+    name = parameters.algorithm_options.name
+    if name != "cgrad":
+        raise NotImplementedError(
+            f"nearfield_options with {name}: a near-field detector plane is "
+            "reconstructed by cgrad only")
+    if binning > 1:
+        raise NotImplementedError(
+            f"nearfield_options with binning={binning}: binned near-field "
+            "data is not implemented")
+    if background_options is not None:
+        raise NotImplementedError(
+            "nearfield_options with background_options: a background "
+            "together with a near-field detector plane is not implemented")
+    if blur_options is not None:
+        raise NotImplementedError(
+            "nearfield_options with blur_options: a blur together with a "
+            "near-field detector plane is not implemented")
+    if parameters.psi.shape[0] > 1:
+        raise NotImplementedError(
+            "nearfield_options with several slices (psi.shape[0] = "
+            f"{parameters.psi.shape[0]}): a multislice near-field "
+            "reconstruction is not implemented")
+    if (parameters.eigen_probe is not None
+            or parameters.eigen_weights is not None):
+        raise NotImplementedError(
+            "nearfield_options with eigen probes is not implemented")
+    if parameters.position_options is not None:
+        raise NotImplementedError(
+            "nearfield_options with position_options: position correction "
+            "in the near field is not implemented")
+    if data_on_host:
+        raise NotImplementedError(
+            "nearfield_options with data_on_host: the near-field route reads "
+            "the minibatch's frames in HBM")
+    if local_data is not None:
+        raise NotImplementedError(
+            "nearfield_options with local_data (the ranks started by "
+            "reconstruct(num_gpu=N)) is not implemented")
+    if world_size > 1:
+        raise NotImplementedError(
+            "nearfield_options with the ranks of a torch.distributed job: a "
+            "near-field reconstruction runs in one process")
+    pw = parameters.probe.shape[-1]
+    if pw != det:
+        raise NotImplementedError(
+            f"nearfield_options with probe window {pw} != detector {det}: "
+            "the probe fills the frame in this geometry")
+    return checked_propagator(options.propagator, det,
+                              "nearfield_options.propagator")

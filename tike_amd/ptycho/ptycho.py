@@ -44,6 +44,8 @@ from .probe import (apply_median_filter_abs_probe, constrain_center_peak,
                     rescale_probe_using_fixed_intensity_photons)
 from . import background as _background
 from . import blur as _blur
+from . import nearfield as _nearfield
+from ..operators import nearfield as _NF
 from .solvers.cgrad import _refuse_binning, _refuse_fly, _refuse_multislice
 from .solvers.dm import refuse as _refuse_dm
 from .solvers.lstsq import chunk_positions, mask_info
@@ -54,13 +56,15 @@ logger = logging.getLogger(__name__)
 
 def _intensity_chunks(operator, psi, scan, probe, eigen_probe=None,
                       eigen_weights=None, fly=1, binning=1, background=None,
-                      blur=None):
+                      blur=None, nearfield=None):
     """Yield (lo, hi, intensity (n, det, det)) over chunks of frames; frame f
     is the sum over the positions f * fly ... f * fly + fly - 1.  With
     binning = B > 1 the intensity is (n, det // B, det // B), a pixel the sum
     over its B x B far-plane pixels.  background (det, det) float32 or None
     is added to every frame; blur (k, k) float32 or None is the kernel every
-    frame is convolved with, cyclically (`Ptycho.blur_cost_factor`)."""
+    frame is convolved with, cyclically (`Ptycho.blur_cost_factor`);
+    nearfield (det, det) complex64 or None is the propagator between the
+    sample and a detector in the near field (`operators.nearfield`)."""
     N = scan.shape[0]
     S = probe.shape[-3]
     det = operator.detector_shape
@@ -73,6 +77,16 @@ def _intensity_chunks(operator, psi, scan, probe, eigen_probe=None,
     for lo in range(0, N, chunk):
         hi = min(N, lo + chunk)
         w = None if eigen_weights is None else eigen_weights[lo:hi]
+        if nearfield is not None:
+            inten = torch.empty(((hi - lo) // fly, det, det),
+                                dtype=torch.float32, device=psi.device)
+            _NF.wave_and_back(
+                operator, psi, scan[lo:hi], probe, nearfield, None, fly,
+                "general", _NF.buffers(None, psi.device, 0, S, det, fly,
+                                       "general", table=False),
+                intensity=inten)
+            yield lo // fly, hi // fly, inten
+            continue
         if psi.shape[0] > 1:  # several slices: the Multislice composition
             far = operator.fwd(probe=get_varying_probe(probe, eigen_probe, w),
                                scan=scan[lo:hi], psi=psi).contiguous()
@@ -103,7 +117,7 @@ def _intensity_chunks(operator, psi, scan, probe, eigen_probe=None,
 
 def simulate(detector_shape, probe, scan, psi, fly=1, eigen_probe=None,
              eigen_weights=None, binning=1, background=None, blur=None,
-             **kwargs):
+             nearfield=None, **kwargs):
     """Real-valued detector counts of simulated ptychography data
     (ptycho.py:128-179).  Returns (FRAME, det, det) float32 on the host.
     binning = B > 1: `detector_shape` stays the far-plane width, a measured
@@ -113,8 +127,16 @@ def simulate(detector_shape, probe, scan, psi, fly=1, eigen_probe=None,
     every frame.  blur: a (k, k) float32 kernel >= 0, k in (3, 5, 7), the
     centre at [k // 2, k // 2]: normalised to sum 1, then every frame is
     convolved with it, cyclically over the (det, det) plane in the stored
-    layout (the detector's opposite edges joined; `ptycho.blur`)."""
+    layout (the detector's opposite edges joined; `ptycho.blur`).
+    nearfield: a (det, det) complex64 propagator in FFT order
+    (`ptycho.nearfield`): the detector sits in the near field, probe window =
+    detector, every frame is |IFFT2(nearfield FFT2(patch x probe))|^2 in the
+    natural, unshifted layout of the detector."""
     binning = _checked_binning(binning, int(detector_shape))
+    if nearfield is not None:
+        nearfield = _checked_simulated_nearfield(
+            nearfield, int(detector_shape), binning, psi, probe, eigen_probe,
+            eigen_weights, background, blur)
     if blur is not None:
         blur = _checked_simulated_blur(blur, int(detector_shape), binning,
                                        psi, eigen_probe, eigen_weights,
@@ -138,8 +160,35 @@ def simulate(detector_shape, probe, scan, psi, fly=1, eigen_probe=None,
                 background=None if background is None else operator.asarray(
                     background, dtype=real),
                 blur=None if blur is None else operator.asarray(
-                    blur, dtype=real).contiguous())])
+                    blur, dtype=real).contiguous(),
+                nearfield=None if nearfield is None else operator.asarray(
+                    nearfield, dtype=cplx).contiguous())])
         return operator.asnumpy(frames)
+
+
+def _checked_simulated_nearfield(nearfield, det, binning, psi, probe,
+                                 eigen_probe, eigen_weights, background, blur):
+    """The propagator of `simulate` as a host array, after its refusals."""
+    if binning > 1:
+        raise NotImplementedError(
+            f"nearfield with binning={binning} is not implemented")
+    if background is not None:
+        raise NotImplementedError(
+            "nearfield with a background is not implemented")
+    if blur is not None:
+        raise NotImplementedError("nearfield with a blur is not implemented")
+    if psi.shape[0] > 1:
+        raise NotImplementedError(
+            f"nearfield with several slices (psi.shape[0] = {psi.shape[0]}) "
+            "is not implemented")
+    if eigen_probe is not None or eigen_weights is not None:
+        raise NotImplementedError(
+            "nearfield with eigen probes is not implemented")
+    if probe.shape[-1] != det:
+        raise NotImplementedError(
+            f"nearfield with probe window {probe.shape[-1]} != detector "
+            f"{det}: the probe fills the frame in this geometry")
+    return _nearfield.checked_propagator(nearfield, det)
 
 
 def _checked_simulated_blur(blur, det, binning, psi, eigen_probe,
@@ -187,7 +236,7 @@ def _checked_simulated_background(background, det, binning, psi, eigen_probe,
 
 def reconstruct(data, parameters, num_gpu=None, use_mpi=False, *, fly=1,
                 binning=1, background_options=None, blur_options=None,
-                **kwargs):
+                nearfield_options=None, **kwargs):
     """Solve the ptychography problem (ptycho.py:182-262).
 
     data (FRAME, WIDE, HIGH): measured intensities, FFT-shifted so that the
@@ -224,6 +273,12 @@ def reconstruct(data, parameters, num_gpu=None, use_mpi=False, *, fly=1,
     kernel (partial spatial coherence, the detector's point-spread function;
     cyclic over the detector plane) and, unless told otherwise, fits the
     kernel.  The fitted kernel is left in `blur_options.kernel`.
+
+    nearfield_options (keyword only): a `NearFieldOptions`; the detector then
+    sits in the near field -- every pattern is |IFFT2(H FFT2(patch x
+    probe))|^2 with the given propagator H, probe window = detector, data and
+    `measured_pixels` in the natural, unshifted layout of the detector -- and
+    cgrad is the solver (`ptycho.nearfield`).
     """
     if use_mpi:
         raise NotImplementedError(
@@ -256,6 +311,12 @@ def reconstruct(data, parameters, num_gpu=None, use_mpi=False, *, fly=1,
             f"blur_options with reconstruct(num_gpu={num_gpu!r}) from a plain "
             "process: the ranks this call would start do not fit a blur "
             "kernel")
+    if (nearfield_options is not None and requested is not None
+            and len(requested) > 1 and _spawn.world_size() == 1):
+        raise NotImplementedError(
+            f"nearfield_options with reconstruct(num_gpu={num_gpu!r}) from a "
+            "plain process: the ranks this call would start do not take a "
+            "near-field detector plane")
     how, where = _spawn.resolve(num_gpu)
     if how == "spawn":
         return _spawn.reconstruct_spawned(data, parameters, where, **kwargs)
@@ -264,6 +325,7 @@ def reconstruct(data, parameters, num_gpu=None, use_mpi=False, *, fly=1,
                         use_mpi, fly=fly, binning=binning,
                         background_options=background_options,
                         blur_options=blur_options,
+                        nearfield_options=nearfield_options,
                         **kwargs) as context:
         context.iterate(parameters.algorithm_options.num_iter)
         result = context.get_result()
@@ -272,7 +334,7 @@ def reconstruct(data, parameters, num_gpu=None, use_mpi=False, *, fly=1,
 
 def reconstruct_multigrid(data, parameters, num_gpu=None, use_mpi=False,
                           num_levels=3, interp=None, *, binning=1,
-                          blur_options=None):
+                          blur_options=None, nearfield_options=None):
     """Coarse-to-fine reconstruction (ptycho.py:975-1047): the real-space
     parameters are downsampled by 2^(num_levels-1) and the diffraction
     patterns cropped in Fourier space, every level runs
@@ -286,6 +348,10 @@ def reconstruct_multigrid(data, parameters, num_gpu=None, use_mpi=False,
         raise NotImplementedError(
             "blur_options with reconstruct_multigrid: a blur kernel of "
             "diffraction patterns cropped in Fourier space is not implemented")
+    if nearfield_options is not None:
+        raise NotImplementedError(
+            "nearfield_options with reconstruct_multigrid: near-field frames "
+            "are not cropped in Fourier space")
     data = A.to_host(data)
     coarsest = 2**(num_levels - 1)
     if data.shape[-1] / coarsest < 64:
@@ -547,17 +613,24 @@ class Reconstruction():
         be cgrad with a shared probe, one slice, no binning, no background,
         no position correction and HBM-resident data, in one process.
         `get_result()` leaves the fitted kernel in `blur_options.kernel`.
+      nearfield_options: a `NearFieldOptions` (default None).  The detector
+        then sits in the near field (`ptycho.nearfield`): every pattern is
+        |IFFT2(H FFT2(patch x probe))|^2 with the given propagator; the solver
+        must be cgrad with a shared probe, one slice, probe window =
+        detector, no binning, no background, no blur, no position correction
+        and HBM-resident data, in one process.  Any `fly`.
     """
 
     fly = 1  # scan positions per diffraction pattern
     binning = 1  # far-plane pixels per measured pixel, per axis
     _blur = None  # (blur_options, its normalised kernel) or None
+    _nearfield = None  # the checked propagator (host) or None
 
     def __init__(self, data, parameters, num_gpu=None, use_mpi=False, *,
                  presharded=False, order=None, batches=None,
                  spatial_sort=True, data_on_host=False, local_data=None,
                  fly=1, binning=1, background_options=None,
-                 blur_options=None):
+                 blur_options=None, nearfield_options=None):
         # a context lives in ONE process with ONE GPU: `num_gpu` must agree
         # with the process group it runs in (`reconstruct` is the entry that
         # starts ranks by itself)
@@ -602,6 +675,13 @@ class Reconstruction():
                 binning=binning, data_on_host=data_on_host,
                 local_data=local_data, world_size=_spawn.world_size(),
                 background_options=background_options)
+        if nearfield_options is not None:
+            self._nearfield = _nearfield.refuse(
+                nearfield_options, parameters, data.shape[-1],
+                binning=binning, data_on_host=data_on_host,
+                local_data=local_data, world_size=_spawn.world_size(),
+                background_options=background_options,
+                blur_options=blur_options)
         name = parameters.algorithm_options.name
         if not hasattr(solvers, name):
             raise NotImplementedError(
@@ -658,6 +738,7 @@ class Reconstruction():
         self.operator.background = None
         self._blur = None if blur is None else (blur_options, blur)
         self.operator.blur = None
+        self.operator.nearfield = None  # (cgrad reads it; set on entry)
         self.comm = Comm()
         self._pending_fits = []  # futures of deferred affine position fits
         self._free_snaps = []  # pinned host buffers of finished fits
@@ -757,6 +838,9 @@ class Reconstruction():
             self.operator.background = _background.State(*self._background)
         if self._blur is not None:
             self.operator.blur = _blur.State(*self._blur)
+        if self._nearfield is not None:
+            self.operator.nearfield = _NF.device_propagator(
+                self._nearfield, self.operator.detector_shape)
         self.parameters = solvers.PtychoParameters.split(
             self.local_order,
             x=self._host_parameters()).copy_to_device()
@@ -848,6 +932,10 @@ class Reconstruction():
         returns the same cost.  `parameters.scan` is replaced only after the
         test has passed.  `position_options` is neither needed nor touched."""
         from .solvers.rpie import _positions_flag, _raise_unless_allowed
+        if self._nearfield is not None:
+            raise NotImplementedError(
+                "nearfield_options with update_positions_pd: position "
+                "refinement in the near field is not implemented")
         if self._blur is not None:
             raise NotImplementedError(
                 "blur_options with update_positions_pd: position refinement "

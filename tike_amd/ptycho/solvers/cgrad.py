@@ -62,6 +62,13 @@ no variable is recovered, one cost-only evaluation.
   gradient.  The third conjugate-gradient call is on a: the minibatch's
   intensities are stored once and every gradient and line-search trial is one
   ``tike_blur_kernel_sums`` launch and k * k numbers of chain in torch.
+* a detector in the near field (the operator's ``nearfield``, set by
+  ``nearfield_options``; no reference counterpart): every pattern is
+  |IFFT2(H FFT2(patch x probe))|^2, probe window = detector, H a fixed
+  propagator.  Whole frames at any ``fly``, also 1:
+  ``_nearfield_cost_and_grad``, whose middle on the 128^2 / 256^2 route is one
+  launch, ``tike_nearfield_plane_gradient`` -- the detector-plane wave never
+  exists in memory.
 * objects of several slices (``psi.shape[0] > 1``, probe window = detector):
   the same cost on the far field behind the last slice, e_d = patch(O_d) x
   beam_d, beam_{d+1} = Fresnel(e_d), and its EXACT gradient -- the adjoint
@@ -86,6 +93,7 @@ from ... import _tuning
 from ... import _arrays as A
 from ... import opt
 from ..._lib import check, lib
+from ...operators import nearfield as NF
 from ...operators.propagation import fft_scales
 from .. import blur as _blur
 from ..exitwave import ExitWaveOptions
@@ -968,6 +976,96 @@ def _fly_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, fly, *,
     return costs.sum(dtype=torch.float64), gpsi, gprobe
 
 
+def _nearfield_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, fly, *,
+                             want_psi, want_probe, want_grad, cm, H):
+    """(sum of the per-frame costs, a device scalar; d cost / d psi or None;
+    d cost / d probe or None -- unnormalised adjoints, as `_fly_cost_and_grad`
+    returns them) of the positions [lo, hi), whole frames, with the detector in
+    the NEAR field: every frame is |IFFT2(H FFT2(patch x probe))|^2 summed over
+    its positions and modes, H (det, det) the operator's `nearfield`
+    (ptycho/nearfield.py; operators/nearfield.py has the three routes).  Per
+    chunk of whole frames, on the fused route: tike_fwd_pass1 ->
+    tike_fresnel_colpass(H) -> tike_nearfield_plane_gradient (a cost-only
+    evaluation, a line-search probe, stops here with out = NULL: nothing
+    plane-sized is written) -> tike_fresnel_colpass(conj H) ->
+    tike_ifft2_pass2_products -> tike_scatter_patches: about 8 crossings of
+    the planes per gradient evaluation.  upstream = num_measured and scale =
+    -1 (the blur route's convention): the wave carries MINUS the unnormalised
+    gradient."""
+    assert lo % fly == 0 and hi % fly == 0, (lo, hi, fly)
+    dev = psi.device
+    S, det = probe.shape[-3], op.detector_shape
+    Hh, W = psi.shape[-2:]
+    N = hi - lo
+    ws = _workspace(op)
+    how = NF.route(op.probe_shape, det, S)
+    fused = how != "general"
+    chunk = max(1, chunk_positions(S, det) // fly) * fly  # whole frames
+    nmax = min(chunk, max(N, 1))
+    bufs = NF.buffers(ws, dev, nmax, S, det, fly, how)
+    costs = ws.get("costs", (max(N // fly, 1),), torch.float32, dev)[:N // fly]
+    want_psi, want_probe = want_grad and want_psi, want_grad and want_probe
+    # (fused: the planar accumulator of the grouped scatter)
+    grads, gpsi, gprobe = _gradient_buffer(
+        psi, probe, want_psi, want_probe,
+        planar=(1, 2, Hh, W) if fused else None)
+    # upstream = num_measured: (float)(n * (1 / n)) = 1, the factor is the
+    # unnormalised l'
+    unit = ws.get("nearfield_upstream", (max(nmax // fly, 1),), torch.float32,
+                  dev)
+    unit.fill_(float(cm.nmeasured))
+    if fused and want_grad:
+        objproj = ws.get("nearfield_objproj", (nmax, det, det),
+                         torch.complex64, dev)
+    inv_scale = fft_scales(det, op.norm)[1]
+    st = A.stream_ptr()
+    for clo in range(lo, hi, chunk):
+        chi = min(hi, clo + chunk)
+        sc = scan[clo:chi]
+        n = chi - clo
+        d = data[clo // fly:chi // fly]
+        if d.dtype not in (torch.float32, torch.uint16):
+            d = d.to(torch.float32)
+        wave, finished = NF.wave_and_back(
+            op, psi, sc, probe, H, d, fly, how, bufs, model=cm.model,
+            measured=cm.mask, num_measured=cm.nmeasured,
+            upstream=unit[:n // fly], scale=-1.0,
+            costs=costs[(clo - lo) // fly:(chi - lo) // fly],
+            want_back=want_grad, unnormalised=True)
+        if not want_grad:
+            continue
+        if not finished:
+            # inverse pass 2 + object projection + probe product, as for the
+            # first slice of a multislice walk back
+            check(
+                lib.tike_ifft2_pass2_products(
+                    A.ptr(wave), A.ptr(psi[0]), A.ptr(sc), A.ptr(probe), 0,
+                    A.ptr(objproj), A.ptr(gprobe), 1.0, None, 0, n, S, det,
+                    Hh, W, inv_scale, st),
+                "nearfield cgrad: inverse pass 2 + both products")
+            if gpsi is not None:
+                check(
+                    lib.tike_scatter_patches(A.ptr(objproj), A.ptr(sc),
+                                             A.ptr(gpsi[0]), n, det, Hh, W,
+                                             st),
+                    "nearfield cgrad: object gradient")
+            continue
+        conv = op.diffraction.diffraction
+        if gpsi is not None:
+            # (Convolution.adj adds into the array it is given)
+            conv.adj(nearplane=wave, scan=sc, probe=probe[0], psi=gpsi[0])
+        if gprobe is not None:
+            gprobe += conv.adj_probe(nearplane=wave, scan=sc,
+                                     psi=psi[0]).sum(dim=0)[None, None]
+    if comm.collective and grads.numel():
+        comm.Allreduce(grads)
+    # the accumulators hold MINUS the gradients
+    if gpsi is not None:
+        gpsi = -torch.complex(gpsi[:, 0], gpsi[:, 1]) if fused else -gpsi
+    return (costs.sum(dtype=torch.float64), gpsi,
+            -gprobe if gprobe is not None else None)
+
+
 MULTISLICE_FUSED = _tuning.cgrad_multislice_fused
 """128^2, 256^2 or 512^2 tiles, probe window = detector, at most 8 modes: a
 multislice gradient runs on the two-pass kernels.  False: the general route
@@ -1120,7 +1218,7 @@ class _Minibatch:
     on_device = False
 
     def __init__(self, op, comm, data, psi, scan, probe, lo, hi, cm, fly,
-                 binning=1, background=None):
+                 binning=1, background=None, nearfield=None):
         self.where = (op, comm, data), scan, (lo, hi)
         # `background`: the state of the third block, the `State` of
         # ptycho/background.py or that of ptycho/blur.py (never both)
@@ -1130,7 +1228,17 @@ class _Minibatch:
         self.blur = blur  # the `State` of ptycho/blur.py
         self.stored = None  # `_Intensities` of the third block
         self.finish = lambda total: _finish_cost(total, comm, op, lo, hi, fly)
-        if psi.shape[0] > 1:  # (every evaluation splits into the same chunks)
+        if nearfield is not None:
+            # the detector in the near field (ptycho/nearfield.py): whole
+            # frames at any fly, also 1
+            if lo % fly or hi % fly:
+                raise ValueError(
+                    f"minibatch [{lo}, {hi}) does not hold whole frames of "
+                    f"fly={fly} positions")
+            global_count(comm, op, lo, hi)
+            self.run = _nearfield_cost_and_grad
+            self.how = dict(cm=cm, fly=fly, H=nearfield)
+        elif psi.shape[0] > 1:  # (every evaluation splits into the same chunks)
             self.run = _multislice_cost_and_grad
             self.how = dict(cm=cm, chunk=_multislice_chunk(op, psi, probe))
         elif (fly > 1 or binning > 1 or background is not None
@@ -1250,6 +1358,7 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
     background = getattr(op, "background", None)
     blur = getattr(op, "blur", None)
     third = background if blur is None else blur  # (never both: refused)
+    nearfield = getattr(op, "nearfield", None)  # (with neither: refused)
     recover = (parameters.object_options is not None,
                parameters.probe_options is not None
                and epoch >= parameters.probe_options.update_start,
@@ -1276,7 +1385,8 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
         hi = lo + len(b)
         comm.minibatch = batch_index
         mb = _Minibatch(op, comm, data, psi, scan, probe, lo, hi, cm, fly,
-                        binning, third)
+                        binning, third,
+                        **({} if nearfield is None else dict(nearfield=nearfield)))
         if positions is not None:
             positions.pending = True
             # the object's first gradient pass writes the projection the sums
