@@ -432,18 +432,8 @@ def test_cgrad_zero_background_is_the_whole_frames_route(tp, fly, monkeypatch):
                            fly, bo)
     assert np.array_equal(bo.background, np.zeros((32, 32), np.float32))
     if fly == 1:
-        whole = cg._Minibatch.__init__
-
-        def init(self, op, comm, data, psi, scan, probe, lo, hi, cm, fly,
-                 binning=1, background=None):
-            whole(self, op, comm, data, psi, scan, probe, lo, hi, cm, fly,
-                  binning, background)
-            if background is None:  # the route binning == 1 would not take
-                self.run = cg._fly_cost_and_grad
-                self.how = dict(cm=cm, fly=fly)
-                self.on_device = False
-
-        monkeypatch.setattr(cg._Minibatch, "__init__", init)
+        # the route a plain minibatch would not take
+        monkeypatch.setattr(cg, "PLAIN_ROUTE", False)
     without = _reconstruct(tp, P, data, _parameters(tp, P, "gaussian", mask),
                            fly, None)
     print(f"fly {fly}: psi {relerr(with_bo.psi, without.psi):.2e} probe "

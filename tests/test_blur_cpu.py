@@ -264,7 +264,8 @@ def test_every_refusal(monkeypatch):
             error=TypeError)
     # update_positions_pd of a context with a blur
     ctx = tp.Reconstruction.__new__(tp.Reconstruction)
-    ctx._blur = (good(), bl.first_guess())
+    from tike_amd.operators.detector import Detector
+    ctx._detector = Detector("blur", 1, bl.first_guess())
     with pytest.raises(NotImplementedError,
                        match="blur_options with update_positions_pd"):
         ctx.update_positions_pd()

@@ -513,18 +513,8 @@ def test_cgrad_delta_kernel_is_the_whole_frames_route(tp, fly, monkeypatch):
                            fly, bo)
     assert np.array_equal(bo.kernel, bl.delta_kernel(3))
     if fly == 1:
-        whole = cg._Minibatch.__init__
-
-        def init(self, op, comm, data, psi, scan, probe, lo, hi, cm, fly,
-                 binning=1, third=None):
-            whole(self, op, comm, data, psi, scan, probe, lo, hi, cm, fly,
-                  binning, third)
-            if third is None:  # the route a plain minibatch would not take
-                self.run = cg._fly_cost_and_grad
-                self.how = dict(cm=cm, fly=fly)
-                self.on_device = False
-
-        monkeypatch.setattr(cg._Minibatch, "__init__", init)
+        # the route a plain minibatch would not take
+        monkeypatch.setattr(cg, "PLAIN_ROUTE", False)
     without = _reconstruct(tp, P, data, _parameters(tp, P, "gaussian", mask),
                            fly, None)
     print(f"fly {fly}: psi {relerr(with_bo.psi, without.psi):.2e} probe "

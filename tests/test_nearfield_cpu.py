@@ -298,7 +298,8 @@ def test_every_refusal(monkeypatch):
             error=TypeError)
     # update_positions_pd of a near-field context
     ctx = tp.Reconstruction.__new__(tp.Reconstruction)
-    ctx._nearfield = H
+    from tike_amd.operators.detector import Detector
+    ctx._detector = Detector("nearfield", 1, H)
     with pytest.raises(NotImplementedError,
                        match="nearfield_options with update_positions_pd"):
         ctx.update_positions_pd()

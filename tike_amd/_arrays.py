@@ -161,6 +161,13 @@ def data_f32(data, lo, hi):
     return d if d.dtype == torch.float32 else d.to(torch.float32)
 
 
+def counts(d):
+    """Resident counts as the kernels with a 16-bit loader read them: uint16
+    as it is, anything else as float32."""
+    return d if d.dtype in (torch.float32, torch.uint16) else d.to(
+        torch.float32)
+
+
 def to_host(x):
     if isinstance(x, torch.Tensor):
         return x.detach().cpu().numpy()

@@ -247,6 +247,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _arrays as A
 from ._lib import check, lib
+from .operators import detector as _D
 from .operators.multislice import Multislice
 from .operators.propagation import fft_scales
 from .ptycho.solvers import _multislice
@@ -1545,14 +1546,13 @@ class _Counts:
     """The counts, the mask and the noise model of one call, and the two
     entries on a chunk's far plane."""
 
-    def __init__(self, data, mask, num_measured, model, fly, binning=1,
-                 background=None, blur=None):
+    def __init__(self, data, mask, num_measured, model, fly,
+                 detector=_D.Detector()):
         self.data, self.mask, self.nm = data, mask, num_measured
-        self.model, self.fly, self.binning = model, fly, binning
-        # (det, det) float32, detached: the factors are taken at I + background
-        self.background = background
-        # (k, k) float32, detached: the factors are taken at blur (*) I
-        self.blur = blur
+        self.model, self.fly = model, fly
+        # (`operators.detector`; b or K detached: the factors are taken at
+        # I + b, at K (*) I)
+        self.detector = detector
         self._stored = None  # the stored intensities of the chunk in hand
         self.u16 = int(data.dtype == torch.uint16)
 
@@ -1577,13 +1577,14 @@ class _Counts:
         on the intensities `factor` has just stored for this chunk."""
         fly = self.fly
         flo, nf = lo // fly, (hi - lo) // fly
-        k, det = self.blur.shape[-1], self._stored.shape[-1]
+        K = self.detector.value
+        k, det = K.shape[-1], self._stored.shape[-1]
         n = lib.tike_blur_kernel_sums_partials(det, k)
         partials = torch.empty(n, dtype=torch.float64, device=ksum.device)
         kgrad = torch.empty((k, k), dtype=torch.float64, device=ksum.device)
         check(
             lib.tike_blur_kernel_sums(
-                A.ptr(self._stored[:nf]), A.ptr(self.blur), k,
+                A.ptr(self._stored[:nf]), A.ptr(K), k,
                 A.ptr(self.data[flo:]), self.u16, A.ptr(self.mask),
                 None if upstream is None else A.ptr(upstream[flo:]),
                 A.ptr(partials), A.ptr(kgrad), nf, det, self.model, self.nm,
@@ -1591,58 +1592,19 @@ class _Counts:
         ksum.add_(kgrad)
 
     def factor(self, lo, hi, far, upstream, costs, table):
-        """tike_cost_factor on the frames of the positions lo ... hi - 1;
-        with binning > 1 tike_binned_cost_factor: counts and mask at data
-        resolution, the table at the far plane's; with a background
-        tike_background_cost_factor; with a blur the chunk's stored
-        intensities (tike_intensity), then tike_blur_cost_factor on them."""
+        """The detector's `tike_*_cost_factor` (`detector.cost_factor`) on the
+        frames of the positions lo ... hi - 1: counts and mask at data
+        resolution, the table at the far plane's; with a blur on the chunk's
+        stored intensities (tike_intensity)."""
         fly = self.fly
         flo, nf = lo // fly, (hi - lo) // fly
-        if self.blur is not None:
-            inten = self._intensity(far, nf)
-            check(
-                lib.tike_blur_cost_factor(
-                    A.ptr(inten), A.ptr(self.blur), self.blur.shape[-1],
-                    A.ptr(self.data[flo:]), self.u16, A.ptr(self.mask),
-                    None if upstream is None else A.ptr(upstream[flo:]),
-                    None if costs is None else A.ptr(costs[flo:]),
-                    A.ptr(table), None, nf, far.shape[-1], self.model,
-                    self.nm, A.stream_ptr()),
-                "cost (tike_blur_cost_factor)")
-            return
-        if self.background is not None:
-            check(
-                lib.tike_background_cost_factor(
-                    A.ptr(far), A.ptr(self.data[flo:]), self.u16,
-                    A.ptr(self.mask), A.ptr(self.background),
-                    None if upstream is None else A.ptr(upstream[flo:]),
-                    None if costs is None else A.ptr(costs[flo:]),
-                    A.ptr(table), nf, far.shape[-3] * fly,
-                    far.shape[-1] * far.shape[-2], self.model, self.nm,
-                    A.stream_ptr()),
-                "cost (tike_background_cost_factor)")
-            return
-        if self.binning > 1:
-            check(
-                lib.tike_binned_cost_factor(
-                    A.ptr(far), A.ptr(self.data[flo:]), self.u16,
-                    A.ptr(self.mask),
-                    None if upstream is None else A.ptr(upstream[flo:]),
-                    None if costs is None else A.ptr(costs[flo:]),
-                    A.ptr(table), nf, far.shape[-3] * fly,
-                    far.shape[-1] * far.shape[-2], self.model, self.nm,
-                    far.shape[-1], self.binning, A.stream_ptr()),
-                "cost (tike_binned_cost_factor)")
-            return
-        check(
-            lib.tike_cost_factor(
-                A.ptr(far), A.ptr(self.data[flo:]), self.u16,
-                A.ptr(self.mask),
-                None if upstream is None else A.ptr(upstream[flo:]),
-                None if costs is None else A.ptr(costs[flo:]), A.ptr(table),
-                nf, far.shape[-3] * fly, far.shape[-1] * far.shape[-2],
-                self.model, self.nm, A.stream_ptr()),
-            "cost (tike_cost_factor)")
+        _D.cost_factor(
+            self.detector, far,
+            self._intensity(far, nf) if self.detector.kind == "blur" else None,
+            A.ptr(self.data[flo:]), self.u16, self.mask,
+            None if upstream is None else A.ptr(upstream[flo:]),
+            None if costs is None else A.ptr(costs[flo:]), table, nf, fly,
+            self.model, self.nm)
 
     def curvature(self, lo, hi, far, dfar, upstream, costs, dcosts, table,
                   floor=COST_FLOOR):
@@ -1730,14 +1692,16 @@ class _Cost(torch.autograd.Function):
         g = g.to(torch.float32).contiguous()
         A.current_device()  # (hands the library its deterministic-mode scratch)
         tables = {}
-        want_b = counts.background is not None and ctx.needs_input_grad[7]
+        kind = counts.detector.kind
+        want_b = kind == "background" and ctx.needs_input_grad[7]
         # d cost_f / d b = d cost_f / d I: the sum of the table over the
         # frames, chunk by chunk in float64, rounded once
         bsum = (torch.zeros((det, det), dtype=torch.float64,
                             device=psi.device) if want_b else None)
         # d (sum_f g_f cost_f) / d K: the chunks' kgrad, float64, rounded once
-        want_k = counts.blur is not None and ctx.needs_input_grad[8]
-        ksum = (torch.zeros(tuple(counts.blur.shape), dtype=torch.float64,
+        want_k = kind == "blur" and ctx.needs_input_grad[8]
+        ksum = (torch.zeros(tuple(counts.detector.value.shape),
+                            dtype=torch.float64,
                             device=psi.device) if want_k else None)
 
         def table_of(lo, hi, far):
@@ -1884,55 +1848,6 @@ class _NearfieldCost(torch.autograd.Function):
         return gpsi, gprobe, gscan, None, None, None
 
 
-def _checked_nearfield(name, operator, nearfield, psi, eigen_probe,
-                       eigen_weights, binning, background, blur):
-    """The propagator of `cost`, detached and contiguous on the device, after
-    its refusals."""
-    from .operators import nearfield as NF
-    if isinstance(nearfield, torch.Tensor) and nearfield.requires_grad:
-        raise NotImplementedError(
-            f"{name}: nearfield that requires a gradient is not implemented: "
-            "the propagator is used as given")
-    if eigen_probe is not None or eigen_weights is not None:
-        raise NotImplementedError(
-            f"{name}: nearfield with eigen probes is not implemented")
-    if isinstance(psi, torch.Tensor) and psi.ndim == 3 and psi.shape[0] > 1:
-        raise NotImplementedError(
-            f"{name}: nearfield with several slices (psi.shape[0] = "
-            f"{psi.shape[0]}) is not implemented")
-    if binning != 1:
-        raise NotImplementedError(
-            f"{name}: nearfield with binning={binning} is not implemented")
-    if background is not None:
-        raise NotImplementedError(
-            f"{name}: nearfield with a background is not implemented")
-    if blur is not None:
-        raise NotImplementedError(
-            f"{name}: nearfield with a blur is not implemented")
-    if not isinstance(nearfield, torch.Tensor):
-        raise TypeError(
-            f"{name}: nearfield must be a torch device tensor, not "
-            f"{type(nearfield).__name__}")
-    if nearfield.dtype != torch.complex64:
-        raise TypeError(
-            f"{name}: nearfield must be torch.complex64, not "
-            f"{nearfield.dtype}")
-    det = operator.detector_shape
-    if tuple(nearfield.shape) != (det, det):
-        raise ValueError(
-            f"{name}: nearfield must be ({det}, {det}), not "
-            f"{tuple(nearfield.shape)}")
-    if operator.probe_shape != det:
-        raise NotImplementedError(
-            f"{name}: nearfield with probe window {operator.probe_shape} != "
-            f"detector {det}: the probe fills the frame in this geometry")
-    if nearfield.device.type != "cuda":
-        raise TypeError(
-            f"{name}: nearfield lives on {nearfield.device}; tike_amd runs on "
-            "the GPU only and there is no CPU fallback")
-    return NF.device_propagator(nearfield.detach(), det)
-
-
 def cost(operator, data, psi, probe, scan, *, model="gaussian",
          measured_pixels=None, eigen_probe=None, eigen_weights=None, fly=1,
          binning=1, check_positions=True, background=None, blur=None,
@@ -2022,72 +1937,44 @@ def cost(operator, data, psi, probe, scan, *, model="gaussian",
                                eigen_weights, binning, background, blur)
         return _NearfieldCost.apply(psi, probe, scan, operator,
                                     _Counts(data, mask, nm, model, fly), H)
-    b = (None if background is None else
-         _checked_background(name, operator, background, binning))
-    K = (None if blur is None else
-         _checked_blur(name, operator, blur, binning, background))
+    detector = _D.far_field(binning)
+    if background is not None:
+        detector = _D.Detector("background", 1, _checked_background(
+            name, operator, background, binning))
+    if blur is not None:
+        detector = _D.Detector("blur", 1, _checked_blur(
+            name, operator, blur, binning, background))
     return _Cost.apply(psi, probe, scan, eigen_probe, eigen_weights, operator,
-                       _Counts(data, mask, nm, model, fly, binning, b, K),
+                       _Counts(data, mask, nm, model, fly, detector),
                        background, blur)
+
+
+def _checked_nearfield(name, operator, nearfield, psi, eigen_probe,
+                       eigen_weights, binning, background, blur):
+    """The propagator of `cost` on the device, after its refusals."""
+    det = operator.detector_shape
+    _D.refuse("nearfield", _D.entry(name), binning=binning,
+              background=background is not None, blur=blur is not None,
+              slices=psi.shape[0], eigen=(eigen_probe is not None
+                                          or eigen_weights is not None),
+              window=operator.probe_shape, det=det)
+    return _D.device_value(name, "nearfield", nearfield, det)
 
 
 def _checked_background(name, operator, background, binning):
     """The background of `cost`, detached and contiguous, after its
     refusals."""
-    if binning != 1:
-        raise NotImplementedError(
-            f"{name}: background with binning={binning} is not implemented")
-    det = operator.detector_shape
-    if not isinstance(background, torch.Tensor):
-        raise TypeError(
-            f"{name}: background must be a torch device tensor, not "
-            f"{type(background).__name__}")
-    if background.dtype != torch.float32:
-        raise TypeError(
-            f"{name}: background must be torch.float32, not "
-            f"{background.dtype}")
-    if tuple(background.shape) != (det, det):
-        raise ValueError(
-            f"{name}: background must be ({det}, {det}), not "
-            f"{tuple(background.shape)}")
-    if background.device.type != "cuda":
-        raise TypeError(
-            f"{name}: background lives on {background.device}; tike_amd runs "
-            "on the GPU only and there is no CPU fallback")
-    return background.detach().contiguous()
+    _D.refuse("background", _D.entry(name), binning=binning)
+    return _D.device_value(name, "background", background,
+                           operator.detector_shape)
 
 
 def _checked_blur(name, operator, blur, binning, background):
     """The blur kernel of `cost`, detached and contiguous, after its
     refusals."""
-    if binning != 1:
-        raise NotImplementedError(
-            f"{name}: blur with binning={binning} is not implemented")
-    if background is not None:
-        raise NotImplementedError(
-            f"{name}: blur with a background is not implemented")
-    det = operator.detector_shape
-    if not isinstance(blur, torch.Tensor):
-        raise TypeError(
-            f"{name}: blur must be a torch device tensor, not "
-            f"{type(blur).__name__}")
-    if blur.dtype != torch.float32:
-        raise TypeError(
-            f"{name}: blur must be torch.float32, not {blur.dtype}")
-    k = blur.shape[-1] if blur.ndim else 0
-    if blur.ndim != 2 or tuple(blur.shape) != (k, k) or k not in (3, 5, 7):
-        raise ValueError(
-            f"{name}: blur must be (k, k) with k in (3, 5, 7), not "
-            f"{tuple(blur.shape)}")
-    if k > det:
-        raise ValueError(
-            f"{name}: blur {tuple(blur.shape)} is wider than the detector "
-            f"({det}, {det})")
-    if blur.device.type != "cuda":
-        raise TypeError(
-            f"{name}: blur lives on {blur.device}; tike_amd runs on the GPU "
-            "only and there is no CPU fallback")
-    return blur.detach().contiguous()
+    _D.refuse("blur", _D.entry(name), binning=binning,
+              background=background is not None)
+    return _D.device_value(name, "blur", blur, operator.detector_shape)
 
 
 def _refuse_binned_curvature(name, binning):

@@ -13,6 +13,7 @@ import torch
 from .. import _tuning
 from .. import _arrays as A
 from .._lib import check, lib
+from . import detector as D
 from . import nearfield as NF
 from . import objective
 from .multislice import Multislice
@@ -413,80 +414,26 @@ class Ptycho(Operator):
                 A.stream_ptr()), "Ptycho.blur_kernel_sums")
         return buf[:n // (1 + k * k)], kgrad
 
-    def _device_blur(self, blur, binning, psi, background):
-        """The blur kernel of `_compute_intensity` and `cost` on the device,
-        after their refusals."""
-        if binning > 1:
-            raise ValueError("blur together with binning > 1 is not supported")
-        if background is not None:
-            raise ValueError(
-                "blur together with a background is not supported")
-        if psi.shape[0] > 1:
-            raise ValueError(
-                "blur together with several object slices is not supported")
+    def _detector(self, psi, probe, binning, background, blur, nearfield):
+        """The `detector.Detector` of `_compute_intensity` and `cost` (host
+        or device arrays), its b, K or H on the device."""
         det = self.detector_shape
-        K = A.to_device(blur, np.float32).contiguous()
-        k = K.shape[-1] if K.ndim else 0
-        if K.ndim != 2 or tuple(K.shape) != (k, k) or k not in (3, 5, 7):
-            raise ValueError(
-                f"blur must be (k, k) with k in (3, 5, 7), not "
-                f"{tuple(K.shape)}")
-        if k > det:
-            raise ValueError(
-                f"blur {tuple(K.shape)} is wider than the detector "
-                f"({det}, {det})")
-        return K
+        window = probe.shape[-1]
+        return D.resident_value(
+            D.build(D.OPERATOR, det, binning=binning, background=background,
+                    blur=blur, nearfield=nearfield, slices=psi.shape[0],
+                    window=window if window != det else self.probe_shape),
+            det)
 
-    def _device_background(self, background, binning, psi):
-        """The background of `_compute_intensity` and `cost` on the device,
-        after their refusals."""
-        if binning > 1:
-            raise ValueError(
-                "background together with binning > 1 is not supported")
-        if psi.shape[0] > 1:
-            raise ValueError(
-                "background together with several object slices is not "
-                "supported")
-        det = self.detector_shape
-        b = A.to_device(background, np.float32).contiguous()
-        if tuple(b.shape) != (det, det):
-            raise ValueError(
-                f"background must have the detector's shape ({det}, {det}), "
-                f"not {tuple(b.shape)}")
-        return b
-
-    def _device_nearfield(self, nearfield, binning, psi, probe, background,
-                          blur):
-        """The propagator of `_compute_intensity` and `cost` on the device,
-        after their refusals."""
-        if binning > 1:
-            raise ValueError(
-                "nearfield together with binning > 1 is not supported")
-        if background is not None:
-            raise ValueError(
-                "nearfield together with a background is not supported")
-        if blur is not None:
-            raise ValueError("nearfield together with a blur is not supported")
-        if psi.shape[0] > 1:
-            raise ValueError(
-                "nearfield together with several object slices is not "
-                "supported")
-        if probe.shape[-1] != self.detector_shape or (
-                self.probe_shape != self.detector_shape):
-            raise ValueError(
-                f"nearfield needs probe window = detector, not "
-                f"{probe.shape[-1]} and {self.detector_shape}")
-        return NF.device_propagator(nearfield, self.detector_shape)
-
-    def _nearfield_inputs(self, psi, scan, probe, fly):
-        psi = A.to_device(psi, np.complex64)
+    def _frame_inputs(self, psi, scan, probe, fly):
+        """psi, scan and probe on the device, scan in whole frames."""
         scan = A.to_device(scan, np.float32)
-        probe = A.to_device(probe, np.complex64)
         if scan.shape[0] % fly:
             raise ValueError(
                 f"{scan.shape[0]} scan positions are not a multiple of "
                 f"fly={fly}")
-        return psi, scan, probe
+        return (A.to_device(psi, np.complex64), scan,
+                A.to_device(probe, np.complex64))
 
     def _compute_intensity(self, data, psi, scan, probe, fly=1, binning=1,
                            background=None, blur=None, nearfield=None):
@@ -499,62 +446,31 @@ class Ptycho(Operator):
         with it, cyclically over the plane (`blur_cost_factor`); with nearfield
         (det, det) complex64 the detector sits in the near field: the
         intensity is |IFFT2(nearfield FFT2(patch x probe))|^2 and the second
-        result is that detector-plane wave (`operators.nearfield`)."""
-        if nearfield is not None:
-            psi_d, scan_d, probe_d = self._nearfield_inputs(psi, scan, probe,
-                                                            fly)
-            H = self._device_nearfield(nearfield, binning, psi_d, probe_d,
-                                       background, blur)
-            w = NF.detector_wave(self, psi_d, scan_d, probe_d, H)
-            N, S, det, _ = w.shape
+        result is that detector-plane wave (`operators.nearfield`).  What the
+        detector does: `operators.detector`."""
+        det = self.detector_shape
+        if binning < 1 or det % binning:
+            raise ValueError(
+                f"binning={binning!r} does not divide the far-plane "
+                f"width {det}")
+        detector = self._detector(psi, probe, binning, background, blur,
+                                  nearfield)
+        psi_d, scan_d, probe_d = self._frame_inputs(psi, scan, probe, fly)
+        if detector.kind == "nearfield":
+            w = NF.detector_wave(self, psi_d, scan_d, probe_d, detector.value)
+            N, S = w.shape[:2]
             intensity = torch.empty((N // fly, det, det), dtype=torch.float32,
                                     device=w.device)
             self.fly_farplane_gradient(w, torch.zeros_like(intensity), fly,
                                        intensity=intensity)
-            return (A.like_input(intensity, psi),
-                    A.like_input(w.view(N, 1, S, det, det), psi))
-        if blur is not None:
-            K = self._device_blur(blur, binning,
-                                  A.to_device(psi, np.complex64), background)
-            intensity, far = self._compute_intensity(data, psi, scan, probe,
-                                                     fly=fly)
-            stored = A.to_device(intensity).contiguous()
-            blurred = torch.empty_like(stored)
-            self.blur_cost_factor(stored, K, blurred=blurred)
-            return A.like_input(blurred, psi), far
-        if background is not None:
-            b = self._device_background(background, binning,
-                                        A.to_device(psi, np.complex64))
-            intensity, far = self._compute_intensity(data, psi, scan, probe,
-                                                     fly=fly)
-            return (A.like_input(A.to_device(intensity) + b, psi), far)
-        kind = psi
-        far = self.fwd_device(A.to_device(probe, np.complex64),
-                              A.to_device(scan, np.float32),
-                              A.to_device(psi, np.complex64))
-        N, _, S, det, _ = far.shape
-        if fly > 1 or binning > 1:
-            if N % fly:
-                raise ValueError(
-                    f"{N} scan positions are not a multiple of fly={fly}")
-            if binning < 1 or det % binning:
-                raise ValueError(
-                    f"binning={binning!r} does not divide the far-plane "
-                    f"width {det}")
-            w = det // binning
-            intensity = torch.empty((N // fly, w, w), dtype=torch.float32,
-                                    device=far.device)
-            # (the counts are read by the cost and the gradient only: any
-            # array of the frames' shape serves)
-            self.binned_farplane_gradient(far, torch.zeros_like(intensity),
-                                          fly, binning, intensity=intensity)
-            return A.like_input(intensity, kind), A.like_input(far, kind)
-        intensity = torch.empty((N, det, det), dtype=torch.float32,
-                                device=far.device)
-        check(
-            lib.tike_intensity(A.ptr(far), A.ptr(intensity), N, S, det * det,
-                               A.stream_ptr()), "Ptycho._compute_intensity")
-        return A.like_input(intensity, kind), A.like_input(far, kind)
+            far = w.view(N, 1, S, det, det)
+        else:
+            far = self.fwd_device(probe_d, scan_d, psi_d)
+            intensity = D.intensity(self, detector, far, fly,
+                                    always_binned=True)
+            if detector.kind == "background":
+                intensity = intensity + detector.value
+        return A.like_input(intensity, psi), A.like_input(far, psi)
 
     def cost(self, data, psi, scan, probe, *, model, fly=1, binning=1,
              background=None, blur=None, nearfield=None):
@@ -565,78 +481,42 @@ class Ptycho(Operator):
         blur (*) intensity (`blur_cost_factor` on the stored intensities); with
         nearfield (det, det) complex64 the mean over frames of the cost of
         |IFFT2(nearfield FFT2(patch x probe))|^2 (`operators.nearfield`, the
-        general route)."""
-        if nearfield is not None:
-            if model not in objective._MODELS:
-                raise ValueError(f"unknown noise model {model!r}")
-            psi_d, scan_d, probe_d = self._nearfield_inputs(psi, scan, probe,
-                                                            fly)
-            H = self._device_nearfield(nearfield, binning, psi_d, probe_d,
-                                       background, blur)
-            counts = A.to_device(data)
-            if counts.dtype not in (torch.float32, torch.uint16):
-                counts = counts.to(torch.float32)
-            if counts.shape[0] * fly != scan_d.shape[0]:
-                raise ValueError(
-                    f"{counts.shape[0]} frames of fly={fly} do not match "
-                    f"{scan_d.shape[0]} scan positions")
-            costs = torch.empty(counts.shape[0], dtype=torch.float32,
-                                device=psi_d.device)
+        general route).  What the detector does: `operators.detector`."""
+        detector = self._detector(psi, probe, binning, background, blur,
+                                  nearfield)
+        if detector.kind == "far" and fly == 1:
+            intensity, _ = self._compute_intensity(data, psi, scan, probe)
+            return getattr(objective, model)(data, intensity)
+        if model not in objective._MODELS:
+            raise ValueError(f"unknown noise model {model!r}")
+        cm = D.Model(objective._MODELS[model])
+        psi_d, scan_d, probe_d = self._frame_inputs(psi, scan, probe, fly)
+        if detector.kind != "nearfield":
+            far = self.fwd_device(probe_d, scan_d, psi_d)
+        if detector.kind == "blur":
+            stored = D.intensity(self, D.Detector(), far, fly,
+                                 always_binned=True)
+        counts = A.counts(A.to_device(data)).contiguous()
+        if counts.shape[0] * fly != scan_d.shape[0]:
+            raise ValueError(
+                f"{counts.shape[0]} frames of fly={fly} do not match "
+                f"{scan_d.shape[0]} scan positions")
+        costs = torch.empty(counts.shape[0], dtype=torch.float32,
+                            device=psi_d.device)
+        if detector.kind == "nearfield":
             S, det = probe_d.shape[-3], self.detector_shape
             NF.wave_and_back(
-                self, psi_d, scan_d, probe_d, H, counts.contiguous(), fly,
+                self, psi_d, scan_d, probe_d, detector.value, counts, fly,
                 "general", NF.buffers(None, psi_d.device, 0, S, det, fly,
                                       "general", table=False),
-                model=objective._MODELS[model], costs=costs)
-            return A.like_input(costs.mean(), psi)
-        if blur is not None:
-            if model not in objective._MODELS:
-                raise ValueError(f"unknown noise model {model!r}")
-            K = self._device_blur(blur, binning,
-                                  A.to_device(psi, np.complex64), background)
-            intensity, _ = self._compute_intensity(None, psi, scan, probe,
-                                                   fly=fly)
-            stored = A.to_device(intensity).contiguous()
-            counts = A.to_device(data)
-            if counts.dtype not in (torch.float32, torch.uint16):
-                counts = counts.to(torch.float32)
-            if counts.shape[0] != stored.shape[0]:
-                raise ValueError(
-                    f"{counts.shape[0]} frames of fly={fly} do not match "
-                    f"{stored.shape[0] * fly} scan positions")
-            costs = torch.empty(counts.shape[0], dtype=torch.float32,
-                                device=stored.device)
-            self.blur_cost_factor(stored, K, counts.contiguous(),
-                                  model=objective._MODELS[model], costs=costs)
-            return A.like_input(costs.mean(), psi)
-        if background is not None:
-            background = self._device_background(
-                background, binning, A.to_device(psi, np.complex64))
-        if fly > 1 or binning > 1 or background is not None:
-            if model not in objective._MODELS:
-                raise ValueError(f"unknown noise model {model!r}")
-            kind = psi
-            far = self.fwd_device(A.to_device(probe, np.complex64),
-                                  A.to_device(scan, np.float32),
-                                  A.to_device(psi, np.complex64))
-            counts = A.to_device(data)
-            if counts.dtype not in (torch.float32, torch.uint16):
-                counts = counts.to(torch.float32)
-            if counts.shape[0] * fly != far.shape[0]:
-                raise ValueError(
-                    f"{counts.shape[0]} frames of fly={fly} do not match "
-                    f"{far.shape[0]} scan positions")
-            costs = torch.empty(counts.shape[0], dtype=torch.float32,
-                                device=far.device)
-            if background is not None:
-                self.background_farplane_gradient(
-                    far, counts.contiguous(), fly, background,
-                    model=objective._MODELS[model], costs=costs)
-            else:
-                self.binned_farplane_gradient(far, counts.contiguous(), fly,
-                                              binning,
-                                              model=objective._MODELS[model],
-                                              costs=costs)
-            return A.like_input(costs.mean(), kind)
-        intensity, _ = self._compute_intensity(data, psi, scan, probe)
-        return getattr(objective, model)(data, intensity)
+                model=cm.model, costs=costs)
+        elif detector.kind == "blur":
+            self.blur_cost_factor(stored, detector.value, counts,
+                                  model=cm.model, costs=costs)
+        else:
+            # (a fly scan alone goes through the binned entry at B = 1)
+            D.farplane_step(
+                self, detector._replace(kind="binned")
+                if detector.kind == "far" else detector, far, counts, fly, cm,
+                costs=costs)
+        return A.like_input(costs.mean(), psi)

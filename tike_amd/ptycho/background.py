@@ -20,6 +20,8 @@ import numpy as np
 import torch
 
 from .. import _arrays as A
+from .._lib import check, lib
+from ..operators import detector as D
 
 
 @dataclasses.dataclass
@@ -39,10 +41,12 @@ class BackgroundOptions:
     """The first epoch that fits it."""
 
 
-def refuse(options, parameters, det, *, fly=1, binning=1, data_on_host=False,
-           local_data=None, world_size=1):
+def refuse(options, parameters, det, *, binning=1, data_on_host=False,
+           local_data=None, world_size=1, background_options=None,
+           blur_options=None):
     """Raise, by name, for everything a background cannot be combined with,
-    before any device work."""
+    before any device work; the checked background otherwise.  (The keywords
+    are those of every model's `refuse`.)"""
     if not isinstance(options, BackgroundOptions):
         raise TypeError(
             "background_options must be a tike_amd.ptycho.BackgroundOptions, "
@@ -52,19 +56,10 @@ def refuse(options, parameters, det, *, fly=1, binning=1, data_on_host=False,
         raise NotImplementedError(
             f"background_options with {name}: a fitted background is "
             "reconstructed by cgrad only")
-    if binning > 1:
-        raise NotImplementedError(
-            f"background_options with binning={binning}: a background of "
-            "binned data is not implemented")
-    if parameters.psi.shape[0] > 1:
-        raise NotImplementedError(
-            "background_options with several slices (psi.shape[0] = "
-            f"{parameters.psi.shape[0]}): a background of a multislice "
-            "reconstruction is not implemented")
-    if (parameters.eigen_probe is not None
-            or parameters.eigen_weights is not None):
-        raise NotImplementedError(
-            "background_options with eigen probes is not implemented")
+    D.refuse("background", D.RECONSTRUCTION, binning=binning,
+             slices=parameters.psi.shape[0],
+             eigen=(parameters.eigen_probe is not None
+                    or parameters.eigen_weights is not None))
     if parameters.position_options is not None:
         raise NotImplementedError(
             "background_options with position_options: position correction "
@@ -81,26 +76,14 @@ def refuse(options, parameters, det, *, fly=1, binning=1, data_on_host=False,
         raise NotImplementedError(
             "background_options with the ranks of a torch.distributed job: a "
             "background is fitted in one process")
-    b = options.background
-    if A.is_device(b):
-        b = A.to_host(b)
-    b = np.asarray(b)
-    if b.shape != (det, det):
-        raise ValueError(
-            f"background_options.background has shape {b.shape}; expected "
-            f"the detector's ({det}, {det})")
-    if b.dtype != np.float32:
-        raise ValueError(
-            f"background_options.background is {b.dtype}; expected float32")
-    if not np.all(np.isfinite(b)) or np.any(b < 0):
-        raise ValueError(
-            "background_options.background must be finite and >= 0")
-    return b
+    return D.checked_background(options.background, det,
+                                "background_options.background")
 
 
 class State:
     """What cgrad reads of the background on the device: a = sqrt(b) (det,
-    det) float32, the variable of its third block, and b = a * a."""
+    det) float32, the variable of its third block, and b = a * a, the `value`
+    of the far-plane step."""
 
     def __init__(self, options, background):
         self.options = options
@@ -108,7 +91,25 @@ class State:
 
     def set(self, a):
         self.a = a
-        self.b = (a * a).contiguous()
+        self.value = (a * a).contiguous()
 
     def write_back(self):
-        self.options.background = A.to_host(self.b)
+        self.options.background = A.to_host(self.value)
+
+    def cost_and_grad(self, op, counts, stored, a, cm, want_grad):
+        """(sum of the per-frame costs at b = a * a, a device scalar; d / d a
+        of that sum = 2 a bgrad, or None) of the frames whose intensities
+        `stored` holds: one `tike_background_sums` launch."""
+        npix = stored.shape[-1] * stored.shape[-2]
+        b = (a * a).contiguous()
+        partials = torch.zeros(lib.tike_background_sums_partials(npix),
+                               dtype=torch.float64, device=a.device)
+        bgrad = torch.empty_like(b) if want_grad else None
+        check(
+            lib.tike_background_sums(
+                A.ptr(stored), A.ptr(counts),
+                int(counts.dtype == torch.uint16), A.ptr(cm.mask), A.ptr(b),
+                None, A.ptr(partials), A.ptr(bgrad), counts.shape[0], npix,
+                cm.model, cm.nmeasured, A.stream_ptr()),
+            "cgrad background sums")
+        return partials.sum(), (2 * a * bgrad if want_grad else None)

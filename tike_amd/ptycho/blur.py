@@ -35,8 +35,10 @@ import numpy as np
 import torch
 
 from .. import _arrays as A
+from ..operators import detector as D
 
-WIDTHS = (3, 5, 7)
+WIDTHS = D.BLUR_WIDTHS
+checked_kernel = D.checked_kernel
 
 
 @dataclasses.dataclass
@@ -58,34 +60,12 @@ class BlurOptions:
     """The first epoch that fits it."""
 
 
-def checked_kernel(kernel, det, what="blur"):
-    """`kernel` as a host (k, k) float32 array of sum 1, after validation of
-    its shape, dtype, finiteness and sign."""
-    K = kernel
-    if A.is_device(K):
-        K = A.to_host(K)
-    K = np.asarray(K)
-    k = K.shape[-1] if K.ndim else 0
-    if K.ndim != 2 or K.shape != (k, k) or k not in WIDTHS:
-        raise ValueError(
-            f"{what} has shape {K.shape}; expected (k, k) with k in {WIDTHS}")
-    if K.dtype != np.float32:
-        raise ValueError(f"{what} is {K.dtype}; expected float32")
-    if k > det:
-        raise ValueError(
-            f"{what} {K.shape} is wider than the detector ({det}, {det})")
-    if not np.all(np.isfinite(K)) or np.any(K < 0):
-        raise ValueError(f"{what} must be finite and >= 0")
-    total = float(K.sum(dtype=np.float64))
-    if not total > 0:
-        raise ValueError(f"{what} must have a positive sum")
-    return (K.astype(np.float64) / total).astype(np.float32)
-
-
-def refuse(options, parameters, det, *, fly=1, binning=1, data_on_host=False,
-           local_data=None, world_size=1, background_options=None):
+def refuse(options, parameters, det, *, binning=1, data_on_host=False,
+           local_data=None, world_size=1, background_options=None,
+           blur_options=None):
     """Raise, by name, for everything a blur cannot be combined with, before
-    any device work; the normalised kernel otherwise."""
+    any device work; the normalised kernel otherwise.  (The keywords are
+    those of every model's `refuse`.)"""
     if not isinstance(options, BlurOptions):
         raise TypeError(
             "blur_options must be a tike_amd.ptycho.BlurOptions, not "
@@ -95,23 +75,11 @@ def refuse(options, parameters, det, *, fly=1, binning=1, data_on_host=False,
         raise NotImplementedError(
             f"blur_options with {name}: a blurred far field is reconstructed "
             "by cgrad only")
-    if binning > 1:
-        raise NotImplementedError(
-            f"blur_options with binning={binning}: a blur of binned data is "
-            "not implemented")
-    if background_options is not None:
-        raise NotImplementedError(
-            "blur_options with background_options: a blur together with a "
-            "background is not implemented")
-    if parameters.psi.shape[0] > 1:
-        raise NotImplementedError(
-            "blur_options with several slices (psi.shape[0] = "
-            f"{parameters.psi.shape[0]}): a blur of a multislice "
-            "reconstruction is not implemented")
-    if (parameters.eigen_probe is not None
-            or parameters.eigen_weights is not None):
-        raise NotImplementedError(
-            "blur_options with eigen probes is not implemented")
+    D.refuse("blur", D.RECONSTRUCTION, binning=binning,
+             background=background_options is not None,
+             slices=parameters.psi.shape[0],
+             eigen=(parameters.eigen_probe is not None
+                    or parameters.eigen_weights is not None))
     if parameters.position_options is not None:
         raise NotImplementedError(
             "blur_options with position_options: position correction "
@@ -150,7 +118,8 @@ def chain(a, kgrad):
 
 class State:
     """What cgrad reads of the blur on the device: a (k, k) float32, the
-    variable of its third block, and K = a^2 / sum a^2."""
+    variable of its third block, and K = a^2 / sum a^2, the `value` of the
+    far-plane step."""
 
     def __init__(self, options, kernel):
         self.options = options
@@ -158,7 +127,17 @@ class State:
 
     def set(self, a):
         self.a = a
-        self.kernel = kernel_of(a)
+        self.value = kernel_of(a)
 
     def write_back(self):
-        self.options.kernel = A.to_host(self.kernel)
+        self.options.kernel = A.to_host(self.value)
+
+    def cost_and_grad(self, op, counts, stored, a, cm, want_grad):
+        """(sum of the per-frame costs at K = a^2 / sum a^2, a device scalar;
+        d / d a of that sum, or None) of the frames whose intensities `stored`
+        holds: one `tike_blur_kernel_sums` launch (with the gradient, its
+        k * k lanes of a second), then `chain`, k * k numbers in torch."""
+        partials, kgrad = op.blur_kernel_sums(
+            stored, kernel_of(a), counts, model=cm.model, measured=cm.mask,
+            num_measured=cm.nmeasured, want_gradient=want_grad)
+        return partials.sum(), (chain(a, kgrad) if want_grad else None)

@@ -32,30 +32,11 @@ import dataclasses
 
 import numpy as np
 
-from .. import _arrays as A
+from ..operators import detector as D
 from ..operators.fresnelspectprop import fresnel_spectrum_propagator
 
 
-def checked_propagator(propagator, det, what="nearfield"):
-    """`propagator` as a host (det, det) complex64 array, after validation of
-    its shape, dtype and finiteness."""
-    H = propagator
-    if A.is_device(H):
-        if H.requires_grad:
-            raise ValueError(
-                f"{what} that requires a gradient is not supported: the "
-                "propagator is used as given")
-        H = A.to_host(H)
-    H = np.asarray(H)
-    if H.ndim != 2 or H.shape != (det, det):
-        raise ValueError(
-            f"{what} has shape {H.shape}; expected ({det}, {det}), the "
-            "detector's shape")
-    if H.dtype != np.complex64:
-        raise ValueError(f"{what} is {H.dtype}; expected complex64")
-    if not np.all(np.isfinite(H)):
-        raise ValueError(f"{what} must be finite")
-    return np.ascontiguousarray(H)
+checked_propagator = D.checked_propagator
 
 
 @dataclasses.dataclass
@@ -96,27 +77,12 @@ def refuse(options, parameters, det, *, binning=1, data_on_host=False,
         raise NotImplementedError(
             f"nearfield_options with {name}: a near-field detector plane is "
             "reconstructed by cgrad only")
-    if binning > 1:
-        raise NotImplementedError(
-            f"nearfield_options with binning={binning}: binned near-field "
-            "data is not implemented")
-    if background_options is not None:
-        raise NotImplementedError(
-            "nearfield_options with background_options: a background "
-            "together with a near-field detector plane is not implemented")
-    if blur_options is not None:
-        raise NotImplementedError(
-            "nearfield_options with blur_options: a blur together with a "
-            "near-field detector plane is not implemented")
-    if parameters.psi.shape[0] > 1:
-        raise NotImplementedError(
-            "nearfield_options with several slices (psi.shape[0] = "
-            f"{parameters.psi.shape[0]}): a multislice near-field "
-            "reconstruction is not implemented")
-    if (parameters.eigen_probe is not None
-            or parameters.eigen_weights is not None):
-        raise NotImplementedError(
-            "nearfield_options with eigen probes is not implemented")
+    D.refuse("nearfield", D.RECONSTRUCTION, binning=binning,
+             background=background_options is not None,
+             blur=blur_options is not None, slices=parameters.psi.shape[0],
+             eigen=(parameters.eigen_probe is not None
+                    or parameters.eigen_weights is not None),
+             window=parameters.probe.shape[-1], det=det)
     if parameters.position_options is not None:
         raise NotImplementedError(
             "nearfield_options with position_options: position correction "
@@ -133,10 +99,5 @@ def refuse(options, parameters, det, *, binning=1, data_on_host=False,
         raise NotImplementedError(
             "nearfield_options with the ranks of a torch.distributed job: a "
             "near-field reconstruction runs in one process")
-    pw = parameters.probe.shape[-1]
-    if pw != det:
-        raise NotImplementedError(
-            f"nearfield_options with probe window {pw} != detector {det}: "
-            "the probe fills the frame in this geometry")
     return checked_propagator(options.propagator, det,
                               "nearfield_options.propagator")

@@ -45,26 +45,21 @@ from .probe import (apply_median_filter_abs_probe, constrain_center_peak,
 from . import background as _background
 from . import blur as _blur
 from . import nearfield as _nearfield
+from ..operators import detector as _D
 from ..operators import nearfield as _NF
 from .solvers.cgrad import _refuse_binning, _refuse_fly, _refuse_multislice
 from .solvers.dm import refuse as _refuse_dm
 from .solvers.lstsq import chunk_positions, mask_info
-from .._lib import check, lib
 
 logger = logging.getLogger(__name__)
 
 
 def _intensity_chunks(operator, psi, scan, probe, eigen_probe=None,
-                      eigen_weights=None, fly=1, binning=1, background=None,
-                      blur=None, nearfield=None):
-    """Yield (lo, hi, intensity (n, det, det)) over chunks of frames; frame f
-    is the sum over the positions f * fly ... f * fly + fly - 1.  With
-    binning = B > 1 the intensity is (n, det // B, det // B), a pixel the sum
-    over its B x B far-plane pixels.  background (det, det) float32 or None
-    is added to every frame; blur (k, k) float32 or None is the kernel every
-    frame is convolved with, cyclically (`Ptycho.blur_cost_factor`);
-    nearfield (det, det) complex64 or None is the propagator between the
-    sample and a detector in the near field (`operators.nearfield`)."""
+                      eigen_weights=None, fly=1, detector=_D.Detector()):
+    """Yield (lo, hi, intensity (n, w, w)) over chunks of frames; frame f is
+    the sum over the positions f * fly ... f * fly + fly - 1, seen through
+    `detector` (`operators.detector`: its b, K or H on the device; w the
+    width of its counts)."""
     N = scan.shape[0]
     S = probe.shape[-3]
     det = operator.detector_shape
@@ -77,11 +72,11 @@ def _intensity_chunks(operator, psi, scan, probe, eigen_probe=None,
     for lo in range(0, N, chunk):
         hi = min(N, lo + chunk)
         w = None if eigen_weights is None else eigen_weights[lo:hi]
-        if nearfield is not None:
+        if detector.kind == "nearfield":
             inten = torch.empty(((hi - lo) // fly, det, det),
                                 dtype=torch.float32, device=psi.device)
             _NF.wave_and_back(
-                operator, psi, scan[lo:hi], probe, nearfield, None, fly,
+                operator, psi, scan[lo:hi], probe, detector.value, None, fly,
                 "general", _NF.buffers(None, psi.device, 0, S, det, fly,
                                        "general", table=False),
                 intensity=inten)
@@ -92,26 +87,9 @@ def _intensity_chunks(operator, psi, scan, probe, eigen_probe=None,
                                scan=scan[lo:hi], psi=psi).contiguous()
         else:
             far = operator.fwd_device(probe, scan[lo:hi], psi, eigen_probe, w)
-        w = det // binning
-        inten = torch.empty(((hi - lo) // fly, w, w), dtype=torch.float32,
-                            device=psi.device)
-        if binning > 1:
-            operator.binned_farplane_gradient(far, torch.zeros_like(inten),
-                                              fly, binning, intensity=inten)
-        elif fly > 1:
-            # (the counts are read by the cost and the gradient only)
-            operator.fly_farplane_gradient(far, torch.zeros_like(inten), fly,
-                                           intensity=inten)
-        else:
-            check(
-                lib.tike_intensity(A.ptr(far), A.ptr(inten), hi - lo, S,
-                                   det * det, A.stream_ptr()), "intensity")
-        if background is not None:
-            inten += background
-        if blur is not None:
-            blurred = torch.empty_like(inten)
-            operator.blur_cost_factor(inten, blur, blurred=blurred)
-            inten = blurred
+        inten = _D.intensity(operator, detector, far, fly)
+        if detector.kind == "background":
+            inten += detector.value
         yield lo // fly, hi // fly, inten
 
 
@@ -132,106 +110,34 @@ def simulate(detector_shape, probe, scan, psi, fly=1, eigen_probe=None,
     (`ptycho.nearfield`): the detector sits in the near field, probe window =
     detector, every frame is |IFFT2(nearfield FFT2(patch x probe))|^2 in the
     natural, unshifted layout of the detector."""
-    binning = _checked_binning(binning, int(detector_shape))
-    if nearfield is not None:
-        nearfield = _checked_simulated_nearfield(
-            nearfield, int(detector_shape), binning, psi, probe, eigen_probe,
-            eigen_weights, background, blur)
-    if blur is not None:
-        blur = _checked_simulated_blur(blur, int(detector_shape), binning,
-                                       psi, eigen_probe, eigen_weights,
-                                       background)
-    if background is not None:
-        background = _checked_simulated_background(
-            background, int(detector_shape), binning, psi, eigen_probe,
-            eigen_weights)
+    det = int(detector_shape)
+    detector = _D.build(
+        _D.SIMULATE, det, binning=_checked_binning(binning, det),
+        background=background, blur=blur, nearfield=nearfield,
+        slices=psi.shape[0],
+        eigen=eigen_probe is not None or eigen_weights is not None,
+        window=probe.shape[-1])
+    if detector.kind in ("background", "blur"):  # (of any real dtype)
+        detector = detector._replace(value=np.asarray(
+            A.to_host(detector.value), dtype=np.float32))
+    detector = _D.checked(detector, det)
     check_allowed_positions(scan, psi, probe.shape)
     real, cplx = precision.floating, precision.cfloating
     wanted = ((psi, cplx), (scan, real), (probe, cplx), (eigen_probe, cplx),
               (eigen_weights, real))
-    with Ptycho(int(detector_shape), probe.shape[-1], nz=psi.shape[-2],
-                n=psi.shape[-1], **kwargs) as operator:
+    with Ptycho(det, probe.shape[-1], nz=psi.shape[-2], n=psi.shape[-1],
+                **kwargs) as operator:
         resident = [None if a is None else operator.asarray(a, dtype=t)
                     for a, t in wanted]
+        if detector.value is not None:
+            detector = detector._replace(value=operator.asarray(
+                detector.value, dtype=cplx if detector.kind == "nearfield"
+                else real).contiguous())
         # (`fly` consecutive positions expose one frame: summed by the kernel)
         frames = torch.cat([
             inten for _, _, inten in _intensity_chunks(
-                operator, *resident, fly=int(fly), binning=binning,
-                background=None if background is None else operator.asarray(
-                    background, dtype=real),
-                blur=None if blur is None else operator.asarray(
-                    blur, dtype=real).contiguous(),
-                nearfield=None if nearfield is None else operator.asarray(
-                    nearfield, dtype=cplx).contiguous())])
+                operator, *resident, fly=int(fly), detector=detector)])
         return operator.asnumpy(frames)
-
-
-def _checked_simulated_nearfield(nearfield, det, binning, psi, probe,
-                                 eigen_probe, eigen_weights, background, blur):
-    """The propagator of `simulate` as a host array, after its refusals."""
-    if binning > 1:
-        raise NotImplementedError(
-            f"nearfield with binning={binning} is not implemented")
-    if background is not None:
-        raise NotImplementedError(
-            "nearfield with a background is not implemented")
-    if blur is not None:
-        raise NotImplementedError("nearfield with a blur is not implemented")
-    if psi.shape[0] > 1:
-        raise NotImplementedError(
-            f"nearfield with several slices (psi.shape[0] = {psi.shape[0]}) "
-            "is not implemented")
-    if eigen_probe is not None or eigen_weights is not None:
-        raise NotImplementedError(
-            "nearfield with eigen probes is not implemented")
-    if probe.shape[-1] != det:
-        raise NotImplementedError(
-            f"nearfield with probe window {probe.shape[-1]} != detector "
-            f"{det}: the probe fills the frame in this geometry")
-    return _nearfield.checked_propagator(nearfield, det)
-
-
-def _checked_simulated_blur(blur, det, binning, psi, eigen_probe,
-                            eigen_weights, background):
-    """The kernel of `simulate` as a normalised host array, after its
-    refusals."""
-    if binning > 1:
-        raise NotImplementedError(
-            f"blur with binning={binning} is not implemented")
-    if background is not None:
-        raise NotImplementedError(
-            "blur with a background is not implemented")
-    if psi.shape[0] > 1:
-        raise NotImplementedError(
-            f"blur with several slices (psi.shape[0] = {psi.shape[0]}) is not "
-            "implemented")
-    if eigen_probe is not None or eigen_weights is not None:
-        raise NotImplementedError("blur with eigen probes is not implemented")
-    return _blur.checked_kernel(
-        np.asarray(A.to_host(blur), dtype=np.float32), det)
-
-
-def _checked_simulated_background(background, det, binning, psi, eigen_probe,
-                                  eigen_weights):
-    """The background of `simulate` as a host array, after its refusals."""
-    if binning > 1:
-        raise NotImplementedError(
-            f"background with binning={binning} is not implemented")
-    if psi.shape[0] > 1:
-        raise NotImplementedError(
-            f"background with several slices (psi.shape[0] = {psi.shape[0]}) "
-            "is not implemented")
-    if eigen_probe is not None or eigen_weights is not None:
-        raise NotImplementedError(
-            "background with eigen probes is not implemented")
-    b = np.asarray(A.to_host(background), dtype=np.float32)
-    if b.shape != (det, det):
-        raise ValueError(
-            f"background has shape {b.shape}; expected the detector's "
-            f"({det}, {det})")
-    if not np.all(np.isfinite(b)) or np.any(b < 0):
-        raise ValueError("background must be finite and >= 0")
-    return b
 
 
 def reconstruct(data, parameters, num_gpu=None, use_mpi=False, *, fly=1,
@@ -287,36 +193,23 @@ def reconstruct(data, parameters, num_gpu=None, use_mpi=False, *, fly=1,
     fly = _checked_fly(fly)
     binning = _checked_binning(binning)
     requested = _spawn.requested_devices(num_gpu)
-    if (binning > 1 and requested is not None and len(requested) > 1
+    if (requested is not None and len(requested) > 1
             and _spawn.world_size() == 1):
-        raise NotImplementedError(
-            f"binning={binning} with reconstruct(num_gpu={num_gpu!r}) from a "
-            "plain process: the ranks this call would start do not take "
-            "binned data")
-    if (fly > 1 and requested is not None and len(requested) > 1
-            and _spawn.world_size() == 1):
-        raise NotImplementedError(
-            f"fly={fly} with reconstruct(num_gpu={num_gpu!r}) from a plain "
-            "process: the ranks this call would start do not take fly-scan "
-            "data; launch one process per GPU with torchrun instead")
-    if (background_options is not None and requested is not None
-            and len(requested) > 1 and _spawn.world_size() == 1):
-        raise NotImplementedError(
-            f"background_options with reconstruct(num_gpu={num_gpu!r}) from "
-            "a plain process: the ranks this call would start do not fit a "
-            "background")
-    if (blur_options is not None and requested is not None
-            and len(requested) > 1 and _spawn.world_size() == 1):
-        raise NotImplementedError(
-            f"blur_options with reconstruct(num_gpu={num_gpu!r}) from a plain "
-            "process: the ranks this call would start do not fit a blur "
-            "kernel")
-    if (nearfield_options is not None and requested is not None
-            and len(requested) > 1 and _spawn.world_size() == 1):
-        raise NotImplementedError(
-            f"nearfield_options with reconstruct(num_gpu={num_gpu!r}) from a "
-            "plain process: the ranks this call would start do not take a "
-            "near-field detector plane")
+        for name, given, cannot in (
+                (f"binning={binning}", binning > 1, "take binned data"),
+                (f"fly={fly}", fly > 1, "take fly-scan data; launch one "
+                 "process per GPU with torchrun instead"),
+                ("background_options", background_options is not None,
+                 "fit a background"),
+                ("blur_options", blur_options is not None,
+                 "fit a blur kernel"),
+                ("nearfield_options", nearfield_options is not None,
+                 "take a near-field detector plane")):
+            if given:
+                raise NotImplementedError(
+                    f"{name} with reconstruct(num_gpu={num_gpu!r}) from a "
+                    "plain process: the ranks this call would start do not "
+                    f"{cannot}")
     how, where = _spawn.resolve(num_gpu)
     if how == "spawn":
         return _spawn.reconstruct_spawned(data, parameters, where, **kwargs)
@@ -340,18 +233,18 @@ def reconstruct_multigrid(data, parameters, num_gpu=None, use_mpi=False,
     patterns cropped in Fourier space, every level runs
     `algorithm_options.num_iter` epochs and hands its upsampled result to the
     next."""
-    if _checked_binning(binning) > 1:
-        raise NotImplementedError(
-            f"binning={binning} with reconstruct_multigrid: cropping binned "
-            "diffraction patterns in Fourier space is not implemented")
-    if blur_options is not None:
-        raise NotImplementedError(
-            "blur_options with reconstruct_multigrid: a blur kernel of "
-            "diffraction patterns cropped in Fourier space is not implemented")
-    if nearfield_options is not None:
-        raise NotImplementedError(
-            "nearfield_options with reconstruct_multigrid: near-field frames "
-            "are not cropped in Fourier space")
+    for name, given, why in (
+            (f"binning={binning}", _checked_binning(binning) > 1,
+             "cropping binned diffraction patterns in Fourier space is not "
+             "implemented"),
+            ("blur_options", blur_options is not None,
+             "a blur kernel of diffraction patterns cropped in Fourier space "
+             "is not implemented"),
+            ("nearfield_options", nearfield_options is not None,
+             "near-field frames are not cropped in Fourier space")):
+        if given:
+            raise NotImplementedError(
+                f"{name} with reconstruct_multigrid: {why}")
     data = A.to_host(data)
     coarsest = 2**(num_levels - 1)
     if data.shape[-1] / coarsest < 64:
@@ -623,8 +516,9 @@ class Reconstruction():
 
     fly = 1  # scan positions per diffraction pattern
     binning = 1  # far-plane pixels per measured pixel, per axis
-    _blur = None  # (blur_options, its normalised kernel) or None
-    _nearfield = None  # the checked propagator (host) or None
+    # what the detector does (`operators.detector`; b, K or H on the host)
+    _detector = _D.Detector()
+    _detector_options = None  # the options of a background or a blur
 
     def __init__(self, data, parameters, num_gpu=None, use_mpi=False, *,
                  presharded=False, order=None, batches=None,
@@ -662,26 +556,19 @@ class Reconstruction():
             raise NotImplementedError(
                 f"fly={fly} with local_data (the ranks started by "
                 "reconstruct(num_gpu=N)) is not implemented")
-        background = None
-        if background_options is not None:
-            background = _background.refuse(
-                background_options, parameters, data.shape[-1], fly=fly,
-                binning=binning, data_on_host=data_on_host,
-                local_data=local_data, world_size=_spawn.world_size())
-        blur = None
-        if blur_options is not None:
-            blur = _blur.refuse(
-                blur_options, parameters, data.shape[-1], fly=fly,
-                binning=binning, data_on_host=data_on_host,
-                local_data=local_data, world_size=_spawn.world_size(),
-                background_options=background_options)
-        if nearfield_options is not None:
-            self._nearfield = _nearfield.refuse(
-                nearfield_options, parameters, data.shape[-1],
-                binning=binning, data_on_host=data_on_host,
-                local_data=local_data, world_size=_spawn.world_size(),
-                background_options=background_options,
-                blur_options=blur_options)
+        self._detector = _D.far_field(binning)
+        for kind, options, refuse in (
+                ("background", background_options, _background.refuse),
+                ("blur", blur_options, _blur.refuse),
+                ("nearfield", nearfield_options, _nearfield.refuse)):
+            if options is not None:
+                self._detector = _D.Detector(kind, 1, refuse(
+                    options, parameters, data.shape[-1], binning=binning,
+                    data_on_host=data_on_host, local_data=local_data,
+                    world_size=_spawn.world_size(),
+                    background_options=background_options,
+                    blur_options=blur_options))
+                self._detector_options = options
         name = parameters.algorithm_options.name
         if not hasattr(solvers, name):
             raise NotImplementedError(
@@ -731,14 +618,9 @@ class Reconstruction():
                 1e-9),
         )
         self.operator.fly = fly  # (a rank without a frame reads it: cgrad)
-        self.operator.binning = binning  # (cgrad reads it)
-        # (cgrad reads it; on the device from the first epoch on)
-        self._background = (None if background is None else
-                            (background_options, background))
-        self.operator.background = None
-        self._blur = None if blur is None else (blur_options, blur)
-        self.operator.blur = None
-        self.operator.nearfield = None  # (cgrad reads it; set on entry)
+        # (cgrad reads both; on the device from the first epoch on)
+        self.operator.detector = self._detector._replace(value=None)
+        self.operator.detector_state = None
         self.comm = Comm()
         self._pending_fits = []  # futures of deferred affine position fits
         self._free_snaps = []  # pinned host buffers of finished fits
@@ -834,13 +716,15 @@ class Reconstruction():
         return self._finish_enter()
 
     def _finish_enter(self):
-        if self._background is not None:
-            self.operator.background = _background.State(*self._background)
-        if self._blur is not None:
-            self.operator.blur = _blur.State(*self._blur)
-        if self._nearfield is not None:
-            self.operator.nearfield = _NF.device_propagator(
-                self._nearfield, self.operator.detector_shape)
+        kind, value = self._detector.kind, self._detector.value
+        if kind == "nearfield":
+            self.operator.detector = self._detector._replace(
+                value=_NF.device_propagator(value,
+                                            self.operator.detector_shape))
+        elif value is not None:  # a background or a blur: cgrad's third block
+            self.operator.detector_state = dict(
+                background=_background.State, blur=_blur.State)[kind](
+                    self._detector_options, value)
         self.parameters = solvers.PtychoParameters.split(
             self.local_order,
             x=self._host_parameters()).copy_to_device()
@@ -932,14 +816,11 @@ class Reconstruction():
         returns the same cost.  `parameters.scan` is replaced only after the
         test has passed.  `position_options` is neither needed nor touched."""
         from .solvers.rpie import _positions_flag, _raise_unless_allowed
-        if self._nearfield is not None:
+        if self._detector.kind in ("nearfield", "blur"):
             raise NotImplementedError(
-                "nearfield_options with update_positions_pd: position "
-                "refinement in the near field is not implemented")
-        if self._blur is not None:
-            raise NotImplementedError(
-                "blur_options with update_positions_pd: position refinement "
-                "together with a blur is not implemented")
+                f"{self._detector.kind}_options with update_positions_pd: "
+                "position refinement with this detector model is not "
+                "implemented")
         if self.fly > 1:
             raise NotImplementedError(
                 f"fly={self.fly} with update_positions_pd: position "
@@ -1083,10 +964,8 @@ class Reconstruction():
             g = self._gather_positions
             p.position_options = po._like(g(po.initial_scan),
                                           g(po.confidence), g(po._momentum))
-        if self.operator.background is not None:
-            self.operator.background.write_back()
-        if self.operator.blur is not None:
-            self.operator.blur.write_back()
+        if self.operator.detector_state is not None:
+            self.operator.detector_state.write_back()
         return p
 
     def get_convergence(self):
@@ -1224,7 +1103,8 @@ def _rescale_probe(operator, comm, data, parameters, fly=1, binning=1):
     sums = torch.zeros(2, dtype=torch.float64, device=parameters.psi.device)
     for lo, hi, inten in _intensity_chunks(operator, parameters.psi,
                                            parameters.scan, parameters.probe,
-                                           fly=fly, binning=binning):
+                                           fly=fly,
+                                           detector=_D.far_field(binning)):
         d = A.data_f32(data, lo, hi)
         if mask_u8 is not None:
             m = mask_u8.bool()

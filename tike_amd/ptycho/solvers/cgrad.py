@@ -21,54 +21,40 @@ algorithm options, the allowed-positions test of rpie, and only then the new
 ``parameters.scan``.  The sums need the object projection alone, which the
 gradient pass of the object writes anyway (``_PositionTerms``).
 
-One epoch loop (``cgrad()``) serves three kinds of minibatch, each behind
+One epoch loop (``cgrad()``) serves three routes, each behind
 ``_Minibatch``.  Per minibatch and per recovered variable (the object, then
-the probe) it runs one conjugate-gradient call -- on the device where the
+the probe, then -- where the detector has one -- the root of its fitted
+table) it runs one conjugate-gradient call -- on the device where the
 minibatch offers that and the search succeeds (``_cg_on_device``), else
 ``_host_cg``, the ONE ``opt.conjugate_gradient`` of this module -- and, when
 no variable is recovered, one cost-only evaluation.
 
 * plain (``_CostPlan`` + ``_cost_and_grad``): one pattern per position, a
-  single slice.  The only kind with device line searches, graph capture and
-  position sums.
-* fly scans (``data`` holds one frame per ``fly`` consecutive positions,
-  reference ptycho.py:95-125): the mean over FRAMES of each frame's mean cost
-  over its measured pixels, the intensity of a frame being the sum over its
-  positions and modes (``_fly_cost_and_grad``: forward,
-  ``tike_fly_farplane_gradient``, adjoint, chunk by chunk over whole frames).
-  The device searches form the intensity per position: every line search is
-  decided on the host.
-* binned data (the operator's ``binning`` = B > 1: a far plane B times finer
-  than the patterns, a measured pixel the sum over its B x B far-plane
-  pixels; no reference counterpart): the fly-scan route at any ``fly``, also
-  1, with ``tike_binned_farplane_gradient`` in that kernel's place; the mask
-  and the pixel count are at data resolution.
-* a fitted background (the operator's ``background`` state, set by
-  ``background_options``; no reference counterpart): every pattern is the
-  coherent intensity plus b = a * a per detector pixel.  The fly-scan route
-  at any ``fly``, also 1, with ``tike_background_farplane_gradient`` in that
-  kernel's place, and a THIRD conjugate-gradient call per minibatch, on a
-  (real), after the object's and the probe's.  The intensity does not depend
-  on b: that call forms the minibatch's intensities once (``_Intensities``)
-  and every gradient and line-search trial is then one
-  ``tike_background_sums`` launch -- no forward operator, no transform.
-* a blurred far field (the operator's ``blur`` state, set by
-  ``blur_options``; no reference counterpart): every pattern is the coherent
-  intensity convolved with a (k, k) kernel K = a^2 / sum a^2, cyclically over
-  the detector plane.  The fly-scan route at any ``fly``, also 1: the kernel
-  of that route only stores the chunk's intensities, ``tike_blur_cost_factor``
-  forms costs and the table K (star) (mask l') from them, and
-  ``tike_farplane_scale`` applies the table to the far plane as MINUS the
-  gradient.  The third conjugate-gradient call is on a: the minibatch's
-  intensities are stored once and every gradient and line-search trial is one
-  ``tike_blur_kernel_sums`` launch and k * k numbers of chain in torch.
-* a detector in the near field (the operator's ``nearfield``, set by
-  ``nearfield_options``; no reference counterpart): every pattern is
-  |IFFT2(H FFT2(patch x probe))|^2, probe window = detector, H a fixed
-  propagator.  Whole frames at any ``fly``, also 1:
-  ``_nearfield_cost_and_grad``, whose middle on the 128^2 / 256^2 route is one
-  launch, ``tike_nearfield_plane_gradient`` -- the detector-plane wave never
-  exists in memory.
+  single slice, a far-field detector as fine as the data.  The only route
+  with device line searches, graph capture and position sums.
+* whole frames (``data`` holds one frame per ``fly`` consecutive positions,
+  reference ptycho.py:95-125; also ``fly`` = 1 whenever the operator's
+  ``detector`` -- ``operators.detector``, no reference counterpart -- is not
+  the plain far field): the mean over FRAMES of each frame's mean cost over
+  its measured pixels, the intensity of a frame being the sum over its
+  positions and modes.  Every line search is decided on the host.  What the
+  detector does is the one thing that differs, chunk by chunk:
+
+  - far field, binned (a far plane B times finer than the patterns; the mask
+    and the pixel count are at data resolution), with a background b = a * a
+    per pixel, or blurred by K = a^2 / sum a^2: ``_fly_cost_and_grad`` --
+    forward, ``detector.farplane_step``, adjoint.  A background or a blur
+    that is fitted adds a THIRD conjugate-gradient call per minibatch, on a
+    (real), after the object's and the probe's: the intensity depends on
+    neither, so that call stores the minibatch's intensities once and every
+    gradient and line-search trial is one launch of the ``State``'s
+    ``cost_and_grad`` (``ptycho/background.py``, ``ptycho/blur.py``) -- no
+    forward operator, no transform.
+  - near field (every pattern is |IFFT2(H FFT2(patch x probe))|^2, probe
+    window = detector, H a fixed propagator): ``_nearfield_cost_and_grad``,
+    whose middle on the 128^2 / 256^2 route is one launch,
+    ``tike_nearfield_plane_gradient`` -- the detector-plane wave never exists
+    in memory.
 * objects of several slices (``psi.shape[0] > 1``, probe window = detector):
   the same cost on the far field behind the last slice, e_d = patch(O_d) x
   beam_d, beam_{d+1} = Fresnel(e_d), and its EXACT gradient -- the adjoint
@@ -93,9 +79,9 @@ from ... import _tuning
 from ... import _arrays as A
 from ... import opt
 from ..._lib import check, lib
+from ...operators import detector as D
 from ...operators import nearfield as NF
 from ...operators.propagation import fft_scales
-from .. import blur as _blur
 from ..exitwave import ExitWaveOptions
 from ..position import gaussian_derivative_taps
 from . import _multislice as M
@@ -397,6 +383,9 @@ def _finish_cost(total, comm, op, lo, hi, fly=1):
 DEVICE_LINE_SEARCH = True
 """Tests set this to False to run opt.conjugate_gradient with the host-side
 line search (one read-back per trial) everywhere."""
+
+PLAIN_ROUTE = True
+"""Tests set this to False to send plain minibatches the whole-frames way."""
 
 LINE_SEARCH_SLOTS = (8, 4)
 """Step lengths enqueued ahead per line search to begin with: first CG
@@ -825,145 +814,54 @@ def _fly_adjoint(op, far, probe, scan, psi, want_psi, want_probe):
     return psi_adj, probe_adj
 
 
-class _Intensities:
-    """The intensities (frames, det, det) float32, WITHOUT the background, of
-    a minibatch at the current object and probe: formed once, by the first
-    evaluation of the background block, in a workspace that the other two
-    blocks do not touch."""
-
-    def __init__(self):
-        self.values = None
-
-
-def _background_cost_and_grad(op, data, lo, hi, fly, a, *, want_grad, cm,
-                              stored):
-    """(sum of the per-frame costs at b = a * a, a device scalar; d / d a of
-    that sum = 2 a bgrad, or None) of the frames [lo / fly, hi / fly) from
-    their stored intensities: one `tike_background_sums` launch."""
-    det = op.detector_shape
-    npix = det * det
-    dev = a.device
-    d = data[lo // fly:hi // fly]
-    if d.dtype not in (torch.float32, torch.uint16):
-        d = d.to(torch.float32)
-    b = (a * a).contiguous()
-    partials = torch.zeros(lib.tike_background_sums_partials(npix),
-                           dtype=torch.float64, device=dev)
-    bgrad = torch.empty_like(b) if want_grad else None
-    check(
-        lib.tike_background_sums(
-            A.ptr(stored.values), A.ptr(d), int(d.dtype == torch.uint16),
-            A.ptr(cm.mask), A.ptr(b), None, A.ptr(partials), A.ptr(bgrad),
-            d.shape[0], npix, cm.model, cm.nmeasured, A.stream_ptr()),
-        "cgrad background sums")
-    return partials.sum(), (2 * a * bgrad if want_grad else None)
+def _whole_frames(op, probe, lo, hi, fly):
+    """(chunk, nmax) of an evaluation over the positions [lo, hi), whole
+    frames: positions per chunk (whole frames), the most a chunk holds."""
+    assert lo % fly == 0 and hi % fly == 0, (lo, hi, fly)
+    chunk = max(1, chunk_positions(probe.shape[-3], op.detector_shape)
+                // fly) * fly
+    return chunk, min(chunk, max(hi - lo, 1))
 
 
-def _blur_cost_and_grad(op, data, lo, hi, fly, a, *, want_grad, cm, stored):
-    """(sum of the per-frame costs at K = a^2 / sum a^2, a device scalar;
-    d / d a of that sum, or None) of the frames [lo / fly, hi / fly) from
-    their stored intensities: one `tike_blur_kernel_sums` launch (with the
-    gradient, its k * k lanes of a second), then the chain of
-    ptycho/blur.py, k * k numbers in torch."""
-    d = data[lo // fly:hi // fly]
-    if d.dtype not in (torch.float32, torch.uint16):
-        d = d.to(torch.float32)
-    partials, kgrad = op.blur_kernel_sums(
-        stored.values, _blur.kernel_of(a), d, model=cm.model,
-        measured=cm.mask, num_measured=cm.nmeasured, want_gradient=want_grad)
-    return partials.sum(), (_blur.chain(a, kgrad) if want_grad else None)
+def _frame_costs(op, nframe, dev):
+    """The workspace's costs of the frames of an evaluation."""
+    return _workspace(op).get("costs", (max(nframe, 1),), torch.float32,
+                              dev)[:nframe]
 
 
 def _fly_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, fly, *,
-                       want_psi, want_probe, want_grad, cm, binning=1,
-                       background=None, stored=None, blur=None):
+                       want_psi, want_probe, want_grad, cm,
+                       detector=D.Detector(), stored=None):
     """(sum of this rank's per-frame costs, a device scalar; d cost / d psi or
     None; d cost / d probe or None -- unnormalised adjoints summed over the
     ranks) of the positions [lo, hi), whole frames: the data rows
     [lo / fly, hi / fly).  Per chunk of whole frames: the forward operator,
-    `tike_fly_farplane_gradient` (costs only for a line-search probe: the far
+    the far-plane step of `detector`, a far-field kind
+    (`detector.farplane_step`; costs only for a line-search probe: the far
     plane is read once and not written) and, for a gradient, the adjoint of
-    the far plane it left.  binning > 1 (any fly): the data rows and the mask
-    are `binning` times coarser than the far plane and
-    `tike_binned_farplane_gradient` stands in that kernel's place.
-    background (det, det) float32: costs and gradients at intensity +
-    background, `tike_background_farplane_gradient` in that kernel's place.
-    stored (with background, cost only): the `_Intensities` that receive the
-    frames' intensities without the background.
-    blur (k, k) float32: costs and gradients at blur (*) intensity, the
-    cyclic convolution of ptycho/blur.py.  `tike_fly_farplane_gradient` then
-    only stores the chunk's intensities (one read of the far plane, nothing
-    written to it), `tike_blur_cost_factor` forms the costs from them and, for
-    a gradient, the table blur (star) (mask l') -- upstream num_measured, so
-    that the factor is the unnormalised one of the other routes --, which
-    `tike_farplane_scale` applies to the far plane as MINUS the gradient: per
-    gradient evaluation the far plane crosses HBM five times (written by the
-    forward, read for the intensities, read and written by the scaling, read
-    by the adjoint), once more than without a blur.  stored (with blur, cost
-    only): receives the frames' intensities, which do not depend on the
-    kernel."""
-    assert lo % fly == 0 and hi % fly == 0, (lo, hi, fly)
+    the far plane it left.  stored (frames, det, det) float32 (background and
+    blur, cost only): receives the frames' intensities without the background
+    or the blur."""
     dev = psi.device
     S, det = probe.shape[-3], op.detector_shape
-    N = hi - lo
-    ws = _workspace(op)
-    chunk = max(1, chunk_positions(S, det) // fly) * fly  # whole frames
-    far_all = ws.get("far", (min(chunk, max(N, 1)), 1, S, det, det),
-                     torch.complex64, dev)
-    costs = ws.get("costs", (max(N // fly, 1),), torch.float32, dev)[:N // fly]
+    chunk, nmax = _whole_frames(op, probe, lo, hi, fly)
+    far_all = _workspace(op).get("far", (nmax, 1, S, det, det),
+                                 torch.complex64, dev)
+    costs = _frame_costs(op, (hi - lo) // fly, dev)
     grads, gpsi, gprobe = _gradient_buffer(
         psi, probe, want_grad and want_psi, want_grad and want_probe)
-    if stored is not None:
-        stored.values = ws.get("background_intensity",
-                               (max(N // fly, 1), det, det), torch.float32,
-                               dev)[:N // fly]
-    if blur is not None:
-        nchunk = max(min(chunk, max(N, 1)) // fly, 1)
-        inten_all = ws.get("blur_intensity", (nchunk, det, det), torch.float32,
-                           dev)
-        table_all = ws.get("blur_table", (nchunk, det, det), torch.float32,
-                           dev)
-        # upstream = num_measured: (float)(n * (1 / n)) = 1, the table is the
-        # unnormalised blur (star) (mask l')
-        unit = ws.get("blur_upstream", (nchunk,), torch.float32, dev)
-        unit.fill_(float(cm.nmeasured))
+    work = D.workspaces(detector, _workspace(op), dev, max(nmax // fly, 1),
+                        det, cm)
     for clo in range(lo, hi, chunk):
         chi = min(hi, clo + chunk)
         sc = scan[clo:chi]
         far = far_all[:chi - clo]
         op.fwd_device(probe, sc, psi, out=far)
-        d = data[clo // fly:chi // fly]
-        if d.dtype not in (torch.float32, torch.uint16):
-            d = d.to(torch.float32)
-        how = dict(model=cm.model, measured=cm.mask,
-                   num_measured=cm.nmeasured,
-                   costs=costs[(clo - lo) // fly:(chi - lo) // fly],
-                   apply_gradient=want_grad)
-        if blur is not None:
-            nf = (chi - clo) // fly
-            inten = (inten_all[:nf] if stored is None else
-                     stored.values[(clo - lo) // fly:(chi - lo) // fly])
-            op.fly_farplane_gradient(far, d, fly, intensity=inten)
-            table = table_all[:nf] if want_grad else None
-            op.blur_cost_factor(inten, blur, d, model=cm.model,
-                                measured=cm.mask, num_measured=cm.nmeasured,
-                                upstream=unit[:nf], costs=how["costs"],
-                                table=table)
-            if want_grad:
-                check(
-                    lib.tike_farplane_scale(A.ptr(far), A.ptr(table), nf,
-                                            S * fly, det * det, -1.0,
-                                            A.stream_ptr()),
-                    "cgrad blur (table applied to the far plane)")
-        elif background is not None:
-            if stored is not None:
-                how["intensity"] = stored.values[(clo - lo) // fly:
-                                                 (chi - lo) // fly]
-            op.background_farplane_gradient(far, d, fly, background, **how)
-        elif binning > 1:
-            op.binned_farplane_gradient(far, d, fly, binning, **how)
-        else:
-            op.fly_farplane_gradient(far, d, fly, **how)
+        frames = slice((clo - lo) // fly, (chi - lo) // fly)
+        D.farplane_step(
+            op, detector, far, A.counts(data[clo // fly:chi // fly]), fly, cm,
+            costs=costs[frames], want_grad=want_grad,
+            intensity=None if stored is None else stored[frames], work=work)
         if want_grad:
             # the far plane now holds MINUS the gradient
             a, b = _fly_adjoint(op, far, probe, sc, psi, want_psi, want_probe)
@@ -992,28 +890,22 @@ def _nearfield_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, fly, *,
     the planes per gradient evaluation.  upstream = num_measured and scale =
     -1 (the blur route's convention): the wave carries MINUS the unnormalised
     gradient."""
-    assert lo % fly == 0 and hi % fly == 0, (lo, hi, fly)
     dev = psi.device
     S, det = probe.shape[-3], op.detector_shape
     Hh, W = psi.shape[-2:]
-    N = hi - lo
     ws = _workspace(op)
     how = NF.route(op.probe_shape, det, S)
     fused = how != "general"
-    chunk = max(1, chunk_positions(S, det) // fly) * fly  # whole frames
-    nmax = min(chunk, max(N, 1))
+    chunk, nmax = _whole_frames(op, probe, lo, hi, fly)
     bufs = NF.buffers(ws, dev, nmax, S, det, fly, how)
-    costs = ws.get("costs", (max(N // fly, 1),), torch.float32, dev)[:N // fly]
+    costs = _frame_costs(op, (hi - lo) // fly, dev)
     want_psi, want_probe = want_grad and want_psi, want_grad and want_probe
     # (fused: the planar accumulator of the grouped scatter)
     grads, gpsi, gprobe = _gradient_buffer(
         psi, probe, want_psi, want_probe,
         planar=(1, 2, Hh, W) if fused else None)
-    # upstream = num_measured: (float)(n * (1 / n)) = 1, the factor is the
-    # unnormalised l'
-    unit = ws.get("nearfield_upstream", (max(nmax // fly, 1),), torch.float32,
-                  dev)
-    unit.fill_(float(cm.nmeasured))
+    unit = D.upstream_unit(ws, "nearfield_upstream", max(nmax // fly, 1), dev,
+                           cm.nmeasured)
     if fused and want_grad:
         objproj = ws.get("nearfield_objproj", (nmax, det, det),
                          torch.complex64, dev)
@@ -1023,9 +915,7 @@ def _nearfield_cost_and_grad(op, comm, data, psi, scan, probe, lo, hi, fly, *,
         chi = min(hi, clo + chunk)
         sc = scan[clo:chi]
         n = chi - clo
-        d = data[clo // fly:chi // fly]
-        if d.dtype not in (torch.float32, torch.uint16):
-            d = d.to(torch.float32)
+        d = A.counts(data[clo // fly:chi // fly])
         wave, finished = NF.wave_and_back(
             op, psi, sc, probe, H, d, fly, how, bufs, model=cm.model,
             measured=cm.mask, num_measured=cm.nmeasured,
@@ -1203,14 +1093,20 @@ class _Minibatch:
         (this rank's cost sum, a device float64 scalar; with want_grad MINUS
         d cost / d variable -- the unnormalised adjoint, summed over the ranks
         -- else None).  variable: 0 the object, 1 the probe, 2 the root a of
-        the background (minibatches with a background only; `a` is then the
-        point of evaluation, psi and probe those of the block's start), None
-        cost only.
+        the detector's fitted table (minibatches with a `state` only; `a` is
+        then the point of evaluation, psi and probe those of the block's
+        start), None cost only.
         position_terms: plain minibatches only, see `_cost_and_grad`.
+    start(psi, probe, variable) -> where the conjugate gradient of `variable`
+        starts.
     finish(total) -> the mean cost over all ranks, a host float: the one
         read-back of an evaluation.
     on_device: line searches may be decided on the device (`_cg_on_device`,
         which wants `plan` and `count`): plain minibatches only.
+
+    detector: the `operators.detector.Detector` of the reconstruction; state:
+    the `State` of ptycho/background.py or ptycho/blur.py, whose `value` then
+    stands in the detector's, or None.
 
     Every rank builds every minibatch and makes every collective, whatever
     its share."""
@@ -1218,40 +1114,23 @@ class _Minibatch:
     on_device = False
 
     def __init__(self, op, comm, data, psi, scan, probe, lo, hi, cm, fly,
-                 binning=1, background=None, nearfield=None):
+                 detector=D.Detector(), state=None):
         self.where = (op, comm, data), scan, (lo, hi)
-        # `background`: the state of the third block, the `State` of
-        # ptycho/background.py or that of ptycho/blur.py (never both)
-        blur = background if isinstance(background, _blur.State) else None
-        background = None if blur is not None else background
-        self.background = background  # the `State` of ptycho/background.py
-        self.blur = blur  # the `State` of ptycho/blur.py
-        self.stored = None  # `_Intensities` of the third block
+        self.detector, self.state = detector, state
+        self.stored = None  # the intensities of the third block
         self.finish = lambda total: _finish_cost(total, comm, op, lo, hi, fly)
-        if nearfield is not None:
-            # the detector in the near field (ptycho/nearfield.py): whole
-            # frames at any fly, also 1
-            if lo % fly or hi % fly:
-                raise ValueError(
-                    f"minibatch [{lo}, {hi}) does not hold whole frames of "
-                    f"fly={fly} positions")
-            global_count(comm, op, lo, hi)
-            self.run = _nearfield_cost_and_grad
-            self.how = dict(cm=cm, fly=fly, H=nearfield)
-        elif psi.shape[0] > 1:  # (every evaluation splits into the same chunks)
+        if psi.shape[0] > 1:  # (every evaluation splits into the same chunks)
             self.run = _multislice_cost_and_grad
             self.how = dict(cm=cm, chunk=_multislice_chunk(op, psi, probe))
-        elif (fly > 1 or binning > 1 or background is not None
-              or blur is not None):
+        elif fly > 1 or detector.kind != "far" or not PLAIN_ROUTE:
             if lo % fly or hi % fly:
                 raise ValueError(
                     f"minibatch [{lo}, {hi}) does not hold whole frames of "
                     f"fly={fly} positions")
             global_count(comm, op, lo, hi)  # (all-reduced ahead of the passes)
-            self.run = _fly_cost_and_grad
+            self.run = (_nearfield_cost_and_grad
+                        if detector.kind == "nearfield" else _fly_cost_and_grad)
             self.how = dict(cm=cm, fly=fly)
-            if binning > 1:
-                self.how["binning"] = binning
         else:
             self.plan = _CostPlan(op, data, psi, scan, probe, lo, hi, cm)
             self.run = _cost_and_grad
@@ -1270,46 +1149,45 @@ class _Minibatch:
                                                   self.on_device))
             self.count = global_count(comm, op, lo, hi)
 
+    def start(self, psi, probe, variable):
+        return (psi, probe, getattr(self.state, "a", None))[variable]
+
     def evaluate(self, psi, probe, variable, want_grad, position_terms=None,
                  a=None):
-        args, scan, span = self.where
+        (op, comm, data), scan, (lo, hi) = self.where
         how = self.how if position_terms is None else dict(
             self.how, position_terms=position_terms)
-        if variable == 2 and self.blur is not None:
+        if self.run is _nearfield_cost_and_grad:
+            how = dict(how, H=self.detector.value)
+        elif self.run is _fly_cost_and_grad:
+            how = dict(how, detector=self.detector if self.state is None else
+                       self.detector._replace(value=self.state.value))
+        if variable == 2:
+            fly = how["fly"]
             if self.stored is None:
                 # the intensities at the block's object and probe, once: they
-                # do not depend on the kernel
-                self.stored = _Intensities()
-                self.run(*args, psi, scan, probe, *span, want_psi=False,
-                         want_probe=False, want_grad=False,
-                         blur=self.blur.kernel, stored=self.stored, **how)
-            return _blur_cost_and_grad(
-                args[0], args[2], *span, how["fly"], a, want_grad=want_grad,
-                cm=how["cm"], stored=self.stored)
-        if variable == 2:
-            if self.stored is None:
-                # the intensities at the block's object and probe, once
-                self.stored = _Intensities()
-                self.run(*args, psi, scan, probe, *span, want_psi=False,
-                         want_probe=False, want_grad=False,
-                         background=self.background.b, stored=self.stored,
-                         **how)
-            return _background_cost_and_grad(
-                args[0], args[2], *span, how["fly"], a, want_grad=want_grad,
-                cm=how["cm"], stored=self.stored)
-        if self.background is not None:
-            how = dict(how, background=self.background.b)
-        if self.blur is not None:
-            how = dict(how, blur=self.blur.kernel)
-        r = self.run(*args, psi, scan, probe, *span, want_psi=variable == 0,
-                     want_probe=variable == 1, want_grad=want_grad, **how)
+                # depend on neither the background nor the kernel
+                nframe = (hi - lo) // fly
+                self.stored = _workspace(op).get(
+                    "background_intensity",
+                    (max(nframe, 1), op.detector_shape, op.detector_shape),
+                    torch.float32, psi.device)[:nframe]
+                self.run(op, comm, data, psi, scan, probe, lo, hi,
+                         want_psi=False, want_probe=False, want_grad=False,
+                         stored=self.stored, **how)
+            return self.state.cost_and_grad(
+                op, A.counts(data[lo // fly:hi // fly]), self.stored, a,
+                how["cm"], want_grad)
+        r = self.run(op, comm, data, psi, scan, probe, lo, hi,
+                     want_psi=variable == 0, want_probe=variable == 1,
+                     want_grad=want_grad, **how)
         return r[0], None if variable is None else r[1 + variable]
 
 
 def _host_cg(minibatch, psi, probe, variable, o, positions=None):
     """`opt.conjugate_gradient` on the object (variable 0), the probe (1) or
-    the root of the background (2: real float32, the minibatch's
-    `background.a`) of one minibatch, every line search decided on the host:
+    the root of the detector's fitted table (2: real float32, the `a` of the
+    minibatch's `state`) of one minibatch, every line search decided on the host:
     (x, mean cost).
     positions: the `_PositionTerms` of the epoch; the first gradient pass
     takes the minibatch's sums if they are still owed.
@@ -1337,9 +1215,7 @@ def _host_cg(minibatch, psi, probe, variable, o, positions=None):
         return [g]
 
     return opt.conjugate_gradient(
-        torch, x=(psi, probe, getattr(
-            minibatch.background if minibatch.blur is None else
-            minibatch.blur, "a", None))[variable],
+        torch, x=minibatch.start(psi, probe, variable),
         cost_function=cost, grad=grad,
         dir_multi=lambda x: x[0], num_iter=o.cg_iter,
         step_length=o.step_length)
@@ -1353,12 +1229,10 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
     saw the old positions, as in lstsq_grad and rpie)."""
     o = parameters.algorithm_options
     fly = _fly_of(op, data, parameters.scan)
-    binning = int(getattr(op, "binning", 1))
-    _refuse(parameters, fly, binning=binning)
-    background = getattr(op, "background", None)
-    blur = getattr(op, "blur", None)
-    third = background if blur is None else blur  # (never both: refused)
-    nearfield = getattr(op, "nearfield", None)  # (with neither: refused)
+    # what `Reconstruction` set; an operator of another maker: the far field
+    detector = getattr(op, "detector", D.Detector())
+    third = getattr(op, "detector_state", None)
+    _refuse(parameters, fly, binning=detector.binning)
     recover = (parameters.object_options is not None,
                parameters.probe_options is not None
                and epoch >= parameters.probe_options.update_start,
@@ -1367,7 +1241,7 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
     psi, probe, scan = parameters.psi, parameters.probe, parameters.scan
     # (the mask and the pixel count are at data resolution)
     cm = _cost_model(parameters.exitwave_options,
-                     op.detector_shape // binning)
+                     detector.width(op.detector_shape))
     position_options = parameters.position_options  # (plain minibatches only)
     positions = None
     if position_options is not None:
@@ -1385,8 +1259,7 @@ def cgrad(parameters, data, batches, comm, *, op, epoch):
         hi = lo + len(b)
         comm.minibatch = batch_index
         mb = _Minibatch(op, comm, data, psi, scan, probe, lo, hi, cm, fly,
-                        binning, third,
-                        **({} if nearfield is None else dict(nearfield=nearfield)))
+                        detector, third)
         if positions is not None:
             positions.pending = True
             # the object's first gradient pass writes the projection the sums

@@ -153,6 +153,7 @@ def gradient_legs(det, S, frames, fly, repeats, k=5):
     against zero background, and the legs of a chunk of the blur route."""
     import importlib
     cg = importlib.import_module("tike_amd.ptycho.solvers.cgrad")
+    from tike_amd.operators.detector import Detector
     from tike_amd.ptycho import background as B
     from tike_amd.ptycho import blur as U
     K = gaussian_kernel(k)
@@ -172,7 +173,7 @@ def gradient_legs(det, S, frames, fly, repeats, k=5):
                 np.zeros((det, det), np.float32)))
         for name, state in states.items():
             mb = cg._Minibatch(op, comm, ctx.data, p.psi, p.scan, p.probe, 0,
-                               N, cm, fly, 1, state)
+                               N, cm, fly, Detector(name), state)
             out[f"{name}_gradient_ms"] = timed(
                 lambda: mb.evaluate(p.psi, p.probe, 0, True), NOTHING,
                 repeats)
@@ -207,7 +208,7 @@ def gradient_legs(det, S, frames, fly, repeats, k=5):
             adjoint=lambda: cg._fly_adjoint(op, far, p.probe, sc, p.psi, True,
                                             False),
             background=lambda: op.background_farplane_gradient(
-                far, d, fly, states["background"].b,
+                far, d, fly, states["background"].value,
                 model=cm.model, measured=cm.mask, num_measured=cm.nmeasured,
                 costs=costs, apply_gradient=True))
         fwd()

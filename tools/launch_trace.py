@@ -3,7 +3,7 @@
 tools/kernel_identity.py for `tike_amd.autograd` and for the solver code that
 shares its multislice walk (not a test):
 
-    python tools/launch_trace.py OUT.json           # in each of two trees
+    python tools/launch_trace.py OUT.json [GROUP]   # in each of two trees
     python tools/launch_trace.py --compare A.json B.json
 
 The first form starts a fresh child process under TIKE_DETERMINISTIC=1 that
@@ -14,7 +14,10 @@ the test helpers that take every branch -- one chunk and three chunks
 lever flipped -- and then `solver_scenarios`: cgrad's multislice cost and
 gradient, rpie's near-plane gradients of an object of slices and one
 minibatch of lstsq's unfused route, each on the smallest shapes that take every
-branch.  Per scenario OUT.json holds the launches (the entry, null /
+branch, and `detector_scenarios`: fly scans, binning, a background, a blur
+and the near field through cgrad, `simulate`, the operator's cost and
+`autograd.cost`.  GROUP ("autograd", "solver" or "detector") runs that group
+alone.  Per scenario OUT.json holds the launches (the entry, null /
 non-null for each pointer, the value of every other argument), the SHA-256 of
 each output tensor (the solver scenarios run twice in the process: an output
 whose bits differ between the two runs -- `tike_conv_adj` sums by float atomics
@@ -218,7 +221,187 @@ def solver_scenarios(record, C, L, dev):
     L.GENERAL_FUSED, L.PFA_ROUTE = saved
 
 
-def child(out):
+def detector_scenarios(record, L, dev):
+    """What lies between the sample and the counts -- fly scans, binning, a
+    background, a blur, the near field -- through names both trees have:
+    `tp.reconstruct` (one epoch of cgrad, cg_iter 2), `tp.simulate`,
+    `Ptycho.cost`, `Ptycho._compute_intensity`, `autograd.cost` and its
+    backward, on the smallest problems of the test helpers; and one plain
+    128^2 cgrad call."""
+    import background as bg
+    import binned as bn
+    import blur as bl
+    import fly_scan as fs
+    import nearfield as nf
+    import numpy as np
+    import torch
+
+    import tike_amd.operators as ops
+    import tike_amd.ptycho as tp
+    from tike_amd import autograd as ag
+    from tike_amd.operators import nearfield as NF
+    to = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    host = lambda xs: [torch.from_numpy(np.ascontiguousarray(x)) for x in xs]
+
+    def problems():
+        """(label, problem, det, fly, keywords of reconstruct with the first
+        guess of the third block (update -> keywords), keywords of the
+        operator's and simulate's entries, the third block's name or None)"""
+        none = lambda update: {}
+        P = fs.problem(obj=96, pw=32, det=32, S=2, fly=2, nframe=12, seed=3,
+                       amp=1.0, mix=0.3, dim=0.5)
+        yield "fly2", P, 32, 2, none, {}, None
+        for fly in bn.SOLVER_FLY:
+            yield (f"binned fly{fly}", bn.problem(fly, **bn.SOLVER), 32, fly,
+                   lambda update: dict(binning=bn.SOLVER["B"]),
+                   dict(binning=bn.SOLVER["B"]), None)
+        for case in ("fly1", "fly2"):
+            fly = bl.SOLVER_CASES[case]["fly"]
+            P = bg.solver_problem(case)
+            yield (f"background {case}", P, 32, fly,
+                   lambda update, P=P: dict(
+                       background_options=tp.BackgroundOptions(
+                           P["b0"].copy(), update=update)),
+                   dict(background=P["background"]), "background")
+            P = bl.solver_problem(case)
+            yield (f"blur {case}", P, 32, fly,
+                   lambda update, P=P: dict(blur_options=tp.BlurOptions(
+                       P["k0"].copy(), update=update)),
+                   dict(blur=P["kernel"]), "blur")
+        for fly in (1, 2):
+            P = nf.solver_problem(fly)
+            yield (f"nearfield128 fly{fly}", P, 128, fly,
+                   lambda update, P=P: dict(
+                       nearfield_options=tp.NearFieldOptions(P["H"].copy())),
+                   dict(nearfield=P["H"]), None)
+        P = nf.problem(32, 2, 2, 6, seed=5)
+        P.update(data=nf.simulate(32, P["probe"], P["scan"], P["psi"], 2,
+                                  P["H"]).astype(np.float32),
+                 psi0=np.ones_like(P["psi"]),
+                 probe0=(0.9 * P["probe"]).astype(np.complex64))
+        yield ("nearfield32 fly2", P, 32, 2,
+               lambda update, P=P: dict(
+                   nearfield_options=tp.NearFieldOptions(P["H"].copy())),
+               dict(nearfield=P["H"]), None)
+
+    def parameters(P, model, mask, recover_probe):
+        return tp.PtychoParameters(
+            probe=P["probe0"].copy(), psi=P["psi0"].copy(),
+            scan=P["scan"].copy(),
+            algorithm_options=tp.CgradOptions(
+                num_batch=1, cg_iter=2, num_iter=1, step_length=1.0,
+                batch_method="contiguous"),
+            probe_options=tp.ProbeOptions(init_rescale_from_measurements=False)
+            if recover_probe else None,
+            object_options=tp.ObjectOptions(),
+            exitwave_options=tp.ExitWaveOptions(measured_pixels=mask,
+                                                noise_model=model))
+
+    def solve(label, P, fly, options, third):
+        """One epoch, over minibatches, noise models, chunks and what is
+        recovered; uint16 counts once."""
+        N, w = len(P["scan"]), P["data"].shape[-1]
+        every, measured = np.ones((w, w), bool), np.nan_to_num(P["data"])
+        noise = [("gaussian", every, measured),
+                 ("poisson", fs.block_mask(w),
+                  fs.masked(measured, fs.block_mask(w))),
+                 ("gaussian u16", every,
+                  np.round(measured).astype(np.uint16))]
+        recover = [(False, None), (True, None)]
+        if third:
+            recover = [(p, u) for p, _ in recover for u in (True, False)]
+        for nbatch in (1, 2):
+            n = N // nbatch
+            assert n % fly == 0, (label, n, fly)
+            batches = [np.arange(i * n, (i + 1) * n) for i in range(nbatch)]
+            # a full chunk of whole frames, then a partial one
+            for chunk in (0, (n // fly // 2 + 1) * fly):
+                L.CHUNK_POSITIONS_OVERRIDE = chunk
+                for model, mask, data in noise:
+                    for probe, update in recover:
+                        if "u16" in model and (nbatch, probe) != (1, True):
+                            continue
+
+                        def run():
+                            kw = options(update)
+                            got = tp.reconstruct(
+                                data, parameters(P, model.split()[0], mask,
+                                                 probe),
+                                fly=fly, order=np.arange(N), batches=batches,
+                                **kw)
+                            fitted = [getattr(o, dict(
+                                background="background", blur="kernel")[third])
+                                      for o in kw.values()] if third else []
+                            return host([got.psi, got.probe, np.asarray(
+                                got.algorithm_options.costs)] + fitted)
+
+                        record(f"cgrad {label} batches {nbatch} chunk {chunk} "
+                               f"{model} probe={probe} update={update}", run)
+        L.CHUNK_POSITIONS_OVERRIDE = 0
+
+    def entries(label, P, det, fly, kw):
+        """simulate, the operator's two entries and autograd.cost."""
+        pw = P["probe"].shape[-1]
+        record(f"simulate {label}", lambda: host([tp.simulate(
+            det, P["probe"], P["scan"], P["psi"], fly=fly, **kw)]))
+        dkw = {k: (v if isinstance(v, int) else to(v)) for k, v in kw.items()}
+        x = dict(psi=to(P["psi0"]), probe=to(P["probe0"]), scan=to(P["scan"]))
+        w = P["data"].shape[-1]
+        mask = fs.block_mask(w)
+        counts = {"gaussian": (to(np.nan_to_num(P["data"])), None),
+                  "poisson": (to(np.round(np.nan_to_num(P["data"])).astype(
+                      np.uint16)), to(mask))}
+        fitted = [k for k in ("background", "blur") if k in kw]
+        with ops.Ptycho(det, pw, nz=P["psi"].shape[-2],
+                        n=P["psi"].shape[-1]) as op:
+            record(f"intensity {label}", lambda: list(op._compute_intensity(
+                None, x["psi"], x["scan"], x["probe"], fly=fly, **dkw)))
+            for model, (data, m) in counts.items():
+                record(f"Ptycho.cost {label} {model}", lambda: [op.cost(
+                    data, x["psi"], x["scan"], x["probe"], model=model,
+                    fly=fly, **dkw)])
+                up = to(np.random.default_rng(1).random(
+                    data.shape[0]).astype(np.float32) + 0.5)
+                for chunk in (0, (len(P["scan"]) // fly // 2 + 1) * fly):
+                    L.CHUNK_POSITIONS_OVERRIDE = chunk
+                    for names in (("psi", "probe", "scan") + tuple(fitted),
+                                  tuple(fitted)):
+                        if not names:
+                            continue
+
+                        def run():
+                            leaves = {k: v.clone().requires_grad_(k in names)
+                                      for k, v in {**x, **dkw}.items()
+                                      if isinstance(v, torch.Tensor)}
+                            out = ag.cost(
+                                op, data, leaves["psi"], leaves["probe"],
+                                leaves["scan"], model=model,
+                                measured_pixels=m, fly=fly,
+                                **{k: leaves.get(k, v)
+                                   for k, v in dkw.items()})
+                            return (out,) + torch.autograd.grad(
+                                out, [leaves[k] for k in names],
+                                grad_outputs=up)
+
+                        record(f"autograd.cost {label} {model} chunk {chunk} "
+                               f"wrt {','.join(names)}", run)
+                L.CHUNK_POSITIONS_OVERRIDE = 0
+
+    for label, P, det, fly, options, kw, third in problems():
+        solve(label, P, fly, options, third)
+        entries(label, P, det, fly, kw)
+        if label.startswith("nearfield128"):
+            NF.FUSED = False
+            solve(label + " FUSED=False", P, fly, options, third)
+            entries(label + " FUSED=False", P, det, fly, kw)
+            NF.FUSED = True
+    # the plain route, untouched
+    P = fs.problem(obj=170, pw=128, det=128, S=2, fly=1, nframe=8, seed=1,
+                   amp=1.0, mix=0.3, dim=0.5)
+    solve("plain128", P, 1, lambda update: {}, None)
+
+
+def child(out, only=None):
     import importlib
 
     import autograd_cost
@@ -261,10 +444,13 @@ def child(out):
         return ["unstable", float(np.linalg.norm(v)),
                 float(v @ np.cos(0.37 * np.arange(v.size)))]
 
-    def record(key, fn, twice=False):
+    def record(key, fn, twice=False, strict=True):
         """twice: the call is made again and an output whose bits differ
         between the two is recorded as "unstable" with its `gist`, not by its
-        hash (sums by float atomics in either mode: `tike_conv_adj`)."""
+        hash (sums by float atomics in either mode: `tike_conv_adj`).  strict
+        False: launches that differ between the two calls (what a process
+        sets up once) are recorded as they are, those of the second call
+        under "again", and `--compare` holds both trees to both."""
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
         torch.cuda.reset_peak_memory_stats()
@@ -276,10 +462,12 @@ def child(out):
         if twice:
             trace[:] = []
             again = digests(fn())[0]
-            assert trace == launches, key
+            assert trace == launches or not strict, key
+            extra = {} if trace == launches else dict(again=list(trace))
             hashes = [a if a == b else gist(t)
                       for a, b, t in zip(hashes, again, outs)]
         results[key] = dict(launches=launches, peak=peak, hashes=hashes)
+        results[key].update(extra if twice else {})
         return results[key]
 
     def shapes():
@@ -373,7 +561,7 @@ def child(out):
             for key, fn in calls.items():
                 record(f"{label}: {key}", fn)
 
-    for shape in shapes():
+    for shape in shapes() if only in (None, "autograd") else ():
         for chunks in (0, 5):
             lstsq.CHUNK_POSITIONS_OVERRIDE = chunks
             scenarios(f"{shape[0]} chunk {chunks}", *shape[1:])
@@ -383,8 +571,22 @@ def child(out):
             setattr(modules[module], lever, not value)
             scenarios(f"fused {lever}={not value}", *shape[1:])
             setattr(modules[module], lever, value)
-    solver_scenarios(lambda key, fn: record(key, fn, twice=True),
-                     modules["cgrad"], lstsq, dev)
+    twice = lambda key, fn: record(key, fn, twice=True)  # noqa: E731
+    if only in (None, "solver"):
+        solver_scenarios(twice, modules["cgrad"], lstsq, dev)
+    if only in (None, "detector"):
+        from tike_amd import _arrays
+        _arrays.current_device()  # (once per process: tike_set_deterministic)
+        # (what is not bit-stable is the atomics' of the general adjoint, at
+        # det 32 and with the near field's FUSED off: the other 128^2
+        # scenarios are held to their bits)
+        detector_scenarios(
+            lambda key, fn: record(
+                key, fn, strict=False,
+                twice="128" not in key or "FUSED=False" in key), lstsq, dev)
+        differ = [k for k, r in results.items() if "again" in r]
+        print(f"{len(differ)} scenarios whose second call launches otherwise",
+              differ[:5])
     with open(out, "w") as fh:
         json.dump(results, fh, default=str)
     unstable = [k for k, r in results.items()
@@ -398,8 +600,8 @@ if __name__ == "__main__":
     if sys.argv[1] == "--compare":
         sys.exit(compare(*sys.argv[2:4]))
     if sys.argv[1] == "--child":
-        sys.exit(child(sys.argv[2]))
+        sys.exit(child(*sys.argv[2:4]))
     # a fresh process: the library reads TIKE_DETERMINISTIC when it is loaded
     sys.exit(subprocess.run(
-        [sys.executable, os.path.abspath(__file__), "--child", sys.argv[1]],
+        [sys.executable, os.path.abspath(__file__), "--child"] + sys.argv[1:3],
         env=dict(os.environ, TIKE_DETERMINISTIC="1"), timeout=900).returncode)
