@@ -147,6 +147,189 @@ def test_cluster_entries_on_the_host():
                                        ctypes.byref(moved)) == 1000001
 
 
+import pytest
+
+_P, _H = ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)
+_I, _LONG, _F, _D = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
+
+
+def test_parse_header_reads_declarations_and_constants():
+    """The binding's reading of a header, on text written here: comments,
+    declarations over several lines, empty lists, every kind of parameter."""
+    constants, entries = L.parse_header("""
+/* int tike_in_a_block_comment(int n);
+ * int tike_in_it_too(void); */
+// int tike_in_a_line_comment(long n);
+#define TIKE_X 12 /* c */
+#define TIKE_GUARD_H
+#define TIKE_Y 1000001
+int tike_void(void);   // int tike_after_code(void);
+int tike_empty();
+const char* tike_x(void);
+int tike_four_lines(const void* in, void* out,  /* (nimage, H, W) */
+                    long ntile, long,
+                    int n, float scale, double
+                    eps, void* stream);
+int tike_pointers(void** h, const unsigned char* m, const long* p, int* q,
+                  const float *a, double* const b, void *);
+""")
+    assert constants == {"TIKE_X": 12, "TIKE_Y": 1000001}
+    assert list(entries) == ["tike_void", "tike_empty", "tike_x",
+                             "tike_four_lines", "tike_pointers"]
+    assert entries["tike_void"] == ("int", [])
+    assert entries["tike_empty"] == ("int", [])
+    assert entries["tike_x"] == ("const char*", [])
+    ret, args = entries["tike_four_lines"]
+    assert ret == "int" and len(args) == 8
+    for got, want in zip(args, [_P, _P, _LONG, _LONG, _I, _F, _D, _P]):
+        assert got is want
+    ret, args = entries["tike_pointers"]
+    assert ret == "int" and len(args) == 7
+    for got, want in zip(args, [_H, _P, _P, _P, _P, _P, _P]):
+        assert got is want
+
+
+@pytest.mark.parametrize("params, position, text", [
+    ("int a, size_t n", 2, "size_t n"),
+    ("unsigned flags", 1, "unsigned flags"),
+    ("void* a, void* b, void*** p", 3, "void*** p"),
+    ("float** rows", 1, "float** rows"),
+    ("long long n", 1, "long long n"),
+    ("struct plan p", 1, "struct plan p"),
+    ("int (*callback)(int)", 1, "int (*callback)(int)"),
+    ("int n[4]", 1, "int n[4]"),
+    ("int a, ", 2, ""),
+    ("char c", 1, "char c"),
+])
+def test_parse_header_refuses_a_parameter_it_has_no_rule_for(params, position,
+                                                             text):
+    """No default: a type outside the table of tike_amd/_lib.py is an
+    ImportError that names the entry, the position (from 1) and the text."""
+    with pytest.raises(ImportError) as e:
+        L.parse_header(f"int tike_ok(int n);\nint tike_bad({params});\n")
+    message = str(e.value)
+    assert "tike_bad" in message and f"parameter {position}:" in message
+    assert f"`{text}`" in message
+
+
+def test_parse_header_refuses_a_name_declared_twice():
+    with pytest.raises(ImportError, match="tike_twice"):
+        L.parse_header("int tike_twice(int n);\nint tike_twice(long n);\n")
+
+
+def test_parse_header_refuses_a_declaration_it_cannot_read():
+    """A `tike_name(` that the declaration pattern passes over (here: no
+    semicolon before the end) does not go missing from the table in silence."""
+    with pytest.raises(ImportError):
+        L.parse_header("int tike_a(int n);\nint tike_b(int n)\n")
+
+
+def test_the_real_header_through_the_parser(monkeypatch):
+    """127 int entries, the header's constants are the module's, and the
+    file is opened once per read -- `declared_symbols` and the version check
+    use what the import read."""
+    import builtins
+    opened = []
+    real_open = builtins.open
+
+    def counting_open(path, *args, **kwargs):
+        opened.append(path)
+        return real_open(path, *args, **kwargs)
+
+    monkeypatch.setattr(builtins, "open", counting_open)
+    constants, entries = L.read_header()
+    assert opened == [L.HEADER_PATH]
+    names = L.declared_symbols()
+    L._check_abi_version()
+    assert opened == [L.HEADER_PATH]
+    monkeypatch.undo()
+
+    assert len(entries) == 128 and entries["tike_build_id"] == ("const char*", [])
+    ints = {n: a for n, (ret, a) in entries.items() if ret == "int"}
+    assert len(ints) == 127 and sorted(ints) == names
+    assert list(ints) == list(L._PROTOTYPES)
+    for name, args in ints.items():
+        assert len(args) == len(L._PROTOTYPES[name]), name
+        assert all(a is b for a, b in zip(args, L._PROTOTYPES[name])), name
+    assert constants == {
+        "TIKE_ERR_ARG": L.ERR_ARG, "TIKE_ERR_UNSUPPORTED": L.ERR_UNSUPPORTED,
+        "TIKE_ERR_COMM": L.ERR_COMM, "TIKE_COMM_ID_BYTES": L.COMM_ID_BYTES,
+        "TIKE_ABI_VERSION": L.ABI_VERSION}
+    assert (L.ERR_ARG, L.ERR_UNSUPPORTED, L.ERR_COMM, L.COMM_ID_BYTES) == (
+        1000001, 1000002, 2000000, 128)
+
+
+def test_a_missing_header_is_an_import_error(monkeypatch, tmp_path):
+    monkeypatch.setattr(L, "HEADER_PATH", str(tmp_path / "tike_amd.h"))
+    with pytest.raises(ImportError, match="tike_amd.h not found"):
+        L.read_header()
+
+
+_TYPE_DUMP = r"""
+#include <cstdio>
+#include <type_traits>
+#include "tike_amd.h"
+template <class T> constexpr char letter() {
+    using B = std::remove_pointer_t<T>;
+    return std::is_same<T, int>::value ? 'i'
+         : std::is_same<T, long>::value ? 'l'
+         : std::is_same<T, float>::value ? 'f'
+         : std::is_same<T, double>::value ? 'd'
+         : std::is_same<T, void**>::value ? 'h'
+         : std::is_pointer<T>::value && !std::is_pointer<B>::value &&
+                   !std::is_function<B>::value ? 'p'
+         : '?';
+}
+template <class R, class... A> void show(const char* name, R (*)(A...)) {
+    const char args[] = {letter<A>()..., 0};
+    std::printf("%s %c %s\n", name,
+                std::is_same<R, int>::value ? 'i'
+                : std::is_same<R, const char*>::value ? 's' : '?', args);
+}
+int main() {
+@SHOW@
+    return 0;
+}
+"""
+
+
+def test_the_compiler_reads_the_header_as_the_binding_does(tmp_path):
+    """The types of every declaration as g++ sees them (one letter per
+    parameter from std::is_same / std::is_pointer on decltype(&tike_name):
+    unevaluated, so the program links without the library) against the ctypes
+    classes the binding derived: an int for a long, a float for a double or
+    two neighbours swapped would show here, on the CPU."""
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(L.HEADER_PATH).read(),
+                  flags=re.S)
+    names = re.findall(r"\b(tike_\w+)\s*\(", text)
+    assert len(names) == len(set(names)) == 128
+    src = tmp_path / "type_dump.cpp"
+    src.write_text(_TYPE_DUMP.replace("@SHOW@", "\n".join(
+        f'    show("{n}", decltype(&{n})(nullptr));' for n in names)))
+    exe = str(tmp_path / "type_dump")
+    subprocess.run(["g++", "-std=c++17", "-I", os.path.dirname(L.HEADER_PATH),
+                    str(src), "-o", exe], check=True, capture_output=True,
+                   timeout=300)
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    compiler = {}
+    for line in out.stdout.splitlines():
+        name, ret, args = line.split(" ")
+        compiler[name] = (ret, args)
+    letter = {_I: "i", _LONG: "l", _F: "f", _D: "d", _P: "p", _H: "h"}
+    binding = {name: ("i", "".join(letter[a] for a in args))
+               for name, args in L._PROTOTYPES.items()}
+    binding["tike_build_id"] = ("s", "")
+    assert sorted(compiler) == sorted(binding) == sorted(names)
+    wrong = {n: (compiler[n], binding[n]) for n in names
+             if compiler[n] != binding[n]}
+    assert not wrong, wrong
+
+
 def test_build_id_is_the_hash_of_the_sources_in_the_tree():
     """`tike_build_id()` = sha256 over the sources in the Makefile's order: the
     loaded library was built from THIS tree (profiles/*_pmc_traffic_*.json

@@ -3,6 +3,9 @@
 The shared library is built in-tree (``tike_amd/csrc/libtike_amd.so``) by
 ``tike_amd/csrc/Makefile`` (``__graft_entry__.build()``).  There is no CPU
 fallback: if the library is missing, importing this module raises.
+
+The argument types of every entry are read from the header, once, at import
+(``parse_header``): the header is the only place a signature is written down.
 """
 import ctypes
 import os
@@ -20,12 +23,77 @@ LIB_PATH = os.environ.get("TIKE_AMD_LIB") or os.path.join(
     _HERE, "csrc", "libtike_amd.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "tike_amd.h")
 
-# the header version this binding's prototypes were written against
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long,
+            "float": ctypes.c_float, "double": ctypes.c_double}
+# [const] BASE [*...] [const] [name]; BASE is one word, or `unsigned` and one
+_PARAMETER = re.compile(
+    r"(?:const\s+)?((?:unsigned\s+)?\w+)\s*(\**)\s*(?:const\b\s*)?(?:\w+)?")
+
+
+def _argtype(name, position, text):
+    """The ctypes class of one parameter.  A spelling outside the rules is
+    refused, never guessed: ctypes would truncate or reinterpret the value
+    without a word."""
+    m = _PARAMETER.fullmatch(text)
+    base, stars = m.groups() if m else (None, None)
+    if stars == "" and base in _SCALARS:
+        return _SCALARS[base]
+    if stars == "*":
+        return ctypes.c_void_p
+    if stars == "**" and base == "void":
+        return ctypes.POINTER(ctypes.c_void_p)
+    raise ImportError(
+        f"include/tike_amd.h: {name}, parameter {position}: no ctypes type "
+        f"for `{text}`")
+
+
+def parse_header(text):
+    """(constants, entries) of the text of a header: every `#define TIKE_*`
+    with an integer value by name, and for every declaration
+    `RET tike_name(PARAMS);`, in order, name -> (RET, [ctypes class, ...])."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {name: int(value) for name, value in re.findall(
+        r"^[ \t]*#[ \t]*define[ \t]+(TIKE_\w+)[ \t]+(-?\d+)[ \t]*$", text,
+        flags=re.M)}
+    entries = {}
+    for ret, name, params in re.findall(
+            r"^[ \t]*(\w[\w \t*]*?)\s*\b(tike_\w+)\s*\((.*?)\)\s*;", text,
+            flags=re.M | re.S):
+        if name in entries:
+            raise ImportError(f"include/tike_amd.h declares {name} twice")
+        params = [" ".join(p.split()) for p in params.split(",")]
+        if params in ([""], ["void"]):
+            params = []
+        entries[name] = (" ".join(ret.split()), [
+            _argtype(name, k, p) for k, p in enumerate(params, 1)])
+    if len(entries) != len(re.findall(r"\btike_\w+\s*\(", text)):
+        raise ImportError(
+            "include/tike_amd.h: a `tike_name(` that is no declaration "
+            "`RET tike_name(PARAMS);` at the start of a line")
+    return constants, entries
+
+
+def read_header():
+    """parse_header of include/tike_amd.h (one read of the file)."""
+    if not os.path.isfile(HEADER_PATH):
+        raise ImportError(
+            f"{HEADER_PATH} not found: the binding reads every prototype from "
+            "the header; `include/` travels with the package.")
+    with open(HEADER_PATH) as f:
+        return parse_header(f.read())
+
+
+_CONSTANTS, _ENTRIES = read_header()
+
+# the header version this package's call sites were written against
 ABI_VERSION = 25
-ERR_ARG = 1000001
-ERR_UNSUPPORTED = 1000002
-ERR_COMM = 2000000
-COMM_ID_BYTES = 128
+try:
+    ERR_ARG = _CONSTANTS["TIKE_ERR_ARG"]
+    ERR_UNSUPPORTED = _CONSTANTS["TIKE_ERR_UNSUPPORTED"]
+    ERR_COMM = _CONSTANTS["TIKE_ERR_COMM"]
+    COMM_ID_BYTES = _CONSTANTS["TIKE_COMM_ID_BYTES"]
+except KeyError as e:
+    raise ImportError(f"{HEADER_PATH} does not define {e.args[0]}") from e
 
 if not os.path.isfile(LIB_PATH):
     raise ImportError(
@@ -35,208 +103,10 @@ if not os.path.isfile(LIB_PATH):
 
 lib = ctypes.CDLL(LIB_PATH)
 
-_p = ctypes.c_void_p
-_i = ctypes.c_int
-_l = ctypes.c_long
-_f = ctypes.c_float
-_d = ctypes.c_double
-
-_PROTOTYPES = {
-    "tike_abi_version": [],
-    "tike_max_grid_dim_y": [],
-    "tike_init": [],
-    "tike_set_deterministic": [_i, _p, _l],
-    "tike_patch_fwd": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
-    "tike_patch_adj": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "tike_conv_fwd": [_p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p],
-    "tike_conv_adj": [_p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p],
-    "tike_conv_adj_probe": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
-    "tike_fft2": [_p, _p, _l, _i, _i, _f, _p],
-    "tike_fft2_supported": [_i],
-    "tike_fft2_general": [_p, _p, _l, _i, _i, _f, _i, _i, _p],
-    "tike_pfa_supported": [_i, _i, _i],
-    "tike_pfa_fwd_gather": [_p, _p, _p, _i, _p, _p, _p, _i, _i, _p, _p, _i, _i, _i,
-                            _i, _i, _i, _p],
-    "tike_pfa_fwd_subtiles_supported": [_i, _i, _i],
-    "tike_pfa_fwd_subtiles": [_p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _i, _i,
-                              _i, _i, _i, _i, _p],
-    "tike_pfa_fft2": [_p, _p, _l, _i, _i, _p],
-    "tike_pfa_combine_gradient": [_p, _p, _p, _p, _i, _i, _i, _f, _i, _f, _l, _i,
-                                  _p],
-    "tike_pfa_inv_products": [_p, _p, _p, _i, _p, _p, _p, _i, _i, _p, _p, _p, _f,
-                              _i, _i, _i, _i, _f, _p],
-    "tike_gen_supported": [_i, _i, _i],
-    "tike_gen_fwd_rows": [_p, _p, _p, _i, _p, _p, _p, _i, _i, _p, _p, _i, _i, _i,
-                          _i, _i, _i, _p],
-    "tike_gen_cols_gradient": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _f,
-                               _l, _p],
-    "tike_gen_inv_rows_gradients": [_p, _p, _p, _i, _p, _p, _p, _i, _i, _p, _p,
-                                    _p, _f, _i, _i, _i, _i, _f, _p],
-    "tike_fresnel_spect_prop": [_p, _p, _p, _l, _i, _i, _f, _f, _p],
-    "tike_fft2_pass1": [_p, _p, _l, _i, _i, _p],
-    "tike_fft2_pass2_inplace": [_p, _l, _i, _i, _f, _p],
-    "tike_slice_step": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p],
-    "tike_slice_step_back": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f,
-                             _p],
-    "tike_fft2_pass2_intensity": [_p, _p, _l, _i, _i, _i, _f, _i, _p],
-    "tike_fresnel_colpass": [_p, _p, _i, _p, _l, _i, _f, _p],
-    "tike_ifft2_pass2_products": [_p, _p, _p, _p, _i, _p, _p, _f, _p, _i, _i, _i,
-                                  _i, _i, _i, _f, _p],
-    "tike_ptycho_fwd": [_p, _p, _p, _i, _p, _p, _i, _i, _p, _i, _i, _i, _i,
-                        _i, _i, _f, _i, _p],
-    "tike_ptycho_adj": [_p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i,
-                        _i, _f, _i, _p],
-    "tike_ifft2_crop": [_p, _p, _p, _l, _i, _i, _f, _p],
-    "tike_ptycho_fwd_intensity": [_p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p,
-                                  _i, _i, _i, _i, _i, _i, _f, _p],
-    "tike_gradient_scale": [_p, _p, _p, _p, _p, _i, _i, _i, _f, _l, _p],
-    "tike_ifft2_crop_scaled": [_p, _p, _i, _p, _p, _l, _i, _i, _f, _p],
-    "tike_ifft2_crop_scaled_modes": [_p, _p, _p, _p, _i, _p, _p, _l, _i, _i, _f,
-                                     _p],
-    "tike_poisson_steps": [_p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _i, _p],
-    "tike_poisson_steps_handoff": [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _f,
-                                   _f, _l, _f, _f, _p],
-    "tike_scale_modes": [_p, _p, _p, _l, _i, _p],
-    "tike_ptycho_fwd_intensity_only": [_p, _p, _p, _i, _p, _p, _i, _i, _p, _p,
-                                       _i, _i, _i, _i, _i, _i, _f, _p],
-    "tike_ptycho_fwd_gradient_scale": [_p, _p, _p, _i, _p, _p, _i, _i, _p, _p,
-                                       _p, _p, _p, _p, _p, _i, _i, _i, _i, _i,
-                                       _i, _f, _i, _f, _l, _p],
-    "tike_fwd_pass1": [_p, _p, _p, _i, _p, _p, _p, _i, _i, _p, _p, _i, _i, _i,
-                       _i, _i, _i, _p],
-    "tike_fwd_gradient_scale": [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _f,
-                                _i, _f, _l, _p],
-    "tike_grad_ifft2_pass1": [_p, _p, _p, _p, _i, _p, _l, _i, _f, _p],
-    "tike_fwd_grad_ifft2_pass1": [_p, _p, _i, _p, _p, _p, _i, _i, _i, _f, _i, _f,
-                                  _l, _p],
-    "tike_fwd_grad_ifft2_pass1_slices": [_p, _p, _i, _p, _p, _p, _i, _i, _i, _f, _i, _f,
-                                  _l, _p, _i, _p],
-    "tike_ifft2_pass1_scaled": [_p, _p, _p, _p, _i, _p, _l, _i, _p],
-    "tike_ifft2_pass2_gradients": [_p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _f,
-                                   _i, _i, _i, _f, _p],
-    "tike_ifft2_pass2_gradients_scaled": [_p, _p, _p, _p, _p, _i, _i, _p, _p,
-                                          _p, _f, _i, _i, _i, _f, _p, _p],
-    "tike_ifft2_pass2_eigen_fits": [_i, _i, _i],
-    "tike_ifft2_pass2_gradients_modes": [_p, _p, _p, _p, _p, _i, _i, _p, _p,
-                                         _p, _f, _i, _i, _i, _f, _i, _i, _i, _p],
-    "tike_poisson_steps_grad_ifft2_pass1": [_p, _p, _i, _p, _p, _p, _p, _p, _i,
-                                            _i, _i, _f, _f, _l, _f, _f, _p],
-    "tike_object_update_precond": [_p, _p, _p, _f, _p, _p, _p, _l, _p],
-    "tike_lstsq_step_sums": [_p, _p, _i, _f, _p, _p],
-    "tike_lstsq_step_solve": [_p, _i, _f, _p, _d, _i, _i, _p, _p],
-    "tike_probe_update": [_p, _p, _p, _p, _f, _l, _p],
-    "tike_eigen_weights0": [_p, _p, _i, _i, _i, _i, _p, _p],
-    "tike_eigen_proj_mean": [_p, _i, _p, _l, _p, _l, _i, _p, _p],
-    "tike_eigen_normalise": [_p, _p, _d, _f, _i, _p, _p, _p],
-    "tike_eigen_dsum": [_p, _i, _l, _p, _p],
-    "tike_eigen_weights": [_p, _i, _l, _p, _d, _p, _l, _p, _i, _p, _p],
-    "tike_grad_ifft2_crop": [_p, _p, _p, _p, _i, _p, _p, _l, _i, _i, _f, _f,
-                             _p],
-    "tike_position_sums": [_p, _p, _i, _p, _p, _p, _i, _i, _p, _i, _p, _p, _i,
-                           _i, _i, _p],
-    "tike_rpie_position_sums": [_p, _p, _p, _p, _i, _p, _p, _i, _i, _p, _i, _p,
-                                _p, _p, _i, _i, _i, _i, _i, _p],
-    "tike_farplane_gradient": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _l,
-                               _p],
-    "tike_intensity": [_p, _p, _l, _i, _l, _p],
-    "tike_cost_each_pattern": [_p, _p, _p, _l, _l, _i, _p],
-    "tike_objective_grad": [_p, _p, _p, _p, _l, _i, _l, _i, _p],
-    "tike_lstsq_gradients": [_p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _i,
-                             _i, _i, _i, _i, _p],
-    "tike_varying_probe": [_p, _p, _p, _i, _i, _p, _i, _i, _i, _p],
-    "tike_scatter_patches": [_p, _p, _p, _i, _i, _i, _i, _p],
-    "tike_eigen_position_sums": [_p, _p, _p, _p, _p, _i, _i, _i, _p, _i, _i,
-                                 _i, _p],
-    "tike_eigen_pixel_update": [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _i, _i,
-                                _i, _p],
-    "tike_probe_grad": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
-    "tike_probe_preconditioner": [_p, _p, _p, _i, _i, _i, _i, _p],
-    "tike_psi_preconditioner": [_p, _p, _p, _i, _i, _i, _i, _p],
-    "tike_scatter_amplitudes": [_p, _p, _p, _i, _i, _i, _i, _p],
-    "tike_lstsq_step_stats": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p,
-                              _p, _i, _i, _i, _i, _i, _i, _p, _p, _p],
-    "tike_eigen_pixel_update1": [_p, _p, _p, _p, _p, _p, _l, _p, _p, _i, _i, _i,
-                                 _p, _p, _f, _p, _p, _p, _i, _i, _p],
-    "tike_lstsq_tail_mid": [_p, _p, _i, _p, _f, _p, _i, _f, _p, _d, _i, _i, _p,
-                            _p],
-    "tike_eigen_position_sums1": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p,
-                                  _i, _i, _p],
-    "tike_lstsq_tail_finish": [_p, _p, _d, _p, _p, _p, _p, _f, _l, _p, _l, _i,
-                               _i, _p, _p, _i, _i, _p],
-    "tike_ifft2_pass2_gradients_eproj": [_p, _p, _p, _p, _p, _i, _i, _p, _p,
-                                         _p, _f, _i, _i, _i, _f, _p, _p, _p],
-    "tike_eigen_pixel_update1q": [_p, _p, _p, _p, _p, _p, _l, _p, _p, _i, _i,
-                                  _i, _p, _p, _i, _i, _p, _p, _p],
-    "tike_lstsq_step_stats_eigen1": [_p, _p, _p, _p, _p, _p, _i, _p, _p, _p,
-                                     _p, _d, _f, _p, _p, _i, _i, _i, _i, _i,
-                                     _i, _p],
-    "tike_lstsq_tail_solve1": [_p, _p, _i, _p, _f, _p, _p, _p, _i, _f, _d, _i,
-                               _i, _p, _p, _p],
-    "tike_lstsq_chunk_gradients": [_p, _p, _p, _p, _p, _i, _i, _p, _i, _p, _i,
-                                   _f, _l, _p, _p, _p, _p, _p, _p, _p, _p, _f,
-                                   _p, _i, _i, _i, _i, _i, _f, _f, _p],
-    "tike_lstsq_chunk_gradients_positions": [
-        _p, _p, _p, _p, _p, _i, _i, _p, _i, _p, _i, _f, _l, _p, _p, _p, _p, _p,
-        _p, _p, _p, _f, _p, _i, _i, _i, _i, _i, _f, _f, _p, _i, _p, _p, _p, _p],
-    "tike_cgrad_direction": [_p, _p, _p, _p, _l, _i, _p, _i, _d, _p, _p, _p],
-    "tike_cgrad_line_search": [_i, _p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i,
-                               _i, _i, _i, _i, _f, _d, _p, _p, _i, _p],
-    "tike_cgrad_line_search_linear": [_i, _p, _p, _p, _p, _p, _p, _i, _p, _i, _p,
-                                      _p, _i, _i, _i, _i, _i, _i, _f, _d, _p, _i,
-                                      _p, _p],
-    "tike_cgrad_line_search_masked": [_i, _p, _p, _p, _p, _p, _p, _i, _p, _p,
-                                      _i, _i, _i, _i, _i, _i, _f, _d, _p, _p,
-                                      _i, _p, _i, _l, _p],
-    "tike_cgrad_line_search_linear_masked": [_i, _p, _p, _p, _p, _p, _p, _i, _p,
-                                             _i, _p, _p, _i, _i, _i, _i, _i, _i,
-                                             _f, _d, _p, _i, _p, _p, _i, _l, _p],
-    "tike_position_pd_sums": [_p, _p, _p, _p, _i, _f, _p, _p, _l, _i, _l, _p],
-    "tike_fly_farplane_gradient": [_p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i,
-                                   _i, _f, _l, _p],
-    "tike_farplane_scale": [_p, _p, _l, _i, _l, _f, _p],
-    "tike_scan_gradient": [_p, _p, _p, _p, _l, _i, _i, _i, _p],
-    "tike_scan_gradient_slices": [_p, _l, _p, _p, _p, _l, _i, _i, _i, _i, _p],
-    "tike_eigen_probe_gradients": [_p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p,
-                                   _p, _p, _l, _i, _i, _i, _i, _p],
-    "tike_conv_fwd_tangent": [_p, _p, _p, _p, _p, _p, _p, _l, _i, _i, _i, _i,
-                              _i, _p],
-    "tike_slice_wave_tangent": [_p, _p, _p, _p, _p, _i, _p, _i, _p, _l, _i, _i,
-                                _i, _i, _p],
-    "tike_intensity_tangent": [_p, _p, _p, _p, _l, _i, _l, _p],
-    "tike_eigen_wave_tangent": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i,
-                                _p, _l, _i, _i, _i, _i, _i, _p],
-    "tike_cost_factor": [_p, _p, _i, _p, _p, _p, _p, _l, _i, _l, _i, _l, _p],
-    "tike_cost_curvature": [_p, _p, _p, _i, _p, _p, _p, _p, _p, _l, _i, _l, _i,
-                            _f, _l, _p],
-    "tike_binned_farplane_gradient": [_p, _p, _i, _p, _p, _p, _i, _i, _i, _i,
-                                      _i, _i, _i, _f, _l, _p],
-    "tike_binned_cost_factor": [_p, _p, _i, _p, _p, _p, _p, _l, _i, _l, _i, _l,
-                                _i, _i, _p],
-    "tike_background_farplane_gradient": [_p, _p, _i, _p, _p, _p, _p, _i, _i,
-                                          _i, _i, _i, _i, _f, _l, _p],
-    "tike_background_cost_factor": [_p, _p, _i, _p, _p, _p, _p, _p, _l, _i, _l,
-                                    _i, _l, _p],
-    "tike_background_sums_partials": [_l],
-    "tike_background_sums": [_p, _p, _i, _p, _p, _p, _p, _p, _l, _l, _i, _l,
-                             _p],
-    "tike_blur_cost_factor": [_p, _p, _i, _p, _i, _p, _p, _p, _p, _p, _l, _i, _i,
-                              _l, _p],
-    "tike_blur_kernel_sums_partials": [_i, _i],
-    "tike_blur_kernel_sums": [_p, _p, _i, _p, _i, _p, _p, _p, _p, _l, _i, _i, _l,
-                              _p],
-    "tike_nearfield_cost_partials": [_l],
-    "tike_nearfield_plane_gradient": [_p, _p, _i, _p, _p, _p, _p, _p, _p, _l, _i,
-                                      _i, _i, _i, _l, _f, _f, _p],
-    "tike_dm_reflect": [_p, _p, _p, _p, _p, _f, _l, _i, _i, _i, _i, _i, _p],
-    "tike_dm_update": [_p, _p, _p, _p, _p, _f, _p, _l, _i, _i, _i, _i, _i, _p],
-    "tike_comm_unique_id": [_p],
-    "tike_comm_create": [_p, _i, _i, ctypes.POINTER(_p)],
-    "tike_comm_destroy": [_p],
-    "tike_comm_allreduce_sum": [_p, _p, _l, _i, _p],
-    "tike_comm_broadcast": [_p, _p, _l, _i, _p],
-    "tike_cluster_farthest_fill": [_p, _l, _p, _i, _l],
-    "tike_cluster_swap_sweep": [_p, _l, _i, _p, _p, _p, _p, _p],
-}
+# name -> argtypes of every entry that returns int (tike_build_id does not),
+# in the header's order
+_PROTOTYPES = {name: args for name, (ret, args) in _ENTRIES.items()
+               if ret == "int"}
 
 
 def build_id():
@@ -252,10 +122,8 @@ def build_id():
 
 
 def declared_symbols():
-    """Names of every function declared in include/tike_amd.h."""
-    with open(HEADER_PATH) as f:
-        text = f.read()
-    return sorted(set(re.findall(r"^int\s+(tike_\w+)\s*\(", text, flags=re.M)))
+    """Names of every `int tike_*` entry declared in include/tike_amd.h."""
+    return sorted(_PROTOTYPES)
 
 
 for _name, _args in _PROTOTYPES.items():
@@ -271,15 +139,14 @@ for _name, _args in _PROTOTYPES.items():
 
 def _check_abi_version():
     """Refuse a library built from another header: its entries would take
-    this binding's positional arguments for something else."""
+    this package's positional arguments for something else."""
     got = lib.tike_abi_version()
-    m = re.search(r"^#define\s+TIKE_ABI_VERSION\s+(\d+)", open(HEADER_PATH).read(),
-                  flags=re.M) if os.path.isfile(HEADER_PATH) else None
-    if got != ABI_VERSION or (m and int(m.group(1)) != ABI_VERSION):
+    header = _CONSTANTS.get("TIKE_ABI_VERSION")
+    if got != ABI_VERSION or header != ABI_VERSION:
         raise ImportError(
             f"{LIB_PATH} reports ABI version {got}, include/tike_amd.h "
-            f"{m.group(1) if m else '?'}, this binding expects {ABI_VERSION}: "
-            "rebuild the library (`make -C tike_amd/csrc`).")
+            f"{'?' if header is None else header}, this binding expects "
+            f"{ABI_VERSION}: rebuild the library (`make -C tike_amd/csrc`).")
 
 
 _check_abi_version()
